@@ -9,12 +9,22 @@ One process per GPU; movies are independent, so ranks never exchange data (weak
 scaling: one stack per rank per step).  torch.distributed (RCCL) is used only for the
 start/stop barrier and the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (warp_rigid_dma):
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and
+reports the headline (`value`, `ms_per_step`); nothing else runs.
+
+--dump-outputs DIR writes what the last timed step returned, as float32 .npy files:
+`field.npy` (2, t, 1, 1) in full; `total.npy` and `frames.npy` flattened, or a fixed sample
+of DUMP_SAMPLE elements at seeded positions when the array is larger (about 32 MiB in all).
+The inputs depend on the arguments alone, so two builds can be compared output for output.
+
+--full adds everything that is not the headline, measured after it:
+`config.shifts_match_ground_truth`; `roofline` for the dominant kernel (warp_rigid_dma):
 algorithmic bytes per launch = 8 B/pixel/frame x 40 frames (each frame read once and
 written once) over its mean duration, measured with HIP events on
 the launch stream around each launch inside the timed region.  `cpu_baseline` is the
 CPU oracle (a port of the reference's torch-CPU op sequence; the reference itself
 cannot be imported) on a bounded sample of the same workload.
+`secondary`, `fp16_storage` and `raw_u8` are the other workloads (--no-secondary skips them).
 """
 
 from __future__ import annotations
@@ -35,6 +45,25 @@ try:
 except Exception:
     METRIC = "frames/sec motion-corrected, 40x4kx4k fp32 stack, 1/2/4/8 MI355X"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_SAMPLE = 1 << 22  # elements kept of each large output by --dump-outputs (16 MiB of float32)
+
+
+def dump_outputs(res, path):
+    """The arrays a caller of the timed path receives (a MovieResult), as float32 .npy files."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name in ("field", "total", "frames"):
+        x = getattr(res, name)
+        if x is None:
+            continue
+        if name != "field":
+            x = x.reshape(-1)
+            if x.numel() > DUMP_SAMPLE:
+                g = torch.Generator().manual_seed(20240611)
+                idx = torch.randint(0, x.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+                x = x[idx.to(x.device)]
+        np.save(os.path.join(path, name + ".npy"), x.float().cpu().numpy())
 
 
 def synth_stack(t, h, w, seed, device, noise=1.0, pad=64):
@@ -84,7 +113,13 @@ def main():
     ap.add_argument("--no-overlap", action="store_true",
                     help="one stream: every step's estimator waits for the previous step's warp")
     ap.add_argument("--cpu-frames", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline (roofline, CPU baseline + parity, "
+                         "other workloads)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -151,18 +186,21 @@ def main():
     run_steps(args.warmup, False)
     barrier()
     t0 = time.perf_counter()
-    out = run_steps(args.steps, True)
+    out = run_steps(args.steps, args.full)
     barrier()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+    # the measurements and checks below run with --full only, after the timed steps
 
     # the same launch with the chip to itself (outside the timed region): under --overlap the
     # timed launches share HBM with the next step's estimator, which stretches them
     solo_ms = None
-    if not args.no_overlap:
+    if args.full and not args.no_overlap:
         lat = engine.frame_lattices(out.field.contiguous(), t, "catmull_rom")
         ev = []
 
@@ -184,7 +222,7 @@ def main():
     # what this box sustains on a plain copy of buffers larger than the Infinity Cache (read + write
     # bytes per second): the practical ceiling next to the 8 TB/s spec the fractions are quoted against
     copy_rate = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             a0 = torch.empty(1 << 28, dtype=torch.float32, device=dev)  # 1 GiB
             b0 = torch.empty_like(a0)
@@ -200,14 +238,15 @@ def main():
             del a0, b0
         except Exception:
             copy_rate = None
-    shifts = (out.field[:, :, 0, 0].transpose(0, 1) / 1.0).cpu()
-    shifts_ok = bool(torch.equal(shifts, expect))
+    if args.full:
+        shifts = (out.field[:, :, 0, 0].transpose(0, 1) / 1.0).cpu()
+        shifts_ok = bool(torch.equal(shifts, expect))
     warp_ms = sum(a.elapsed_time(b) for a, b in warp_events) / max(len(warp_events), 1) if warp_events else float("nan")
     alg_bytes = 8.0 * h * w * t  # read + write of every frame, once
     achieved = alg_bytes / (warp_ms * 1e-3) / 1e9 if warp_events else float("nan")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # N = 1 only (contract)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # N = 1 only (contract)
         import oracle
 
         n = min(args.cpu_frames, t)
@@ -238,7 +277,7 @@ def main():
     # The same steps on the same stacks STORED as fp16 (reported, never the headline value): K1 and the
     # rigid warp read the 16-bit samples as they are (8 instead of 12 compulsory B/pixel/frame)
     half_storage = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         try:
             sa, sb = stack.half(), stack_b.half()
             n16 = max(10, args.steps // 4)
@@ -265,7 +304,7 @@ def main():
     # through the fused raw pipeline (statistics pass + K1 and the rigid warp conditioning on the fly: no fp32
     # movie), next to conditioning into an fp32 movie first (mc.condition_movie) and the headline pipeline
     raw_u8 = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         try:
             gq = torch.Generator(device=dev).manual_seed(99)
             gain = (1.0 + 0.05 * torch.randn(h, w, generator=gq, device=dev)).clamp(0.7, 1.3)
@@ -324,7 +363,7 @@ def main():
     # Secondary workload (reported, never the headline value): BASELINE.json configs[2], local
     # motion on a K3-sized stack -- 1024-px patches (6 x 10), B-spline warp, frame sum.
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         try:
             del out
             torch.cuda.empty_cache()
@@ -418,7 +457,7 @@ def main():
 
     traffic = None
     tp = os.path.join(ROOT, "profiles", "warp_traffic.json")
-    if os.path.exists(tp):
+    if args.full and os.path.exists(tp):
         try:
             traffic = json.load(open(tp)).get("hbm_bytes_per_launch")
         except Exception:
@@ -445,9 +484,11 @@ def main():
                             f"1 stack per GPU per step"
                             + ("" if args.no_overlap else ", consecutive steps overlapped on two HIP streams"),
                 "pixel_spacing": 1.0, "b_factor": 500, "frequency_range": [300, 10],
-                "shifts_match_ground_truth": shifts_ok,
             },
-            "roofline": {
+        }
+        if args.full:
+            line["config"]["shifts_match_ground_truth"] = shifts_ok
+            line["roofline"] = {
                 "bound": "hbm", "kernel": "warp_rigid_dma", "achieved": achieved, "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                 # `traffic` = HBM bytes per launch from the rocprofv3 PMC passes committed under
@@ -463,12 +504,8 @@ def main():
                 # kernel's ACTUAL traffic (`traffic`) over its unshared launch time sits on that line
                 "box_copy_rate": copy_rate,
                 "actual_traffic_rate_unshared": (traffic / (solo_ms * 1e-3) / 1e9) if (traffic and solo_ms) else None,
-            },
-            "cpu_baseline": cpu,
-            "secondary": secondary,
-            "fp16_storage": half_storage,
-            "raw_u8": raw_u8,
-        }
+            }
+            line.update(cpu_baseline=cpu, secondary=secondary, fp16_storage=half_storage, raw_u8=raw_u8)
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

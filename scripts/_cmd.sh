@@ -1,7 +1,7 @@
 cd $GRAFT_REPO_ROOT
 for tag in base k2nt base k2nt; do
   if [ $tag = base ]; then export MCORR_LIB=$PWD/torch_motion_correction_amd/libmcorr.so; else export MCORR_LIB=$PWD/variants/$tag/libmcorr.so; fi
-  python bench.py --steps 40 --warmup 5 --no-secondary --no-cpu-baseline 2>&1 | python -c "
+  python bench.py --steps 40 --warmup 5 --full --no-secondary --no-cpu-baseline 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
