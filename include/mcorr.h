@@ -92,6 +92,38 @@ int mc_raw_movie_stats(const void* raw, int kind, const float* gain, int nframes
                        int wl, int wu, int mean_zero, double* stats, float* mu, float* sub, float* mean_rstd,
                        void* stream);
 
+/* N2 with the hot-pixel step (examples/ttMotion.py:127-172; rule of mc_condition_movie_hot), still without a
+ * conditioned fp32 movie.  The raw K1 and the raw warp run on the unreplaced samples v = raw * gain; each hot
+ * pixel is then applied as a sparse correction by delta = r - v (r: its replacement), both consumers being
+ * linear in the sample.  Sequence per movie:
+ *  1. mc_raw_hot_detect: one pass for stats (as mc_raw_movie_stats, before replacement) and hstats[f][3] =
+ *     {sum v, sum v^2, -} of the whole frame, then the detection pass: every hot pixel takes a slot of the list
+ *     keys[i] = f*h*w + pixel index, rv[2i..] = {r, v}; *counter = number of hot pixels (may exceed `capacity`:
+ *     then only `capacity` entries were written and the list is unusable), counts[f] = per frame.  gain is
+ *     required (pass ones for none); w % 8 == 0 and 8-byte (u8) / 16-byte aligned raw, 16-byte aligned gain,
+ *     else MC_ERR_UNSUPPORTED.
+ *  2. the caller sorts the n = *counter entries by key (ascending) -- the fixed order every later step sums in.
+ *  3. mc_raw_hot_finalize: stats corrected for the replacement, then mu / sub / mean_rstd as
+ *     mc_raw_movie_stats gives them, for the frames AFTER replacement (mu rounded as mc_condition_movie_hot).
+ *  4. mc_xc_rows_hot_correct after K1 (mc_xc_rows_forward_raw / mc_xcg_rows_forward_raw) of frames
+ *     [frame0, frame0 + njobs): adds (r - v) * rstd * mask(y,x) * exp(-2 pi i kx x / W) to T1[f - frame0][kx][y - y0]
+ *     for every kept bin; one workgroup per (frame, row), no atomics.
+ *  5. after mc_warp_rigid_raw (its weight tables in `scratch`): mc_warp_rigid_hot_taps writes n * 49 records
+ *     (key = f*h*w + output pixel or INT64_MAX, value = (r - v) * the warp's weight of q for that output);
+ *     the caller sorts them stably by key (for the sum: by key mod h*w) and mc_hot_scatter_add adds every
+ *     run of equal keys < limit, summed in order, to out[key] (the frames, or the sum with limit = h*w). */
+int mc_raw_hot_detect(const void* raw, int kind, const float* gain, int nframes, int h, int w, int hl, int hu,
+                      int wl, int wu, float threshold, double* stats, double* hstats, long long* keys, float* rv,
+                      long long capacity, unsigned long long* counter, int* counts, void* stream);
+int mc_raw_hot_finalize(const long long* keys, const float* rv, int64_t n, int nframes, int h, int w, int hl, int hu,
+                        int wl, int wu, int mean_zero, const double* hstats, double* stats, float* mu, float* sub,
+                        float* mean_rstd, void* stream);
+int mc_xc_rows_hot_correct(const long long* keys, const float* rv, int64_t n, int frame0, int njobs, int h, int w,
+                           const float* mask, const float* mean_rstd, void* T1, const mc_xc_geom* geom, void* stream);
+int mc_warp_rigid_hot_taps(const long long* keys, const float* rv, int64_t n, int nframes, int h, int w,
+                           const float* scratch, long long* rec_key, float* rec_val, void* stream);
+int mc_hot_scatter_add(const long long* key, const float* val, int64_t m, int64_t limit, float* out, void* stream);
+
 /* Input conditioning of raw detector frames (caller-side steps of the reference's pipeline,
  * examples/ttMotion.py:90-121 gain multiply and :174-199 per-frame mean-zero):
  * out[f] = raw[f] * gain - mean(raw[f] * gain), fp32 out.  kind: storage type of raw, 0 = u8,

@@ -98,6 +98,11 @@ SIGNATURES = {
     "mc_rigid_tables_from_shifts": [vp, f32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "mc_warp_rigid_raw": [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp],
     "mc_condition_movie_hot": [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp],
+    "mc_raw_hot_detect": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp, vp, vp],
+    "mc_raw_hot_finalize": [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "mc_xc_rows_hot_correct": [vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, GP, vp],
+    "mc_warp_rigid_hot_taps": [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp],
+    "mc_hot_scatter_add": [vp, vp, i64, i64, vp, vp],
     "mc_spline_points": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp],
     "mc_dose_accumulate": [vp, i32, i32, i32, vp, i32, i32, f32, f32, f32, f32, i32, i32, vp],
     "mc_polyphase_fourier_shift": [vp, vp, i32, i32, i32, i32, vp],

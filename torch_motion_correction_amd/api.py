@@ -358,38 +358,64 @@ def condition_movie(movie, gain=None, mean_zero=True, device=None, hot_pixel_thr
     return res.to(out_dev)
 
 
-@_on_gpu
 def motion_correct_raw(movie, gain, pixel_spacing, reference_frame=None, b_factor=500, frequency_range=(300, 10),
-                       grid_type="catmull_rom", mean_zero=True, return_frames=False, device=None):
+                       grid_type="catmull_rom", mean_zero=True, return_frames=False, device=None,
+                       hot_pixel_threshold=None, return_hot_counts=False):
     """The reference pipeline's gain_correct -> set_frames_mean_zero -> estimate_global_motion -> correct_motion
     -> sum (examples/ttMotion.py:90-121, 180-199, 286-398) for a RAW uint8 / int16 movie, with the conditioning
     fused into the kernels that read the raw bytes: one statistics pass, then the estimator's row transform and
     the rigid warp compute ``raw * gain - frame mean`` on the fly.  No conditioned fp32 movie is allocated.
-    Returns ``(field (2,t,1,1) Angstrom, sum (h,w)[, frames (t,h,w)])`` -- what ``condition_movie`` followed by
-    ``estimate_global_motion`` and ``motion_correct_sum`` return.  Fused kernels exist for power-of-two frame
-    widths and the K3 formats (5760 / 11520 columns), rows of whole quads, at most 256 frames; any other shape
-    takes exactly that route, on an fp32 copy."""
+    Returns ``(field (2,t,1,1) Angstrom, sum (h,w)[, frames (t,h,w)][, hot counts (t,) int32])`` -- what
+    ``condition_movie`` followed by ``estimate_global_motion`` and ``motion_correct_sum`` return.  Fused kernels
+    exist for power-of-two frame widths and the K3 formats (5760 / 11520 columns), rows of whole quads, at most
+    256 frames; any other shape takes exactly that route, on an fp32 copy.
+
+    ``hot_pixel_threshold`` (the example uses 10.0) adds the example's remove_hot_pixels step
+    (examples/ttMotion.py:127-172) between the gain and the mean, with condition_movie's deterministic
+    replacement; the fused route applies the few hot pixels as sparse corrections (engine.RawMovie).  A threshold
+    that finds more hot pixels than the fused list holds takes the condition_movie route.  ``return_hot_counts``
+    appends the number of hot pixels per frame (zeros without a threshold)."""
+    thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # ValueError before any device is touched
+    return _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, grid_type,
+                               mean_zero, return_frames, device, thr, return_hot_counts)
+
+
+@_on_gpu
+def _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, grid_type, mean_zero,
+                        return_frames, device, thr, return_hot_counts):
     out_dev = _out_device(movie, device)
     dev = require_gpu(out_dev)
     raw = movie.detach().to(dev)
     t = raw.shape[0]
     ref = t // 2 if reference_frame is None else int(reference_frame)
     ps = float(pixel_spacing)
-    try:
-        rm = engine.RawMovie(raw, None if gain is None else gain.to(dev), mean_zero=bool(mean_zero))
-        shifts = engine.global_shifts_raw(rm, ref, ps, float(b_factor), tuple(frequency_range))
-        field = image_shifts_to_deformation_field(shifts, ps)
-        lat = engine.frame_lattices(field.contiguous(), t, grid_type)
-        frames, total = engine.warp_rigid_raw(rm, lat, ps, want_frames=bool(return_frames), want_sum=True)
-    except (McorrUnsupported, TypeError):
-        img = engine.condition_movie(raw, None if gain is None else gain.to(dev), bool(mean_zero))
+    gd = None if gain is None else gain.to(dev)
+    fused = raw.dtype in (torch.uint8, torch.int16)
+    counts = None
+    if fused:
+        try:
+            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
+            shifts = engine.global_shifts_raw(rm, ref, ps, float(b_factor), tuple(frequency_range))
+            field = image_shifts_to_deformation_field(shifts, ps)
+            lat = engine.frame_lattices(field.contiguous(), t, grid_type)
+            frames, total = engine.warp_rigid_raw(rm, lat, ps, want_frames=bool(return_frames), want_sum=True)
+            counts = rm.hot_counts
+        except McorrUnsupported:
+            fused = False
+    if not fused:
+        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr, return_hot_counts=thr is not None)
+        if thr is not None:
+            img, counts = img
         shifts = engine.global_shifts(img, ref, ps, float(b_factor), tuple(frequency_range))
         field = image_shifts_to_deformation_field(shifts, ps)
         lat = engine.frame_lattices(field.contiguous(), t, grid_type)
         frames, total = engine.warp(img, lat, ps, want_frames=bool(return_frames), want_sum=True, rigid=True)
+    out = [field.to(out_dev), total.to(out_dev)]
     if return_frames:
-        return field.to(out_dev), total.to(out_dev), frames.to(out_dev)
-    return field.to(out_dev), total.to(out_dev)
+        out.append(frames.to(out_dev))
+    if return_hot_counts:
+        out.append(torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None else counts.to(out_dev))
+    return tuple(out)
 
 
 @_on_gpu

@@ -517,6 +517,301 @@ __global__ __launch_bounds__(256) void cond_hot_kernel(const void* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------ N2 + hot pixels: sparse corrections
+// The fused raw path with the hot-pixel step (mc_raw_hot_detect ... mc_hot_scatter_add, include/mcorr.h).
+// Hot pixels are sparse and the estimator's row transform and the rigid warp are linear in the conditioned
+// sample, so the tuned raw kernels run on the UNREPLACED values v and each hot pixel is applied afterwards as
+// a correction by delta = r - v (r: its replacement).  Only the statistics must be known beforehand: the
+// hot-pixel limits need the whole frame's second moment, the frame means and the box statistics are those
+// of the frames after replacement.
+//
+// pass 1, raw_stats_hot_kernel: raw_stats_kernel's {sum v, sum_box v, sum_box v^2} into stats[f][3] and the
+// detection moments {sum v, sum v^2} into hstats[f][3] (cond_stats2_kernel's layout: hot_limits reads it).
+// Whole-frame terms are fp32 partial sums of 8 samples, accumulated in double (cond_stats2_kernel sums every
+// sample in double: the limits agree to the rounding of those partials, ~1e-11 of the frame's variance).
+template <int KIND>
+__global__ __launch_bounds__(256) void raw_stats_hot_kernel(const void* __restrict__ raw, const float* __restrict__ gain,
+                                                            int h, int w, int nframes, int hl, int hu, int wl, int wu,
+                                                            double* __restrict__ stats, double* __restrict__ hstats) {
+  const int f0 = blockIdx.y * COND_FR;
+  const int64_t hw = (int64_t)h * w;
+  double sa[COND_FR], sq[COND_FR], sb[COND_FR], qb[COND_FR];
+#pragma unroll
+  for (int ff = 0; ff < COND_FR; ++ff) sa[ff] = sq[ff] = sb[ff] = qb[ff] = 0.0;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < hw; i += (int64_t)gridDim.x * 256 * 8) {
+    float g[8];
+    {
+      const float4 a = *reinterpret_cast<const float4*>(gain + i), b = *reinterpret_cast<const float4*>(gain + i + 4);
+      g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w; g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
+    }
+    const int y = (int)(i / w), x = (int)(i - (int64_t)y * w);
+    float bw[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) bw[k] = (y >= hl && y < hu && x + k >= wl && x + k < wu) ? 1.f : 0.f;
+    const bool any_box = y >= hl && y < hu && x + 7 >= wl && x < wu;
+#pragma unroll
+    for (int ff = 0; ff < COND_FR; ++ff) {
+      if (f0 + ff >= nframes) break;
+      float v[8];
+      cond_load8<KIND>(raw, (int64_t)(f0 + ff) * hw + i, v);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] *= g[k];
+      sa[ff] += (double)(((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7])));
+      sq[ff] += (double)(((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) +
+                         ((v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7])));
+      if (any_box) {
+        float ps = 0.f, pq = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          ps = __builtin_fmaf(bw[k], v[k], ps);
+          pq = __builtin_fmaf(bw[k] * v[k], v[k], pq);
+        }
+        sb[ff] += (double)ps;
+        qb[ff] += (double)pq;
+      }
+    }
+  }
+  __shared__ double part[COND_FR][4][4];
+#pragma unroll
+  for (int ff = 0; ff < COND_FR; ++ff) {
+    double r0 = sa[ff], r1 = sb[ff], r2 = qb[ff], r3 = sq[ff];
+    for (int off = 32; off > 0; off >>= 1) {
+      r0 += __shfl_down(r0, off);
+      r1 += __shfl_down(r1, off);
+      r2 += __shfl_down(r2, off);
+      r3 += __shfl_down(r3, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      part[ff][0][threadIdx.x >> 6] = r0;
+      part[ff][1][threadIdx.x >> 6] = r1;
+      part[ff][2][threadIdx.x >> 6] = r2;
+      part[ff][3][threadIdx.x >> 6] = r3;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < COND_FR * 4) {
+    const int ff = threadIdx.x / 4, c = threadIdx.x - 4 * ff;
+    if (f0 + ff < nframes) {
+      const double r = (part[ff][c][0] + part[ff][c][1]) + (part[ff][c][2] + part[ff][c][3]);
+      if (c < 3) atomicAdd(&stats[3 * (f0 + ff) + c], r);
+      if (c == 0) atomicAdd(&hstats[3 * (f0 + ff)], r);
+      if (c == 3) atomicAdd(&hstats[3 * (f0 + ff) + 1], r);
+    }
+  }
+}
+
+// pass 2: cond_hot_kernel<KIND, 0>'s detection and replacement (hot_limits, hot_replacement: the same rule
+// bit for bit), with the gain tile in registers over COND_FR frames as in pass 1.  Every hot pixel takes a
+// slot of the list: key = f * h * w + pixel index, rv = {r, v}.  Beyond `cap` slots nothing is written, the
+// counter keeps counting (the host sees the overflow).
+template <int KIND>
+__global__ __launch_bounds__(256) void raw_hot_detect_kernel(const void* __restrict__ raw, const float* __restrict__ gain,
+                                                             int h, int w, int nframes, float thr,
+                                                             const double* __restrict__ hstats,
+                                                             long long* __restrict__ keys, float2* __restrict__ rv,
+                                                             long long cap, unsigned long long* __restrict__ counter,
+                                                             int* __restrict__ counts) {
+  const int f0 = blockIdx.y * COND_FR;
+  const int64_t hw = (int64_t)h * w;
+  float lo[COND_FR], hi[COND_FR];
+#pragma unroll
+  for (int ff = 0; ff < COND_FR; ++ff) {
+    lo[ff] = hi[ff] = 0.f;
+    if (f0 + ff < nframes) {
+      const HotLimits L = hot_limits(hstats, f0 + ff, hw, thr);
+      lo[ff] = L.lo;
+      hi[ff] = L.hi;
+    }
+  }
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < hw; i += (int64_t)gridDim.x * 256 * 8) {
+    float g[8];
+    {
+      const float4 a = *reinterpret_cast<const float4*>(gain + i), b = *reinterpret_cast<const float4*>(gain + i + 4);
+      g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w; g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
+    }
+#pragma unroll
+    for (int ff = 0; ff < COND_FR; ++ff) {
+      if (f0 + ff >= nframes) break;
+      const int64_t base = (int64_t)(f0 + ff) * hw;
+      float v[8];
+      cond_load8<KIND>(raw, base + i, v);
+      unsigned hot = 0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        v[k] *= g[k];
+        hot |= (v[k] > hi[ff] || v[k] < lo[ff]) ? 1u << k : 0u;
+      }
+      while (hot) {  // rare: a handful of pixels per frame; the sample is formed again as cond_hot_kernel does
+        const int k = __builtin_ctz(hot);
+        hot &= hot - 1;
+        const int64_t j = i + k;
+        const HotLimits L = hot_limits(hstats, f0 + ff, hw, thr);
+        const float vk = cond_load<KIND>(raw, base + j) * gain[j];
+        const int y = (int)(j / w), x = (int)(j - (int64_t)y * w);
+        const float r = hot_replacement<KIND>(raw, gain, base, h, w, y, x, L);
+        const unsigned long long slot = atomicAdd(counter, 1ull);
+        if (slot < (unsigned long long)cap) {
+          keys[slot] = base + j;
+          rv[slot] = make_float2(r, vk);
+        }
+        atomicAdd(&counts[f0 + ff], 1);
+      }
+    }
+  }
+}
+
+// first index in keys[0, n) (ascending) that is >= k
+__device__ __forceinline__ int64_t hot_lower_bound(const long long* keys, int64_t n, long long k) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// pass 3 (list sorted by key): per frame, the corrections of the moments --
+//   sum v += sum (r - v);   sum_box v += sum_box (r - v);   sum_box v^2 += sum_box (r^2 - v^2)
+// in double; stats[3 f] becomes cond_hot_kernel's sum after replacement (stats[3f] + stats[3f+2] there), so
+// raw_stats_finalize rounds mu as mean_after.  One workgroup per frame, entries dealt to the threads in a
+// fixed way and a fixed reduction tree: no atomics, the same result every time.
+__global__ __launch_bounds__(256) void raw_hot_stats_fix(const long long* __restrict__ keys,
+                                                         const float2* __restrict__ rv, int64_t n, int nframes,
+                                                         int h, int w, int hl, int hu, int wl, int wu,
+                                                         const double* __restrict__ hstats,
+                                                         double* __restrict__ stats) {
+  const int f = blockIdx.x;
+  const int64_t hw = (int64_t)h * w;
+  __shared__ int64_t range[2];
+  __shared__ double red[3][256];
+  if (threadIdx.x < 2) range[threadIdx.x] = hot_lower_bound(keys, n, (long long)(f + threadIdx.x) * hw);
+  __syncthreads();
+  double d = 0.0, db = 0.0, qb = 0.0;
+  for (int64_t e = range[0] + threadIdx.x; e < range[1]; e += 256) {
+    const float2 p = rv[e];
+    const double r = (double)p.x, v = (double)p.y;
+    d += r - v;
+    const int64_t j = keys[e] - (long long)f * hw;
+    const int y = (int)(j / w), x = (int)(j - (int64_t)y * w);
+    if (y >= hl && y < hu && x >= wl && x < wu) {
+      db += r - v;
+      qb += r * r - v * v;
+    }
+  }
+  red[0][threadIdx.x] = d;
+  red[1][threadIdx.x] = db;
+  red[2][threadIdx.x] = qb;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s)
+      for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    stats[3 * f] = hstats[3 * f] + red[0][0];
+    stats[3 * f + 1] += red[1][0];
+    stats[3 * f + 2] += red[2][0];
+  }
+}
+
+// K1 correction.  K1 (raw) transformed A = (v - sub_f) * rstd * mask; a hot pixel's sample is
+// (r - sub_f) * rstd * mask, so every kept bin of its row gains  dA * exp(-2 pi i kx x / W),
+// dA = (r - v) * rstd * mask(y, x)  (the forward rfft convention of K1: no scale, negative exponent).
+// One workgroup per (frame, row) segment of the sorted list -- the workgroup of the segment's first entry;
+// the others return at once -- so every T1 element is written by one workgroup, in list order.
+__global__ __launch_bounds__(256) void xc_rows_hot_fix(const long long* __restrict__ keys, const float2* __restrict__ rv,
+                                                       int64_t n, int frame0, int njobs, int h, int w,
+                                                       const float* __restrict__ mask,
+                                                       const float* __restrict__ mean_rstd, cfloat* __restrict__ T1,
+                                                       int W, int nkx, int y0, int ny) {
+  const int64_t e0 = blockIdx.x;
+  if (e0 >= n) return;
+  const long long seg = keys[e0] / w;  // f * h + y
+  if (e0 > 0 && keys[e0 - 1] / w == seg) return;
+  const int f = (int)(seg / h), y = (int)(seg - (long long)f * h);
+  if (f < frame0 || f >= frame0 + njobs || y < y0 || y >= y0 + ny) return;
+  const float rstd = mean_rstd[1];
+  cfloat* col = T1 + (int64_t)(f - frame0) * nkx * ny + (y - y0);
+  for (int kx = threadIdx.x; kx < nkx; kx += 256) {
+    float ar = 0.f, ai = 0.f;
+    for (int64_t e = e0; e < n && keys[e] / w == seg; ++e) {
+      const int x = (int)(keys[e] - seg * w);
+      const float m = mask ? mask[(int64_t)y * w + x] : 1.f;
+      if (m == 0.f) continue;
+      const float2 p = rv[e];
+      const float dA = (p.x - p.y) * rstd * m;
+      const int ph = (int)(((int64_t)kx * x) % W);  // exact phase index; the angle in revolutions ph / W
+      const float rev = (float)ph / (float)W;        // in [0, 1): v_sin / v_cos take revolutions
+      ar += dA * __builtin_amdgcn_cosf(rev);
+      ai -= dA * __builtin_amdgcn_sinf(rev);
+    }
+    cfloat* o = col + (int64_t)kx * ny;
+    o->x += ar;
+    o->y += ai;
+  }
+}
+
+// Warp correction, step 1: hot pixel q of frame f adds delta * wy(py, qy) * wx(px, qx) to every output p
+// whose taps read q.  wy / wx are warp_rigid_raw's own weights from the tables in `scratch` (Wy[f][h][5],
+// Wx[f][5][w], S[f][2]: output p reads clip(p + S - 1 + k) with weight W[p][k], k = 0..4), summed over the
+// taps that clip onto q at the frame edge; outputs of the zero-outside rule have all-zero weights.  The
+// outputs lie in [q - S - 3, q - S + 1] per axis (clipped taps included); a 7 x 7 window around that covers
+// them.  One record (key = f h w + p, value) per window position, key HOT_NONE where the weight is zero.
+#define HOT_WIN 7
+#define HOT_NONE 0x7fffffffffffffffLL
+__global__ __launch_bounds__(256) void warp_rigid_hot_taps(const long long* __restrict__ keys,
+                                                           const float2* __restrict__ rv, int64_t n, int nframes,
+                                                           int h, int w, const float* __restrict__ scratch,
+                                                           long long* __restrict__ rec_key,
+                                                           float* __restrict__ rec_val) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= n * HOT_WIN * HOT_WIN) return;
+  const int64_t e = gid / (HOT_WIN * HOT_WIN);
+  const int tap = (int)(gid - e * (HOT_WIN * HOT_WIN));
+  const int64_t hw = (int64_t)h * w;
+  const long long key = keys[e];
+  const int f = (int)(key / hw);
+  const int64_t q = key - (long long)f * hw;
+  const int qy = (int)(q / w), qx = (int)(q - (int64_t)qy * w);
+  const float* Wy = scratch;
+  const float* Wx = Wy + (int64_t)nframes * 5 * h;
+  const int* S = reinterpret_cast<const int*>(Wx + (int64_t)nframes * 5 * w);
+  const int Sy = S[2 * f], Sx = S[2 * f + 1];
+  const int py = qy - Sy - 4 + tap / HOT_WIN, px = qx - Sx - 4 + tap % HOT_WIN;
+  long long out_key = HOT_NONE;
+  float val = 0.f;
+  if (py >= 0 && py < h && px >= 0 && px < w) {
+    float wy = 0.f, wx = 0.f;
+    for (int k = 0; k < 5; ++k) {
+      const int ry = min(max(py + Sy - 1 + k, 0), h - 1);
+      const int rx = min(max(px + Sx - 1 + k, 0), w - 1);
+      if (ry == qy) wy += Wy[((int64_t)f * h + py) * 5 + k];
+      if (rx == qx) wx += Wx[((int64_t)f * 5 + k) * w + px];
+    }
+    if (wy != 0.f && wx != 0.f) {
+      const float2 p = rv[e];
+      val = (p.x - p.y) * wy * wx;
+      out_key = (long long)f * hw + (int64_t)py * w + px;
+    }
+  }
+  rec_key[gid] = out_key;
+  rec_val[gid] = val;
+}
+
+// step 2 (records sorted by key, stable): every run of equal keys is summed in order by the thread of its
+// first record and added to out[key] -- one writer per output element, a fixed order, no atomics.
+__global__ __launch_bounds__(256) void hot_scatter_add(const long long* __restrict__ key, const float* __restrict__ val,
+                                                       int64_t m, int64_t limit, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  const long long k = key[i];
+  if (k < 0 || k >= limit || (i > 0 && key[i - 1] == k)) return;
+  float s = 0.f;
+  for (int64_t j = i; j < m && key[j] == k; ++j) s += val[j];
+  out[k] += s;
+}
+
 // ------------------------------------------------------------------ statistics
 template <typename T>
 __global__ __launch_bounds__(256) void box_stats_partial(const T* __restrict__ stack, int h,
@@ -734,6 +1029,87 @@ int mc_raw_movie_stats(const void* raw, int kind, const float* gain, int nframes
   }
   hipLaunchKernelGGL(raw_stats_finalize, dim3(1), dim3(64), 0, st, (const double*)stats, nframes, hw,
                      (int64_t)(hu - hl) * (wu - wl), mean_zero, mu, sub, mean_rstd);
+  return mc_check_launch();
+}
+
+int mc_raw_hot_detect(const void* raw, int kind, const float* gain, int nframes, int h, int w, int hl, int hu,
+                      int wl, int wu, float threshold, double* stats, double* hstats, long long* keys, float* rv,
+                      long long capacity, unsigned long long* counter, int* counts, void* stream) {
+  if (!raw || !gain || !stats || !hstats || !keys || !rv || !counter || !counts || nframes < 1 || h < 1 || w < 1 ||
+      capacity < 1 || !(threshold > 0.f) || !(threshold < INFINITY))
+    return MC_ERR_ARG;
+  if (kind < 0 || kind > 3) return MC_ERR_UNSUPPORTED;
+  if (hl < 0 || hu > h || wl < 0 || wu > w || hl >= hu || wl >= wu) return MC_ERR_ARG;
+  if ((w % 8) || (reinterpret_cast<uintptr_t>(raw) & (kind == 0 ? 7 : 15)) || (reinterpret_cast<uintptr_t>(gain) & 15) ||
+      (reinterpret_cast<uintptr_t>(rv) & 7))
+    return MC_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t hw = (int64_t)h * w;
+  hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * 3 * nframes, st);
+  if (e == hipSuccess) e = hipMemsetAsync(hstats, 0, sizeof(double) * 3 * nframes, st);
+  if (e == hipSuccess) e = hipMemsetAsync(counter, 0, sizeof(unsigned long long), st);
+  if (e == hipSuccess) e = hipMemsetAsync(counts, 0, sizeof(int) * nframes, st);
+  if (e != hipSuccess) return (int)e;
+  int64_t tb = (hw / 8 + 255) / 256;
+  if (tb > 2048) tb = 2048;
+  const dim3 grid((unsigned)tb, (nframes + COND_FR - 1) / COND_FR);
+#define MC_HOT_DETECT(K)                                                                                          \
+  do {                                                                                                            \
+    hipLaunchKernelGGL(raw_stats_hot_kernel<K>, grid, dim3(256), 0, st, raw, gain, h, w, nframes, hl, hu, wl, wu, \
+                       stats, hstats);                                                                            \
+    hipLaunchKernelGGL(raw_hot_detect_kernel<K>, grid, dim3(256), 0, st, raw, gain, h, w, nframes, threshold,     \
+                       (const double*)hstats, keys, (float2*)rv, capacity, counter, counts);                      \
+  } while (0)
+  switch (kind) {
+    case 0: MC_HOT_DETECT(0); break;
+    case 1: MC_HOT_DETECT(1); break;
+    case 2: MC_HOT_DETECT(2); break;
+    default: MC_HOT_DETECT(3); break;
+  }
+#undef MC_HOT_DETECT
+  return mc_check_launch();
+}
+
+int mc_raw_hot_finalize(const long long* keys, const float* rv, int64_t n, int nframes, int h, int w, int hl, int hu,
+                        int wl, int wu, int mean_zero, const double* hstats, double* stats, float* mu, float* sub,
+                        float* mean_rstd, void* stream) {
+  if (!stats || !hstats || !mu || !sub || !mean_rstd || n < 0 || (n > 0 && (!keys || !rv)) || nframes < 1 || h < 1 ||
+      w < 1 || hl < 0 || hu > h || wl < 0 || wu > w || hl >= hu || wl >= wu)
+    return MC_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(raw_hot_stats_fix, dim3(nframes), dim3(256), 0, st, keys, (const float2*)rv, n,
+                     nframes, h, w, hl, hu, wl, wu, hstats, stats);
+  hipLaunchKernelGGL(raw_stats_finalize, dim3(1), dim3(64), 0, st, (const double*)stats, nframes, (int64_t)h * w,
+                     (int64_t)(hu - hl) * (wu - wl), mean_zero, mu, sub, mean_rstd);
+  return mc_check_launch();
+}
+
+int mc_xc_rows_hot_correct(const long long* keys, const float* rv, int64_t n, int frame0, int njobs, int h, int w,
+                           const float* mask, const float* mean_rstd, void* T1, const mc_xc_geom* q, void* stream) {
+  if (!keys || !rv || !mean_rstd || !T1 || !q || n < 0 || frame0 < 0 || njobs < 1 || h < 1 || w < 1 || q->W != w ||
+      q->nkx < 1 || q->ny < 1 || q->y0 < 0 || q->y0 + q->ny > h || n > 0x7fffffffLL)
+    return MC_ERR_ARG;
+  if (n == 0) return MC_OK;
+  hipLaunchKernelGGL(xc_rows_hot_fix, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, keys, (const float2*)rv, n,
+                     frame0, njobs, h, w, mask, mean_rstd, (cfloat*)T1, q->W, q->nkx, q->y0, q->ny);
+  return mc_check_launch();
+}
+
+int mc_warp_rigid_hot_taps(const long long* keys, const float* rv, int64_t n, int nframes, int h, int w,
+                           const float* scratch, long long* rec_key, float* rec_val, void* stream) {
+  if (!keys || !rv || !scratch || !rec_key || !rec_val || n < 0 || nframes < 1 || h < 2 || w < 2) return MC_ERR_ARG;
+  if (n == 0) return MC_OK;
+  const int64_t m = n * HOT_WIN * HOT_WIN;
+  hipLaunchKernelGGL(warp_rigid_hot_taps, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keys,
+                     (const float2*)rv, n, nframes, h, w, scratch, rec_key, rec_val);
+  return mc_check_launch();
+}
+
+int mc_hot_scatter_add(const long long* key, const float* val, int64_t m, int64_t limit, float* out, void* stream) {
+  if (!key || !val || !out || m < 0 || limit < 1) return MC_ERR_ARG;
+  if (m == 0) return MC_OK;
+  hipLaunchKernelGGL(hot_scatter_add, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, key, val,
+                     m, limit, out);
   return mc_check_launch();
 }
 

@@ -1,12 +1,14 @@
 """Device-side pipelines on top of libmcorr (all tensors already on the GPU).
 
 These functions only allocate buffers (torch caching allocator), build small index
-tables and enqueue libmcorr kernels on the current stream; they never synchronise.
+tables and enqueue libmcorr kernels on the current stream; they never synchronise (one exception:
+a RawMovie with a hot-pixel threshold reads the length of its hot-pixel list back).
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -979,14 +981,42 @@ _RAW_KINDS = {torch.uint8: 0, torch.int16: 1, torch.float16: 2, torch.float32: 3
 # ------------------------------------------------------------------ N2: the rigid path straight from raw frames
 
 
+def check_hot_pixel_threshold(thr):
+    """None, or a finite threshold > 0 as a float; ValueError otherwise (before anything is launched)."""
+    if thr is None:
+        return None
+    try:
+        v = float(thr)
+    except (TypeError, ValueError):
+        raise ValueError(f"hot_pixel_threshold must be a finite number > 0, got {thr!r}") from None
+    if not (math.isfinite(v) and v > 0.0):
+        raise ValueError(f"hot_pixel_threshold must be a finite number > 0, got {thr!r}")
+    return v
+
+
+def hot_list_capacity(t, h, w):
+    """Entries of a RawMovie's hot-pixel list: one per 4096 samples of the movie, at least 4096 (16 bytes each:
+    2.6 MB for 40 x 4096^2).  A threshold that finds more hot pixels raises McorrUnsupported."""
+    return max(4096, (t * h * w) // 4096)
+
+
 class RawMovie:
     """A raw detector movie with what the fused kernels need to condition it on the fly
     (c = raw * gain - mu_f, examples/ttMotion.py:90-121, 180-199): the (t,h,w) u8 / i16 stack, the (h,w)
     fp32 gain reference and, from ONE pass over the raw bytes (mc_raw_movie_stats), the frame means `mu`,
     the per-frame offsets `sub` = mu + box mean and `mean_rstd` of the conditioned central box.  No fp32
-    movie is ever allocated."""
+    movie is ever allocated.
 
-    def __init__(self, raw, gain, mean_zero=True):
+    With `hot_pixel_threshold` the hot-pixel step of examples/ttMotion.py:127-172 (the rule of
+    condition_movie's, mc_condition_movie_hot) sits between the gain and the mean: a statistics pass that also
+    sums v^2 over the whole frame and a detection pass (mc_raw_hot_detect) give the list of hot pixels --
+    `hot_keys` (n,) int64 = f*h*w + pixel index, ascending, `hot_rv` (n, 2) = {replacement, value} -- and
+    `hot_counts` (t,) int32; the statistics are those of the frames after replacement.  global_shifts_raw and
+    warp_rigid_raw apply the list as sparse corrections.  Reading the list's length back costs one small
+    device-to-host copy; more hot pixels than hot_list_capacity() raise McorrUnsupported."""
+
+    def __init__(self, raw, gain, mean_zero=True, hot_pixel_threshold=None):
+        thr = check_hot_pixel_threshold(hot_pixel_threshold)
         lib = _lib.load()
         if raw.dtype not in (torch.uint8, torch.int16):
             raise TypeError(f"the fused raw path reads uint8 or int16 frames, got {raw.dtype}")
@@ -999,14 +1029,45 @@ class RawMovie:
             raise ValueError(f"gain reference {tuple(self.gain.shape)} does not match the frames {(h, w)}")
         self.kind = _RAW_KINDS[raw.dtype]
         self.shape = (t, h, w)
+        self.hot_pixel_threshold = thr
+        self.n_hot = 0
+        self.hot_keys = self.hot_rv = self.hot_counts = None
         hl, hu, wl, wu = int(0.25 * h), int(0.75 * h), int(0.25 * w), int(0.75 * w)  # utils.py:76-81
         self.stats = torch.empty((t, 3), dtype=torch.float64, device=dev)
         self.mu = torch.empty(t, dtype=torch.float32, device=dev)
         self.sub = torch.empty(t, dtype=torch.float32, device=dev)
         self.mean_rstd = torch.empty(2, dtype=torch.float32, device=dev)
-        check(lib.mc_raw_movie_stats(ptr(self.raw), self.kind, ptr(self.gain), t, h, w, hl, hu, wl, wu,
-                                     1 if mean_zero else 0, ptr(self.stats), ptr(self.mu), ptr(self.sub),
-                                     ptr(self.mean_rstd), stream_ptr(dev)), "mc_raw_movie_stats")
+        st = stream_ptr(dev)
+        if thr is None:
+            check(lib.mc_raw_movie_stats(ptr(self.raw), self.kind, ptr(self.gain), t, h, w, hl, hu, wl, wu,
+                                         1 if mean_zero else 0, ptr(self.stats), ptr(self.mu), ptr(self.sub),
+                                         ptr(self.mean_rstd), st), "mc_raw_movie_stats")
+            return
+        cap = hot_list_capacity(t, h, w)
+        hstats = torch.empty((t, 3), dtype=torch.float64, device=dev)
+        keys = torch.empty(cap, dtype=torch.int64, device=dev)
+        rv = torch.empty((cap, 2), dtype=torch.float32, device=dev)
+        counter = torch.empty(1, dtype=torch.int64, device=dev)
+        self.hot_counts = torch.empty(t, dtype=torch.int32, device=dev)
+        check(lib.mc_raw_hot_detect(ptr(self.raw), self.kind, ptr(self.gain), t, h, w, hl, hu, wl, wu, thr,
+                                    ptr(self.stats), ptr(hstats), ptr(keys), ptr(rv), cap, ptr(counter),
+                                    ptr(self.hot_counts), st), "mc_raw_hot_detect")
+        n = int(counter.item())  # the one device-to-host copy of the hot-pixel step
+        if n > cap:
+            raise _lib.McorrUnsupported(
+                f"hot_pixel_threshold={thr:g} finds {n} hot pixels in this movie, more than the {cap} entries "
+                "of the fused path's hot-pixel list")
+        self.hot_keys, order = torch.sort(keys[:n], stable=True)
+        self.hot_rv = rv[:n][order].contiguous()
+        self.n_hot = n
+        check(lib.mc_raw_hot_finalize(ptr(self.hot_keys), ptr(self.hot_rv), n, t, h, w, hl, hu, wl, wu,
+                                      1 if mean_zero else 0, ptr(hstats), ptr(self.stats), ptr(self.mu),
+                                      ptr(self.sub), ptr(self.mean_rstd), st), "mc_raw_hot_finalize")
+
+    def device_tensors(self):
+        """Every device tensor a consumer on another stream reads (for record_stream)."""
+        return [x for x in (self.raw, self.gain, self.mu, self.sub, self.mean_rstd, self.hot_keys, self.hot_rv,
+                            self.hot_counts) if x is not None]
 
 
 def raw_fused_supported(raw, pl):
@@ -1054,6 +1115,9 @@ def global_shifts_raw(rm: RawMovie, reference_frame, pixel_spacing, b_factor, fr
             check(lib.mc_xcg_rows_forward_raw(ptr(rm.raw), rm.kind, ptr(rm.gain), ptr(off), w, ptr(pl.mask), ptr(sub),
                                               ptr(rm.mean_rstd), ptr(T1), ptr(pl.tw_row), line, n, g, st),
                   "mc_xcg_rows_forward_raw")
+        if rm.n_hot:  # hot pixels of these frames: sparse correction of T1 (no fp32 movie)
+            check(lib.mc_xc_rows_hot_correct(ptr(rm.hot_keys), ptr(rm.hot_rv), rm.n_hot, a, n, h, w, ptr(pl.mask),
+                                             ptr(rm.mean_rstd), ptr(T1), g, st), "mc_xc_rows_hot_correct")
         if a + n >= t and AFTER_K1_HOOK is not None:
             AFTER_K1_HOOK()
         check(_k2(lib, g, dev, T1, pl.filt, S[a:a + n], pl.tw_col, n, st), "xc cols forward")
@@ -1084,7 +1148,34 @@ def warp_rigid_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want
         RIGID_KERNEL_HOOK(run)
     else:
         run()
+    if rm.n_hot:
+        _warp_hot_correct(lib, rm, scratch, frames, total, stream_ptr(dev))
     return frames, total
+
+
+_HOT_NONE = (1 << 63) - 1
+
+
+def _warp_hot_correct(lib, rm, scratch, frames, total, st):
+    """Add each hot pixel's delta, times the weight with which mc_warp_rigid_raw read it, into the outputs whose
+    taps reach it.  Records are summed per output element in a fixed order (stable sorts, one writer each):
+    frames and sum are reproducible bit for bit."""
+    t, h, w = rm.shape
+    m = rm.n_hot * 49
+    dev = rm.raw.device
+    rec_key = torch.empty(m, dtype=torch.int64, device=dev)
+    rec_val = torch.empty(m, dtype=torch.float32, device=dev)
+    check(lib.mc_warp_rigid_hot_taps(ptr(rm.hot_keys), ptr(rm.hot_rv), rm.n_hot, t, h, w, ptr(scratch),
+                                     ptr(rec_key), ptr(rec_val), st), "mc_warp_rigid_hot_taps")
+    if frames is not None:
+        k, order = torch.sort(rec_key, stable=True)
+        check(lib.mc_hot_scatter_add(ptr(k), ptr(rec_val[order].contiguous()), m, t * h * w, ptr(frames), st),
+              "mc_hot_scatter_add")
+    if total is not None:
+        pk = torch.where(rec_key == _HOT_NONE, rec_key, rec_key % (h * w))
+        k, order = torch.sort(pk, stable=True)
+        check(lib.mc_hot_scatter_add(ptr(k), ptr(rec_val[order].contiguous()), m, h * w, ptr(total), st),
+              "mc_hot_scatter_add")
 
 
 def condition_movie(raw, gain=None, mean_zero=True, hot_pixel_threshold=None, return_hot_counts=False):

@@ -295,11 +295,19 @@ class RawMoviePipeline(MoviePipeline):
     statistics pass over the raw bytes, then the estimator's row transform and the rigid warp condition the
     samples on the fly (``raw * gain - frame mean``, examples/ttMotion.py:90-121, 180-199) -- no conditioned
     fp32 movie is allocated.  Results equal ``condition_movie`` followed by the MoviePipeline.  Frame shapes
-    without a fused kernel raise McorrUnsupported (use ``motion_correct_raw``, which falls back)."""
+    without a fused kernel raise McorrUnsupported (use ``motion_correct_raw``, which falls back).
+
+    ``hot_pixel_threshold``: the example's hot-pixel step as in ``motion_correct_raw`` (per movie the same
+    results).  The length of a movie's hot-pixel list is read back to the host once, right after its detection
+    pass on the estimator's stream and before its K1 is enqueued (the previous movie's warp is then not yet
+    enqueued; the one before it may still run).  A movie with more hot pixels than the list holds raises
+    McorrUnsupported naming the threshold."""
 
     def __init__(self, gain, device=None, pixel_spacing: float = 1.0, reference_frame: Optional[int] = None,
                  b_factor: float = 500, frequency_range=(300, 10), grid_type: str = "catmull_rom",
-                 return_frames: bool = True, overlap: bool = True, mean_zero: bool = True):
+                 return_frames: bool = True, overlap: bool = True, mean_zero: bool = True,
+                 hot_pixel_threshold: Optional[float] = None):
+        self.hot_pixel_threshold = engine.check_hot_pixel_threshold(hot_pixel_threshold)
         super().__init__(device, pixel_spacing, reference_frame, b_factor, frequency_range, grid_type,
                          return_frames, overlap)
         self.gain = None if gain is None else gain.detach().to(device=self.device, dtype=torch.float32).contiguous()
@@ -318,7 +326,8 @@ class RawMoviePipeline(MoviePipeline):
     def _estimate(self, img: torch.Tensor) -> torch.Tensor:
         t = img.shape[0]
         ref = t // 2 if self.reference_frame is None else int(self.reference_frame)
-        rm = engine.RawMovie(img, self.gain, mean_zero=self.mean_zero)  # the statistics pass, on the estimator's stream
+        # the statistics (and hot-pixel) passes, on the estimator's stream
+        rm = engine.RawMovie(img, self.gain, mean_zero=self.mean_zero, hot_pixel_threshold=self.hot_pixel_threshold)
         self._rm[id(img)] = rm
         shifts = engine.global_shifts_raw(rm, ref, self.pixel_spacing, self.b_factor, self.frequency_range)
         return self._field_and_tables(img, shifts)
@@ -326,10 +335,12 @@ class RawMoviePipeline(MoviePipeline):
     def _prepare(self, img: torch.Tensor, field: torch.Tensor):
         rm = self._rm.pop(id(img))
         shifts_px, scratch = self._tables.pop(id(img))
-        return shifts_px, scratch, rm.mu, rm
+        # every tensor the warp stream reads that was made on the estimator's stream (the all-ones gain of
+        # gain=None, the hot-pixel list, ...) is in the tuple: the caller record_stream()s them all
+        return (shifts_px, scratch, *rm.device_tensors(), rm)
 
     def _correct(self, img: torch.Tensor, tables):
-        shifts_px, scratch, _, rm = tables
+        shifts_px, scratch, rm = tables[0], tables[1], tables[-1]
         return engine.warp_rigid_raw(rm, None, self.pixel_spacing, want_frames=self.return_frames, want_sum=True,
                                      tables=(shifts_px, scratch))
 
