@@ -233,6 +233,18 @@ int mc_xc_rows_forward_raw(const void* raw, int storage, const float* gain, cons
                            void* T1, const void* tw_row, int njobs, const mc_xc_geom* q, const int* row_chord,
                            void* stream);
 
+/* N2: the patch estimator's 1024-sample rows (mc_xc_rows_forward_dual_t's wave-per-row engine) from the raw bytes
+ * of a u8 / i16 movie: rows of (raw * gain - job_sub[job]) * mean_rstd[1] * mask^expo_a (and mask^expo_b into T1b
+ * when expo_b is given) -> T1a / T1b.  Patch jobs: job_off / row_stride in samples of the movie; the gain has the
+ * frames' row pitch and a job's gain values sit at job_off[job] % frame_area (its offset within its frame);
+ * job_sub[job] = the job's frame mean + the box mean (mc_raw_movie_stats).  Geometries the wave engine does not
+ * take (W != 1024, nkx > 128, ny % 8) and other storage tags: MC_ERR_UNSUPPORTED. */
+int mc_xc_rows_forward_dual_raw(const void* raw, int storage, const float* gain, int64_t frame_area,
+                                const int64_t* job_off, int64_t row_stride, const int* expo_a, const int* expo_b,
+                                const float* mask, const float* job_sub, const float* mean_rstd, void* T1a, void* T1b,
+                                const void* tw_row, int njobs, const mc_xc_geom* q, const int* row_chord,
+                                void* stream);
+
 /* K2.  Column FFT of T1, kept ky rows, times filt (or NULL) -> S[j][kx][kyi].
  * estimate_motion_xc.py:78,98 / :340-346. */
 int mc_xc_cols_forward(const void* T1, const float* filt, void* S, const void* tw_col, int njobs,
@@ -354,6 +366,15 @@ int mc_warp_frames(const float* frames, int nframes, int h, int w, const float* 
 int mc_warp_frames_t(const void* frames, int storage, int nframes, int h, int w, const float* lattice,
                      int GH, int GW, float pixel_spacing, float* scratch, float* out_frames, float* out_sum,
                      void* stream);
+
+/* N2: mc_warp_frames_t fed from the RAW movie: every sample is conditioned as raw * gain - mu[f] (gain (h,w)
+ * fp32, mu from mc_raw_movie_stats) on its way into the resampler's window, so the outputs (fp32, same contract)
+ * equal mc_warp_frames on the output of mc_condition_movie; outside the frame the result is the conditioned
+ * domain's zero.  storage: MC_STORE_U8 (w % 16 == 0) or MC_STORE_I16 (w % 8 == 0); 16-byte aligned raw, the
+ * sparse lattice of mc_warp_frames_t's fp16 path and h * w < 2^31; anything else is MC_ERR_UNSUPPORTED. */
+int mc_warp_frames_raw(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h, int w,
+                       const float* lattice, int GH, int GW, float pixel_spacing, float* scratch, float* out_frames,
+                       float* out_sum, void* stream);
 
 /* N2: the rigid warp (correct_motion for a (2,t,1,1) field, correct_motion.py:18-78) fed from the RAW movie:
  * every sample is conditioned as raw * gain - mu[f] on its way to the resampler (examples/ttMotion.py:90-121,

@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     get_pixel_shifts,
     image_shifts_to_deformation_field,
     motion_correct_raw,
+    motion_correct_raw_patches,
     motion_correct_sum,
     resample_deformation_field,
 )
@@ -43,6 +44,7 @@ __all__ = [
     "estimate_motion",
     "motion_correct_sum",
     "motion_correct_raw",
+    "motion_correct_raw_patches",
     "dose_weighted_sum",
     "condition_movie",
     "evaluate_deformation_field_at_t",

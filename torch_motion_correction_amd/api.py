@@ -418,6 +418,89 @@ def _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, f
     return tuple(out)
 
 
+def motion_correct_raw_patches(movie, gain, pixel_spacing, patch_sidelength=1024, reference_frame=None,
+                               reference_strategy="mean_except_current", b_factor=500, frequency_range=(300, 10),
+                               sub_pixel_refinement=True, temporal_smoothing=True, smoothing_window_size=5,
+                               deformation_field=None, outlier_rejection=True, outlier_threshold=3.0,
+                               grid_type="catmull_rom", mean_zero=True, return_frames=False, device=None,
+                               hot_pixel_threshold=None, return_hot_counts=False):
+    """The local-motion flow of the reference pipeline for a RAW uint8 / int16 movie: ``condition_movie(movie, gain,
+    mean_zero, hot_pixel_threshold)`` then ``estimate_motion_cross_correlation_patches`` and ``motion_correct_sum``
+    with the field it returns.  Returns ``(field (2,t,gh,gw) Angstrom, centres (t,gh,gw,3) int64, sum (h,w)[, frames
+    (t,h,w)][, hot counts (t,) int32])``.
+
+    Fused route (no conditioned fp32 movie is allocated): u8 / i16 movies, 1024-px patches, no prior
+    ``deformation_field`` and no ``hot_pixel_threshold``.  The patch row pass and the field warp read the raw bytes
+    and form ``raw * gain - frame mean`` on the fly (engine.patch_field_raw, engine.warp_field_raw); the results
+    differ from the conditioned route only by the fp32 rounding of that conditioning.  Every other case, and any
+    shape the raw kernels do not take, runs exactly the conditioned route."""
+    if reference_strategy not in ("middle_frame", "mean_except_current"):
+        raise ValueError(f"Unknown reference_strategy: {reference_strategy}")
+    thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # ValueError before any device is touched
+    if not int(patch_sidelength) > 0:
+        raise ValueError(f"patch_sidelength must be > 0, got {patch_sidelength!r}")
+    return _motion_correct_raw_patches(movie, gain, pixel_spacing, int(patch_sidelength), reference_frame,
+                                       reference_strategy, b_factor, frequency_range, sub_pixel_refinement,
+                                       temporal_smoothing, smoothing_window_size, deformation_field, outlier_rejection,
+                                       outlier_threshold, grid_type, mean_zero, return_frames, device, thr,
+                                       return_hot_counts)
+
+
+@_on_gpu
+def _motion_correct_raw_patches(movie, gain, pixel_spacing, patch_sidelength, reference_frame, reference_strategy,
+                                b_factor, frequency_range, sub_pixel_refinement, temporal_smoothing,
+                                smoothing_window_size, deformation_field, outlier_rejection, outlier_threshold,
+                                grid_type, mean_zero, return_frames, device, thr, return_hot_counts):
+    out_dev = _out_device(movie, device)
+    dev = require_gpu(out_dev)
+    raw = movie.detach().to(dev)
+    t = raw.shape[0]
+    ps = float(pixel_spacing)
+    gd = None if gain is None else gain.to(dev)
+    est = dict(reference_strategy=reference_strategy, b_factor=b_factor, frequency_range=frequency_range,
+               patch_sidelength=patch_sidelength, sub_pixel_refinement=sub_pixel_refinement,
+               temporal_smoothing=temporal_smoothing, smoothing_window_size=smoothing_window_size,
+               outlier_rejection=outlier_rejection, outlier_threshold=outlier_threshold)
+    fused = raw.dtype in (torch.uint8, torch.int16) and deformation_field is None and thr is None
+    if fused:
+        # the estimator's own argument rules (estimate_motion_cross_correlation_patches), before any launch
+        ref = t // 2 if reference_frame is None else reference_frame
+        if reference_strategy == "middle_frame":
+            normalize_frame_index(ref, t)
+        else:
+            ref = t // 2
+        if BUG_COMPATIBLE and outlier_rejection and not sub_pixel_refinement:
+            raise RuntimeError("std and var only support floating point and complex dtypes")
+        try:
+            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero))
+            field, centers = engine.patch_field_raw(
+                rm, ps, ref, reference_strategy, float(b_factor), frequency_range, patch_sidelength,
+                bool(sub_pixel_refinement), bool(temporal_smoothing), int(smoothing_window_size),
+                bool(outlier_rejection), float(outlier_threshold))
+            lat = engine.frame_lattices(field, t, grid_type)
+            if RIGID_FAST_PATH and _is_rigid(field):  # a single patch: motion_correct_sum's rigid warp
+                frames, total = engine.warp_rigid_raw(rm, lat, ps, want_frames=bool(return_frames), want_sum=True)
+            else:
+                frames, total = engine.warp_field_raw(rm, lat, ps, want_frames=bool(return_frames), want_sum=True)
+        except McorrUnsupported:
+            fused = False
+    counts = None
+    if not fused:
+        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr, return_hot_counts=thr is not None)
+        if thr is not None:
+            img, counts = img
+        field, centers = estimate_motion_cross_correlation_patches(img, ps, reference_frame=reference_frame,
+                                                                   deformation_field=deformation_field, **est)
+        res = motion_correct_sum(img, field, ps, grid_type=grid_type, return_frames=bool(return_frames))
+        total, frames = res if return_frames else (res, None)
+    out = [field.to(out_dev), centers.to(out_dev), total.to(out_dev)]
+    if return_frames:
+        out.append(frames.to(out_dev))
+    if return_hot_counts:
+        out.append(torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None else counts.to(out_dev))
+    return tuple(out)
+
+
 @_on_gpu
 def dose_weighted_sum(movie, pixel_spacing, dose_per_frame, pre_exposure=0.0, voltage=300.0, device=None):
     """``sum_f irfft2(q_f * rfft2(frame_f))`` with the Grant & Grigorieff exposure filter

@@ -1847,6 +1847,8 @@ struct FieldArgs {
   const int* xtap;       // [w][4]
   int GW;
   unsigned char* flags;  // [f][tile]: 1 = irregular, left to warp_field_slow
+  const float* gain;     // raw frames (N2) only: (h, w) gain reference
+  const float* mu;       // raw frames (N2) only: [f] frame means, subtracted after the gain multiply
 };
 
 __device__ __forceinline__ int wave_min_i(int v) {
@@ -2487,20 +2489,27 @@ __global__ __launch_bounds__(64) void warp_field_plan(FieldArgs fa, int unit_ps,
   }
 }
 
-template <bool WRITE_FRAMES, bool WRITE_SUM, bool UNIT_PS, bool HALF>
+// RAW (N2): 1 = u8, 2 = i16 frames, staged like fp16 (16-byte units from the unit-aligned column at or left
+// of the window) in the fp16 stage's space; the widening pass forms c = raw * gain - mu[f] with the gain read
+// at the same (clamped) pixel, so the fp32 window holds what mc_condition_movie would have written.
+template <bool WRITE_FRAMES, bool WRITE_SUM, bool UNIT_PS, bool HALF, int RAW = 0>
 __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldArgs fa, const int4* __restrict__ plan) {
+  static_assert(!(HALF && RAW), "fp16 or raw, not both");
+  constexpr bool STAGED = HALF || RAW != 0;         // the DMA lands in a stage, a widening pass fills the window
+  constexpr int SB = RAW == 1 ? 1 : 2;              // bytes per staged sample
+  constexpr int UPS = 16 / SB;                      // staged samples per 16-byte unit
   const WarpArgs& a = fa.w;
   extern __shared__ __attribute__((aligned(16))) char smem_gw[];
   // fp32 frames: [window 0][window 1][E 0][E 1].  fp16 frames: [fp32 window][fp16 stage 0][fp16
   // stage 1][E 0][E 1] -- the DMA lands the raw fp16 window in a stage, one pass per frame widens it
   // into the single fp32 window (10 elements per thread; doing it per tap would be 24 instructions
   // per pixel), so the HBM side moves half the bytes and the arithmetic is unchanged.
-  auto win_of = [&](int bi) { return reinterpret_cast<float4*>(smem_gw) + (HALF ? 0 : bi) * GW_QUADS_PAD; };
+  auto win_of = [&](int bi) { return reinterpret_cast<float4*>(smem_gw) + (STAGED ? 0 : bi) * GW_QUADS_PAD; };
   auto stage_of = [&](int bi) {
     return reinterpret_cast<float4*>(smem_gw + GW_QUADS_PAD * 16) + bi * GW3_STAGE_UNITS;
   };
   auto est_of = [&](int bi) {
-    return reinterpret_cast<float*>(smem_gw + (HALF ? GW_QUADS_PAD * 16 + 2 * GW3_STAGE_UNITS * 16
+    return reinterpret_cast<float*>(smem_gw + (STAGED ? GW_QUADS_PAD * 16 + 2 * GW3_STAGE_UNITS * 16
                                                     : 2 * GW_QUADS_PAD * 16)) + bi * (2 * GW3_EROWS * 256);
   };
   __shared__ int s_ytap[RIGID_WAVES * RIGID_ROWS][4];
@@ -2553,9 +2562,9 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
   };
   // The (window row, 16-byte unit) of each DMA unit this thread issues does not depend on the frame:
   // the divisions are done once (per frame they were 13 of the kernel's 98 VALU instructions per pixel)
-  constexpr int DMA_UNITS = HALF ? GW3_STAGE_UNITS / 64 : GW_QUADS_PAD / 64;  // wave-units of 64 lanes
+  constexpr int DMA_UNITS = STAGED ? GW3_STAGE_UNITS / 64 : GW_QUADS_PAD / 64;  // wave-units of 64 lanes
   constexpr int DMA_NIT = (DMA_UNITS + GW3_WAVES - 1) / GW3_WAVES;
-  constexpr int DMA_QROW = HALF ? GW3_QH : GW_QUADS;
+  constexpr int DMA_QROW = STAGED ? GW3_QH : GW_QUADS;
   int dma_tr[DMA_NIT], dma_qc[DMA_NIT];
 #pragma unroll
   for (int it = 0; it < DMA_NIT; ++it) {
@@ -2572,19 +2581,20 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
     const int nrows = RIGID_WAVES * RIGID_ROWS + 3 + 2 * mgy;
     int nq = (RIGID_LANES * 4 + 6 + 2 * mgx + 3) / 4;
     nq = nq < GW_QUADS ? nq : GW_QUADS;
-    if (HALF) {  // 16-byte units of 8 samples from the 8-aligned column at or left of the window
-      const _Float16* frh = reinterpret_cast<const _Float16*>(a.frames) + (int64_t)f * hw;
-      const int axa = p.y & ~7;
-      const int nqh = (p.y - axa + RIGID_LANES * 4 + 3 + 2 * mgx + 7) / 8;  // <= GW3_QH
+    if (STAGED) {  // 16-byte units of UPS samples (fp16 / i16: 8, u8: 16) from the unit-aligned column at or left of the window
+      const char* frb = reinterpret_cast<const char*>(a.frames) + (int64_t)f * hw * SB;
+      const int axa = p.y & ~(UPS - 1);
+      const int nqh = (p.y - axa + RIGID_LANES * 4 + 3 + 2 * mgx + UPS - 1) / UPS;  // <= GW3_QH
 #pragma unroll
       for (int it = 0; it < DMA_NIT; ++it) {
         if (dma_tr[it] < nrows && dma_qc[it] < nqh) {
           int r = p.x + dma_tr[it];
           r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
-          int c = axa + 8 * dma_qc[it];
-          c = c < 0 ? 0 : (c > w - 8 ? w - 8 : c);  // clamped units are never read (see widen)
+          int c = axa + UPS * dma_qc[it];
+          c = c < 0 ? 0 : (c > w - UPS ? w - UPS : c);  // clamped units are never read (see widen)
           const unsigned off = __umul24((unsigned)r, (unsigned)w) + (unsigned)c;  // h w < 2^32 (checked by the host)
-          __builtin_amdgcn_global_load_lds(frh + off, (lds_vptr)(stage_of(bi) + (wave + it * GW3_WAVES) * 64), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds(frb + (size_t)off * SB, (lds_vptr)(stage_of(bi) + (wave + it * GW3_WAVES) * 64),
+                                           16, 0, 0);
         }
       }
     } else {
@@ -2613,19 +2623,53 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
 
   // fp16: stage `bi` -> the fp32 window.  Window column j is absolute column p.y + j; border padding
   // = the clipped column, which always lies in an unclamped unit of the stage (w % 8 == 0).
-  auto widen = [&](const int4 p, int bi) {
+  auto widen = [&](const int4 p, int bi, int f) {
     if (p.z >> 16) return;
     const int mgy = p.z & 255, mgx = (p.z >> 8) & 255;
     const int nrows = RIGID_WAVES * RIGID_ROWS + 3 + 2 * mgy;
     const int ncols = RIGID_LANES * 4 + 3 + 2 * mgx;  // <= GW_STRIDE
-    const int axa = p.y & ~7;
-    const _Float16* st = reinterpret_cast<const _Float16*>(stage_of(bi));
+    const int axa = p.y & ~(UPS - 1);
     float* wn = reinterpret_cast<float*>(win_of(0));
-    for (int i = tid; i < nrows * ncols; i += RIGID_LANES * GW3_WAVES) {
-      const int tr = i / ncols, j = i - tr * ncols;
-      int xa = p.y + j;
-      xa = xa < 0 ? 0 : (xa > w - 1 ? w - 1 : xa);
-      wn[tr * GW_STRIDE + j] = (float)st[tr * (8 * GW3_QH) + (xa - axa)];
+    if constexpr (RAW != 0) {
+      // raw: c = raw * gain - mu[f] (the conditioning of mc_condition_movie, in the same fp32 operations).  The
+      // gain window moves with the frame's displacement, so it is read per frame, at the sample's own clamped
+      // pixel; a fixed trip count keeps all of a thread's gain loads in flight together.
+      constexpr int NIT = (GW_ROWS * GW_STRIDE + RIGID_LANES * GW3_WAVES - 1) / (RIGID_LANES * GW3_WAVES);
+      const char* st = reinterpret_cast<const char*>(stage_of(bi));
+      const float m = fa.mu[f];
+      float gv[NIT], rv[NIT];
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int i = tid + it * RIGID_LANES * GW3_WAVES;
+        gv[it] = 0.f;
+        rv[it] = 0.f;
+        if (i < nrows * ncols) {
+          const int tr = i / ncols, j = i - tr * ncols;
+          int xa = p.y + j;
+          xa = xa < 0 ? 0 : (xa > w - 1 ? w - 1 : xa);
+          int r = p.x + tr;
+          r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
+          gv[it] = fa.gain[__umul24((unsigned)r, (unsigned)w) + (unsigned)xa];
+          const char* sp = st + tr * (16 * GW3_QH) + (xa - axa) * SB;
+          rv[it] = RAW == 1 ? (float)*reinterpret_cast<const unsigned char*>(sp) : (float)*reinterpret_cast<const short*>(sp);
+        }
+      }
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int i = tid + it * RIGID_LANES * GW3_WAVES;
+        if (i < nrows * ncols) {
+          const int tr = i / ncols, j = i - tr * ncols;
+          wn[tr * GW_STRIDE + j] = rv[it] * gv[it] - m;
+        }
+      }
+    } else {
+      const _Float16* st = reinterpret_cast<const _Float16*>(stage_of(bi));
+      for (int i = tid; i < nrows * ncols; i += RIGID_LANES * GW3_WAVES) {
+        const int tr = i / ncols, j = i - tr * ncols;
+        int xa = p.y + j;
+        xa = xa < 0 ? 0 : (xa > w - 1 ? w - 1 : xa);
+        wn[tr * GW_STRIDE + j] = (float)st[tr * (8 * GW3_QH) + (xa - axa)];
+      }
     }
   };
 
@@ -2633,8 +2677,8 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
   dma(0, pc, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (HALF) {
-    widen(pc, 0);
+  if (STAGED) {
+    widen(pc, 0, 0);
     __syncthreads();
   }
   for (int f = 0; f < a.nframes; ++f) {
@@ -2656,7 +2700,7 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
       nq = nq < GW_QUADS ? nq : GW_QUADS;
       float* const tile = reinterpret_cast<float*>(win_of(bi));
       const float* const es = est_of(bi);
-      if (!HALF && (ax < 0 || ax + 4 * nq > w)) {  // border padding: clipped columns (edge tiles only)
+      if (!STAGED && (ax < 0 || ax + 4 * nq > w)) {  // border padding: clipped columns (edge tiles only)
         for (int i = tid; i < nrows * GW_STRIDE; i += RIGID_LANES * GW3_WAVES) {
           const int tr = i / GW_STRIDE, e = i - tr * GW_STRIDE;
           const int c = ax + e;
@@ -2670,7 +2714,7 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
         __syncthreads();
       }
       const bool interior_rt = whole_tile && wy0 >= 0 && wy0 + nrows <= h && ax >= 0 &&
-                               ax + (HALF ? RIGID_LANES * 4 + 3 + 2 * mgx : 4 * nq) <= w;
+                               ax + (STAGED ? RIGID_LANES * 4 + 3 + 2 * mgx : 4 * nq) <= w;
       const int oy = 1 + wy0, ox = 1 + ax;
       const unsigned tap_base = (unsigned)(uintptr_t)(lds_vptr)tile - 4u * (unsigned)(oy * GW_STRIDE + ox);
       // The tile-frame's two bodies are separate instantiations: the interior one (no zero-outside
@@ -2818,8 +2862,8 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // DMA of f+1 (and this frame's stores)
     __syncthreads();  // buffer bi is free again, buffer bi^1 is complete
-    if (HALF && f + 1 < a.nframes) {
-      widen(pn, bi ^ 1);
+    if (STAGED && f + 1 < a.nframes) {
+      widen(pn, bi ^ 1, f + 1);
       __syncthreads();
     }
     pc = pn;
@@ -2841,7 +2885,9 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
 // Tile-frames warp_field flagged as irregular: generic per-pixel gathers from global
 // memory (border padding by clipping every tap coordinate).  One workgroup per tile, so
 // the += on out_sum cannot race.
-template <bool UNIT_PS, bool HALF = false>
+// RAW (N2): u8 / i16 frames, every tap conditioned as raw * gain - mu[f] at its clamped pixel (the zero
+// outside the frame stays the conditioned domain's zero).
+template <bool UNIT_PS, bool HALF = false, int RAW = 0>
 __global__ __launch_bounds__(RIGID_LANES* RIGID_WAVES) void warp_field_slow(FieldArgs fa, int write_frames,
                                                                            int write_sum) {
   const WarpArgs& a = fa.w;
@@ -2890,7 +2936,9 @@ __global__ __launch_bounds__(RIGID_LANES* RIGID_WAVES) void warp_field_slow(Fiel
         float t4[4];
         for (int j = 0; j < 4; ++j) {
           const int64_t o = ro + (int)fminf(fmaxf(fx + (float)(j - 1), 0.f), fw - 1.f);
-          t4[j] = HALF ? (float)frh[o] : fr[o];
+          if constexpr (RAW == 1) t4[j] = (float)reinterpret_cast<const unsigned char*>(a.frames)[f * hw + o] * fa.gain[o] - fa.mu[f];
+          else if constexpr (RAW == 2) t4[j] = (float)reinterpret_cast<const short*>(a.frames)[f * hw + o] * fa.gain[o] - fa.mu[f];
+          else t4[j] = HALF ? (float)frh[o] : fr[o];
         }
         rowv[ii] = gw_dot4(wx, t4[0], t4[1], t4[2], t4[3]);
       }
@@ -3189,6 +3237,79 @@ int mc_warp_frames_t(const void* frames_any, int storage, int nframes, int h, in
   else if (out_frames) MC_WARP_LAUNCH(true, false);
   else MC_WARP_LAUNCH(false, true);
 #undef MC_WARP_LAUNCH
+  return mc_check_launch();
+}
+
+// N2: the deformation-field warp fed from the RAW movie (warp_field3 / warp_field_slow with RAW = 1 / 2): the same
+// tables, plan and tiles as mc_warp_frames_t for fp16 frames, the raw window conditioned in the widening pass.
+int mc_warp_frames_raw(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h, int w,
+                       const float* lattice, int GH, int GW, float pixel_spacing, float* scratch, float* out_frames,
+                       float* out_sum, void* stream) {
+  if (storage != MC_STORE_U8 && storage != MC_STORE_I16) return MC_ERR_UNSUPPORTED;
+  if (!raw || !gain || !mu || !lattice || !scratch || (!out_frames && !out_sum)) return MC_ERR_ARG;
+  if (nframes < 1 || h < 2 || w < 2 || GH < 1 || GW < 1 || !(pixel_spacing > 0.f)) return MC_ERR_ARG;
+  if (((uintptr_t)scratch) & 15) return MC_ERR_ARG;
+  const int ups = storage == MC_STORE_U8 ? 16 : 8;  // samples per 16-byte DMA unit: rows of whole units
+  const bool small32 = h < (1 << 24) && w < (1 << 24) && (int64_t)h * w < ((int64_t)1 << 31);
+  if ((w % ups) || (((uintptr_t)raw) & 15) || (((uintptr_t)gain) & 3) || !small32 ||
+      (int64_t)32 * (GH - 1) * 2 > (int64_t)3 * (h - 1))
+    return MC_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  float* etab = scratch;
+  int* ytap = reinterpret_cast<int*>(scratch + etab_floats(nframes, GH, w));
+  float* ycoef = reinterpret_cast<float*>(ytap + 4 * (int64_t)h);
+  int* xtap = reinterpret_cast<int*>(ycoef + 4 * (int64_t)h);
+  float* xcoef = reinterpret_cast<float*>(xtap + 4 * (int64_t)w);
+  hipLaunchKernelGGL(warp_axis_tables, dim3((h + 255) / 256), dim3(256), 0, s, h, GH, ytap, ycoef);
+  hipLaunchKernelGGL(warp_axis_tables, dim3((w + 255) / 256), dim3(256), 0, s, w, GW, xtap, xcoef);
+  hipLaunchKernelGGL(warp_etab, dim3((w + 255) / 256, nframes * 2 * GH), dim3(256), 0, s, lattice,
+                     GH, GW, w, xtap, xcoef, etab);
+  WarpArgs a;
+  a.frames = static_cast<const float*>(raw); a.nframes = nframes; a.h = h; a.w = w; a.GH = GH; a.etab = etab;
+  a.ytap = ytap; a.ycoef = ycoef; a.pixel_spacing = pixel_spacing;
+  a.out_frames = out_frames; a.out_sum = out_sum;
+  a.tiles_x = (w + RIGID_LANES * 4 - 1) / (RIGID_LANES * 4);
+  a.tiles_y = (h + RIGID_WAVES * RIGID_ROWS - 1) / (RIGID_WAVES * RIGID_ROWS);
+  const bool unit = (pixel_spacing == 1.0f);
+  FieldArgs fa;
+  fa.w = a;
+  fa.lattice = lattice;
+  fa.xtap = xtap;
+  fa.GW = GW;
+  fa.flags = reinterpret_cast<unsigned char*>(xcoef + 4 * (int64_t)w);
+  fa.gain = gain;
+  fa.mu = mu;
+  hipError_t e = hipMemsetAsync(fa.flags, 0, (size_t)field_flag_bytes(nframes, h, w), s);
+  if (e != hipSuccess) return (int)e;
+  dim3 grid(a.tiles_x * a.tiles_y), block(RIGID_LANES, RIGID_WAVES), block3(RIGID_LANES, GW3_WAVES);
+  int4* plan = reinterpret_cast<int4*>(fa.flags + field_flag_bytes(nframes, h, w));
+  // windows at the exact column, as for fp16 (the widening pass places them)
+  hipLaunchKernelGGL(warp_field_plan, dim3(a.tiles_x * a.tiles_y, nframes), dim3(64), 0, s, fa, unit ? 1 : 0, 1, plan);
+  const size_t lds3 = (size_t)GW_QUADS_PAD * 16 + (size_t)2 * GW3_STAGE_UNITS * 16 + (size_t)2 * 2 * GW3_EROWS * 256 * 4;
+#define MC_GW3R_GO(F, S, U, R)                                                                    \
+  do {                                                                                            \
+    auto k = warp_field3<F, S, U, false, R>;                                                      \
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3); \
+    hipLaunchKernelGGL(k, grid, block3, lds3, s, fa, (const int4*)plan);                          \
+  } while (0)
+#define MC_GW3R_LAUNCH(F, S, R)                         \
+  do {                                                  \
+    if (unit) MC_GW3R_GO(F, S, true, R);                \
+    else MC_GW3R_GO(F, S, false, R);                    \
+  } while (0)
+#define MC_GW3R_MODE(R)                                                        \
+  do {                                                                         \
+    if (out_frames && out_sum) MC_GW3R_LAUNCH(true, true, R);                  \
+    else if (out_frames) MC_GW3R_LAUNCH(true, false, R);                       \
+    else MC_GW3R_LAUNCH(false, true, R);                                       \
+    if (unit) hipLaunchKernelGGL((warp_field_slow<true, false, R>), grid, block, 0, s, fa, out_frames ? 1 : 0, out_sum ? 1 : 0); \
+    else hipLaunchKernelGGL((warp_field_slow<false, false, R>), grid, block, 0, s, fa, out_frames ? 1 : 0, out_sum ? 1 : 0); \
+  } while (0)
+  if (storage == MC_STORE_U8) MC_GW3R_MODE(1);
+  else MC_GW3R_MODE(2);
+#undef MC_GW3R_MODE
+#undef MC_GW3R_LAUNCH
+#undef MC_GW3R_GO
   return mc_check_launch();
 }
 

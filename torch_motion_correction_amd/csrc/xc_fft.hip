@@ -736,12 +736,37 @@ __device__ __forceinline__ void wf5_fft(wf2 (&A)[8], int t, wf2* slab, const wf2
   X[1] = wf_unpack(z[1], m1, twK[t + 64]);
 }
 
-template <bool DUAL, bool HALF>
-__global__ __launch_bounds__(256, WF5_MIN_WAVES) void xc_rows_fwd_wave512(
+// RAW (N2): 1 = u8, 2 = i16 patch rows conditioned on the fly, A = (raw * gain - job_sub[job]) * mean_rstd[1]
+// * mask^e.  A patch job's gain sits at its offset within its frame: gain + job_off[job] % frame_area, with the
+// frames' row pitch (the gain pair of a lane is one 8-byte load next to its 2- / 4-byte raw pair).
+// the two raw samples of a lane as loaded (u8: 2 bytes, i16: 4 bytes; one register until they are widened)
+template <int RAW>
+__device__ __forceinline__ unsigned wf5_ld2raw(const void* row, int x) {
+  if constexpr (RAW == 1) {
+    unsigned short v;
+    __builtin_memcpy(&v, static_cast<const unsigned char*>(row) + x, 2);
+    return v;
+  } else {
+    unsigned v;
+    __builtin_memcpy(&v, static_cast<const short*>(row) + x, 4);
+    return v;
+  }
+}
+template <int RAW>
+__device__ __forceinline__ wf2 wf5_widen2raw(unsigned v) {
+  if constexpr (RAW == 1) return wf2{(float)(v & 0xffu), (float)(v >> 8)};
+  else return wf2{(float)(short)(v & 0xffffu), (float)((int)v >> 16)};
+}
+
+// (raw DUAL: the gain pairs next to the raw and mask ones need a few registers more than five waves per SIMD
+// leave, so it aims at four rather than spill)
+template <bool DUAL, bool HALF, int RAW = 0>
+__global__ __launch_bounds__(256, (RAW && DUAL) ? 4 : WF5_MIN_WAVES) void xc_rows_fwd_wave512(
     const void* __restrict__ src_any, const int64_t* __restrict__ job_off, int64_t row_stride,
     const int* __restrict__ expo_a, const int* __restrict__ expo_b, const float* __restrict__ mask,
     const float* __restrict__ mean_rstd, cfloat* __restrict__ T1a, cfloat* __restrict__ T1b,
-    const cfloat* __restrict__ tw_row, XcGeom g, const int2* __restrict__ chord) {
+    const cfloat* __restrict__ tw_row, XcGeom g, const int2* __restrict__ chord,
+    const float* __restrict__ gain, int64_t frame_area, const float* __restrict__ job_sub) {
   __shared__ __attribute__((aligned(16))) wf2 slabs[4][WF5_SLAB];
   __shared__ __attribute__((aligned(16))) wf2 tab[WF5_TWA + WF5_TWB + WF5_TWK];
   const wf2* twA = tab;
@@ -770,11 +795,13 @@ __global__ __launch_bounds__(256, WF5_MIN_WAVES) void xc_rows_fwd_wave512(
       if (i < NTAB) tab[i] = wf_from(tv[j]);
     }
   }
-  const float mean = mean_rstd ? mean_rstd[0] : 0.f;
+  const float mean = RAW ? job_sub[job] : (mean_rstd ? mean_rstd[0] : 0.f);
   const float rstd = mean_rstd ? mean_rstd[1] : 1.f;
   const int ea = expo_a[job], eb = DUAL ? expo_b[job] : 1;
-  const float* base = HALF ? nullptr : static_cast<const float*>(src_any) + job_off[job];
+  const float* base = (HALF || RAW) ? nullptr : static_cast<const float*>(src_any) + job_off[job];
   const _Float16* base_h = HALF ? static_cast<const _Float16*>(src_any) + job_off[job] : nullptr;
+  const char* base_r = RAW ? static_cast<const char*>(src_any) + job_off[job] * (RAW == 1 ? 1 : 2) : nullptr;
+  const float* gbase = RAW ? gain + job_off[job] % frame_area : nullptr;
   cfloat* outa = T1a + (int64_t)job * g.nkx * g.ny;
   cfloat* outb = DUAL ? T1b + (int64_t)job * g.nkx * g.ny : nullptr;
   const int r16 = grp * WF5_ROWS_PER_WG;
@@ -791,19 +818,36 @@ __global__ __launch_bounds__(256, WF5_MIN_WAVES) void xc_rows_fwd_wave512(
     const int xlo = chord ? chord[y].x : bxlo, xhi = chord ? chord[y].y + 2 : bxhi;
     int tl = t;
     asm volatile("" : "+v"(tl));  // per-row addresses are re-derived, not carried (registers)
-    const float* row = HALF ? nullptr : base + (int64_t)y * row_stride;
+    const float* row = (HALF || RAW) ? nullptr : base + (int64_t)y * row_stride;
     const _Float16* row_h = HALF ? base_h + (int64_t)y * row_stride : nullptr;
+    const char* row_r = RAW ? base_r + (int64_t)y * row_stride * (RAW == 1 ? 1 : 2) : nullptr;
+    const float* grow = RAW ? gbase + (int64_t)y * row_stride : nullptr;
     const float* mrow = mask + (int64_t)y * g.W;
     wf2 A[8], Bv[8], mk[8];
+    if constexpr (RAW != 0) {
+      unsigned rv[8];
 #pragma unroll
-    for (int n1 = 0; n1 < 8; ++n1) {  // all sixteen loads in flight before anything is used
-      const int x = 128 * n1 + 2 * tl;
-      const int xc = min(max(x, xlo), xhi);  // outside the support: mask == 0
-      A[n1] = HALF ? wf5_ld2h(row_h + xc) : wf5_ld2(row + xc);
-      mk[n1] = *reinterpret_cast<const wf2*>(mrow + x);
+      for (int n1 = 0; n1 < 8; ++n1) {  // raw, gain and mask loads all in flight before anything is used
+        const int x = 128 * n1 + 2 * tl;
+        const int xc = min(max(x, xlo), xhi);  // outside the support: mask == 0
+        rv[n1] = wf5_ld2raw<RAW>(row_r, xc);
+        A[n1] = wf5_ld2(grow + xc);  // the gain pair, multiplied in place below
+        mk[n1] = *reinterpret_cast<const wf2*>(mrow + x);
+      }
+#pragma unroll
+      for (int n1 = 0; n1 < 8; ++n1)
+        A[n1] = __builtin_elementwise_fma(wf5_widen2raw<RAW>(rv[n1]), A[n1], wf2{-mean, -mean}) * rstd;
+    } else {
+#pragma unroll
+      for (int n1 = 0; n1 < 8; ++n1) {  // all sixteen loads in flight before anything is used
+        const int x = 128 * n1 + 2 * tl;
+        const int xc = min(max(x, xlo), xhi);  // outside the support: mask == 0
+        A[n1] = HALF ? wf5_ld2h(row_h + xc) : wf5_ld2(row + xc);
+        mk[n1] = *reinterpret_cast<const wf2*>(mrow + x);
+      }
+#pragma unroll
+      for (int n1 = 0; n1 < 8; ++n1) A[n1] = (A[n1] - mean) * rstd;
     }
-#pragma unroll
-    for (int n1 = 0; n1 < 8; ++n1) A[n1] = (A[n1] - mean) * rstd;
     if (DUAL && ea == 1 && eb == 2) {  // the leave-one-out schedule's only pair: mask and mask^2, no power loop
 #pragma unroll
       for (int n1 = 0; n1 < 8; ++n1) {
@@ -1912,7 +1956,8 @@ int mc_xc_rows_forward_dual_t(const void* src, int storage, const int64_t* job_o
 #define MC_W512_GO(D, H)                                                                              \
   hipLaunchKernelGGL((xc_rows_fwd_wave512<D, H>), grid, dim3(256), 0, (hipStream_t)stream, src, job_off, \
                      row_stride, expo_a, D ? expo_b : (const int*)nullptr, mask, mean_rstd, (cfloat*)T1a, \
-                     D ? (cfloat*)T1b : (cfloat*)nullptr, (const cfloat*)tw_row, g, (const int2*)row_chord)
+                     D ? (cfloat*)T1b : (cfloat*)nullptr, (const cfloat*)tw_row, g, (const int2*)row_chord,         \
+                     (const float*)nullptr, (int64_t)1, (const float*)nullptr)
   if (expo_b) {
     if (half) MC_W512_GO(true, true);
     else MC_W512_GO(true, false);
@@ -1921,6 +1966,39 @@ int mc_xc_rows_forward_dual_t(const void* src, int storage, const int64_t* job_o
     else MC_W512_GO(false, false);
   }
 #undef MC_W512_GO
+  return mc_check_launch();
+}
+
+// N2: patch rows straight from the raw bytes of a u8 / i16 movie (the wave-per-row 1024-sample engine only).
+int mc_xc_rows_forward_dual_raw(const void* raw, int storage, const float* gain, int64_t frame_area,
+                                const int64_t* job_off, int64_t row_stride, const int* expo_a, const int* expo_b,
+                                const float* mask, const float* job_sub, const float* mean_rstd, void* T1a, void* T1b,
+                                const void* tw_row, int njobs, const mc_xc_geom* q, const int* row_chord,
+                                void* stream) {
+  if (storage != MC_STORE_U8 && storage != MC_STORE_I16) return MC_ERR_UNSUPPORTED;
+  XcGeom g;
+  int rc = geom_from(q, &g, true, false);
+  if (rc) return rc;
+  if (!raw || !gain || !job_off || !expo_a || !mask || !job_sub || !mean_rstd || !T1a || !tw_row || njobs < 1 ||
+      (expo_b && !T1b) || frame_area < 1 || row_stride < 1)
+    return MC_ERR_ARG;
+  if (g.W != 2 * WF5_N || g.nkx > 128 || (g.ny % 8) || (reinterpret_cast<uintptr_t>(mask) & 7) ||
+      (reinterpret_cast<uintptr_t>(gain) & 3) || (storage == MC_STORE_I16 && (reinterpret_cast<uintptr_t>(raw) & 1)))
+    return MC_ERR_UNSUPPORTED;
+  dim3 grid(njobs, (g.ny + WF5_ROWS_PER_WG - 1) / WF5_ROWS_PER_WG);
+#define MC_W512_RAW(D, R)                                                                                       \
+  hipLaunchKernelGGL((xc_rows_fwd_wave512<D, false, R>), grid, dim3(256), 0, (hipStream_t)stream, raw, job_off,   \
+                     row_stride, expo_a, D ? expo_b : (const int*)nullptr, mask, mean_rstd, (cfloat*)T1a,        \
+                     D ? (cfloat*)T1b : (cfloat*)nullptr, (const cfloat*)tw_row, g, (const int2*)row_chord, gain, \
+                     frame_area, job_sub)
+  if (expo_b) {
+    if (storage == MC_STORE_U8) MC_W512_RAW(true, 1);
+    else MC_W512_RAW(true, 2);
+  } else {
+    if (storage == MC_STORE_U8) MC_W512_RAW(false, 1);
+    else MC_W512_RAW(false, 2);
+  }
+#undef MC_W512_RAW
   return mc_check_launch();
 }
 

@@ -379,14 +379,10 @@ def patch_field(img, stats, pixel_spacing, reference_frame, reference_strategy, 
     centres (estimate_motion_xc.py:250-411).  `img` is the (already pre-corrected)
     stack; `stats` = central-box statistics to normalise with inside K1, or None when
     `img` is already normalised.  `field0` = prior field resampled to (2,t,gh,gw) or None."""
-    lib = _lib.load()
     t, h, w = img.shape
     dev = img.device
     p = int(patch_sidelength)
-    if reference_strategy not in ("middle_frame", "mean_except_current"):
-        raise ValueError(f"Unknown reference_strategy: {reference_strategy}")
-    if p > h or p > w:
-        raise ValueError(f"patch_sidelength {p} exceeds the frame size {h}x{w}")
+    _check_patch_args(reference_strategy, p, h, w)
     pl = planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev)
     g = pl.geom
     if img.dtype != torch.float32 and not (g.W == 1024 and g.nkx <= 128 and g.ny % 8 == 0):
@@ -395,6 +391,37 @@ def patch_field(img, stats, pixel_spacing, reference_frame, reference_strategy, 
         if stats is not None:
             pass  # the statistics were taken from the fp16 bytes: identical values
         img = img.float()
+    src = [img]
+
+    def spectra(off, ex, frames, expo_b=None, min_expo=None):
+        try:
+            return _forward_spectra(src[0], off, w, ex, pl, stats, job_expo_b=expo_b, min_expo=min_expo)
+        except _lib.McorrUnsupported:
+            if src[0].dtype == torch.float32:
+                raise
+            src[0] = src[0].float()  # the C side has no fp16 kernel for this case after all: widen once
+            return _forward_spectra(src[0], off, w, ex, pl, stats, job_expo_b=expo_b, min_expo=min_expo)
+
+    return _patch_field_core((t, h, w), dev, pl, p, pixel_spacing, reference_frame, reference_strategy,
+                             sub_pixel_refinement, temporal_smoothing, smoothing_window_size, field0,
+                             outlier_rejection, outlier_threshold, spectra)
+
+
+def _check_patch_args(reference_strategy, p, h, w):
+    if reference_strategy not in ("middle_frame", "mean_except_current"):
+        raise ValueError(f"Unknown reference_strategy: {reference_strategy}")
+    if p > h or p > w:
+        raise ValueError(f"patch_sidelength {p} exceeds the frame size {h}x{w}")
+
+
+def _patch_field_core(shape, dev, pl, p, pixel_spacing, reference_frame, reference_strategy, sub_pixel_refinement,
+                      temporal_smoothing, smoothing_window_size, field0, outlier_rejection, outlier_threshold,
+                      spectra):
+    """The patch estimator after its K1 source is chosen: `spectra(job_off, job_expo, frames, expo_b, min_expo)`
+    returns the filtered spectra of the jobs (a pair with `expo_b`); `frames` = each job's frame index."""
+    lib = _lib.load()
+    t, h, w = shape
+    g = pl.geom
     cy, cx = lattice.patch_grid_centers(t, h, w, p)
     gh, gw = len(cy), len(cx)
     npatch = gh * gw
@@ -412,7 +439,7 @@ def patch_field(img, stats, pixel_spacing, reference_frame, reference_strategy, 
     def jobs(frames, expos):
         off = (np.asarray(frames, dtype=np.int64)[:, None] * (h * w) + origin[None, :]).reshape(-1)
         ex = np.repeat(np.asarray(expos, dtype=np.int32), npatch)
-        return _i64(off, dev), _i32(ex, dev)
+        return _i64(off, dev), _i32(ex, dev), np.repeat(np.asarray(frames, dtype=np.int64), npatch)
 
     nproc = len(processed)
     if nproc > 0:
@@ -421,14 +448,8 @@ def patch_field(img, stats, pixel_spacing, reference_frame, reference_strategy, 
                 raise ValueError("mean_except_current needs at least 2 frames")
             if ref_expo.max() > 1 or cur_expo.max() > 0:
                 raise NotImplementedError("unexpected mask schedule")
-            off, ex1 = jobs(range(t), [1] * t)
-            try:
-                U, V = _forward_spectra(img, off, w, ex1, pl, stats, job_expo_b=ex1 * 2, min_expo=1)
-            except _lib.McorrUnsupported:
-                if img.dtype == torch.float32:
-                    raise
-                img = img.float()  # the C side has no fp16 kernel for this case after all: widen once
-                U, V = _forward_spectra(img, off, w, ex1, pl, stats, job_expo_b=ex1 * 2, min_expo=1)
+            off, ex1, fr = jobs(range(t), [1] * t)
+            U, V = spectra(off, ex1, fr, expo_b=ex1 * 2, min_expo=1)
             sp, si, sr = lattice.leave_one_out_schedule(ref_expo)
             sp, si, sr = _i32(sp, dev), _i32(si, dev), torch.as_tensor(sr, device=dev)
             REF = torch.empty_like(U)
@@ -439,17 +460,11 @@ def patch_field(img, stats, pixel_spacing, reference_frame, reference_strategy, 
             S_cur, S_ref = U, REF
         else:
             exl = [int(cur_expo[f]) + 1 for f in processed]
-            off, ex = jobs(processed, exl)
-            try:
-                S_cur = _forward_spectra(img, off, w, ex, pl, stats, min_expo=min(exl))
-            except _lib.McorrUnsupported:
-                if img.dtype == torch.float32:
-                    raise
-                img = img.float()
-                S_cur = _forward_spectra(img, off, w, ex, pl, stats, min_expo=min(exl))
+            off, ex, fr = jobs(processed, exl)
+            S_cur = spectra(off, ex, fr, min_expo=min(exl))
             exl = [int(ref_read[f]) + 1 for f in processed]
-            off, ex = jobs([reference_frame] * nproc, exl)
-            S_ref = _forward_spectra(img, off, w, ex, pl, stats, min_expo=min(exl))
+            off, ex, fr = jobs([reference_frame] * nproc, exl)
+            S_ref = spectra(off, ex, fr, min_expo=min(exl))
         pair_idx = torch.arange(nproc * npatch, device=dev, dtype=torch.int32)
         peaks, _, nb = _peaks(S_cur, pair_idx, S_ref, pair_idx, pl, want_nbhd=sub_pixel_refinement)
         flags = (1 if sub_pixel_refinement else 0) | (2 if outlier_rejection else 0)
@@ -1150,6 +1165,79 @@ def warp_rigid_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want
         run()
     if rm.n_hot:
         _warp_hot_correct(lib, rm, scratch, frames, total, stream_ptr(dev))
+    return frames, total
+
+
+def _local_raw_check(rm: RawMovie):
+    if rm.hot_pixel_threshold is not None:
+        raise _lib.McorrUnsupported("the fused local-motion route has no hot-pixel corrections: condition the movie")
+
+
+def patch_field_raw(rm: RawMovie, pixel_spacing, reference_frame, reference_strategy, b_factor, frequency_range,
+                    patch_sidelength, sub_pixel_refinement, temporal_smoothing, smoothing_window_size,
+                    outlier_rejection, outlier_threshold):
+    """patch_field of the conditioned movie (condition_movie, then the central-box statistics) straight from a
+    RawMovie: the 1024-px patch row pass reads the raw bytes and the gain (mc_xc_rows_forward_dual_raw) and
+    subtracts each job's frame mean + box mean.  Raises McorrUnsupported for any shape that needs another kernel
+    (patch sizes other than 1024, a hot-pixel threshold); there is no silent fall-back."""
+    _local_raw_check(rm)
+    lib = _lib.load()
+    t, h, w = rm.shape
+    dev = rm.raw.device
+    p = int(patch_sidelength)
+    _check_patch_args(reference_strategy, p, h, w)
+    pl = planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev)
+    g = pl.geom
+    if not _wave512_ok(g, True, True, 1):
+        raise _lib.McorrUnsupported(f"no raw patch kernel for {p}-px patches (1024 only)")
+    st = stream_ptr(dev)
+
+    def spectra(off, ex, frames, expo_b=None, min_expo=None):
+        if min_expo is None or min_expo < 1:
+            raise _lib.McorrUnsupported("the raw patch kernel needs mask exponents >= 1")
+        njobs = int(off.numel())
+        sub = rm.sub[torch.as_tensor(frames, device=dev)].contiguous()  # each job's frame mean + box mean
+        dual = expo_b is not None
+        S = torch.empty((njobs, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
+        Sb = torch.empty_like(S) if dual else None
+        per_job = g.nkx * g.ny * 8 * (2 if dual else 1)
+        chunk = max(1, min(njobs, WORKSPACE_BYTES // per_job))
+        T1 = torch.empty((chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
+        T1b = torch.empty_like(T1) if dual else None
+        for a in range(0, njobs, chunk):
+            n = min(chunk, njobs - a)
+            check(lib.mc_xc_rows_forward_dual_raw(ptr(rm.raw), rm.kind, ptr(rm.gain), h * w, ptr(off[a:a + n]), w,
+                                                  ptr(ex[a:a + n]), ptr(expo_b[a:a + n]) if dual else None,
+                                                  ptr(pl.mask), ptr(sub[a:a + n]), ptr(rm.mean_rstd), ptr(T1),
+                                                  ptr(T1b), ptr(pl.tw_row), n, g,
+                                                  ptr(pl.chord) if USE_ROW_CHORDS else None, st),
+                  "mc_xc_rows_forward_dual_raw")
+            check(_k2(lib, g, dev, T1, pl.filt, S[a:a + n], pl.tw_col, n, st), "xc cols forward")
+            if dual:
+                check(_k2(lib, g, dev, T1b, pl.filt, Sb[a:a + n], pl.tw_col, n, st), "xc cols forward")
+        return (S, Sb) if dual else S
+
+    return _patch_field_core((t, h, w), dev, pl, p, pixel_spacing, reference_frame, reference_strategy,
+                             sub_pixel_refinement, temporal_smoothing, smoothing_window_size, None,
+                             outlier_rejection, outlier_threshold, spectra)
+
+
+def warp_field_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want_sum=False):
+    """``warp(img, lattices, ...)`` (deformation-field lattices) of the conditioned movie without materialising it
+    (mc_warp_frames_raw).  Raises McorrUnsupported outside the raw kernel's shapes."""
+    _local_raw_check(rm)
+    lib = _lib.load()
+    t, h, w = rm.shape
+    dev = rm.raw.device
+    _, _, GH, GW = lattices.shape
+    frames = torch.empty((t, h, w), dtype=torch.float32, device=dev) if want_frames else None
+    total = torch.empty((h, w), dtype=torch.float32, device=dev) if want_sum else None
+    nbytes = C.c_int64(0)
+    check(lib.mc_warp_scratch_bytes(t, h, w, GH, GW, C.byref(nbytes)), "mc_warp_scratch_bytes")
+    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+    check(lib.mc_warp_frames_raw(ptr(rm.raw), rm.kind, ptr(rm.gain), ptr(rm.mu), t, h, w, ptr(lattices.contiguous()),
+                                 GH, GW, float(pixel_spacing), ptr(scratch), ptr(frames), ptr(total), stream_ptr(dev)),
+          "mc_warp_frames_raw")
     return frames, total
 
 
