@@ -376,6 +376,16 @@ int mc_warp_frames_raw(const void* raw, int storage, const float* gain, const fl
                        const float* lattice, int GH, int GW, float pixel_spacing, float* scratch, float* out_frames,
                        float* out_sum, void* stream);
 
+/* mc_warp_frames_raw with the sum ACCUMULATED: out_sum (required) += this call's frame sum, each element by the one
+ * lane that owns it (old + tile sum), then warp_field_slow adds its tile-frames as in mc_warp_frames_raw.  A movie
+ * warped a chunk of frames at a time -- mc_warp_frames_raw for the first chunk, this for the rest, in stream order
+ * -- sums to ((s_0 + s_1) + s_2) + ... of the per-chunk sums, reproducible bit for bit when no tile-frame takes
+ * the slow kernel (with it, a chunk adds (old + fast) + slow).  NULL inputs or out_sum: MC_ERR_ARG before any
+ * launch; shapes as mc_warp_frames_raw. */
+int mc_warp_frames_raw_accumulate(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h,
+                                  int w, const float* lattice, int GH, int GW, float pixel_spacing, float* scratch,
+                                  float* out_frames, float* out_sum, void* stream);
+
 /* N2: the rigid warp (correct_motion for a (2,t,1,1) field, correct_motion.py:18-78) fed from the RAW movie:
  * every sample is conditioned as raw * gain - mu[f] on its way to the resampler (examples/ttMotion.py:90-121,
  * 180-199), so the result equals mc_warp_rigid on the output of mc_condition_movie without that fp32 movie.
@@ -384,6 +394,14 @@ int mc_warp_frames_raw(const void* raw, int storage, const float* gain, const fl
 int mc_warp_rigid_raw(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h, int w,
                       const float* shifts_px, float* scratch, float* out_frames, float* out_sum, int phase,
                       void* stream);
+
+/* mc_warp_rigid_raw with the sum ACCUMULATED: out_sum (required) += this call's frame sum, each element by the one
+ * lane that owns it (old + tile sum).  Chunks of a movie -- mc_warp_rigid_raw for the first, this for the rest, in
+ * stream order -- sum to ((s_0 + s_1) + s_2) + ... bit for bit.  NULL inputs or out_sum: MC_ERR_ARG before any
+ * launch; shapes and phase as mc_warp_rigid_raw. */
+int mc_warp_rigid_raw_accumulate(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h,
+                                 int w, const float* shifts_px, float* scratch, float* out_frames, float* out_sum,
+                                 int phase, void* stream);
 
 /* The tail of the rigid movie pipeline in two launches: integer-peak shifts (t,2) px of estimate_global_motion ->
  * field (2,t) Angstrom (image_shifts_to_deformation_field, deformation_field_utils.py:129-162), the per-frame

@@ -21,6 +21,7 @@ from .api import (  # noqa: F401
     motion_correct_raw,
     motion_correct_raw_patches,
     motion_correct_sum,
+    motion_correct_sum_raw,
     resample_deformation_field,
 )
 from ._lib import McorrError  # noqa: F401
@@ -45,6 +46,7 @@ __all__ = [
     "motion_correct_sum",
     "motion_correct_raw",
     "motion_correct_raw_patches",
+    "motion_correct_sum_raw",
     "dose_weighted_sum",
     "condition_movie",
     "evaluate_deformation_field_at_t",

@@ -96,9 +96,11 @@ SIGNATURES = {
     "mc_xc_rows_forward_raw": [vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, GP, vp, vp],
     "mc_xc_rows_forward_dual_raw": [vp, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, GP, vp, vp],
     "mc_warp_frames_raw": [vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, f32, vp, vp, vp, vp],
+    "mc_warp_frames_raw_accumulate": [vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, f32, vp, vp, vp, vp],
     "mc_xcg_rows_forward_raw": [vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, LP, i32, GP, vp],
     "mc_rigid_tables_from_shifts": [vp, f32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "mc_warp_rigid_raw": [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp],
+    "mc_warp_rigid_raw_accumulate": [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp],
     "mc_condition_movie_hot": [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp],
     "mc_raw_hot_detect": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp, vp, vp],
     "mc_raw_hot_finalize": [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],

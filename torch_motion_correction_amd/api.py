@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import functools
 import inspect
+import math
 
 import torch
 
@@ -358,9 +359,38 @@ def condition_movie(movie, gain=None, mean_zero=True, device=None, hot_pixel_thr
     return res.to(out_dev)
 
 
+def _check_dose(dose_per_frame):
+    """None, or a finite dose >= 0 (e/A^2 per frame) as a float; ValueError otherwise (before any device is touched)."""
+    if dose_per_frame is None:
+        return None
+    try:
+        v = float(dose_per_frame)
+    except (TypeError, ValueError):
+        raise ValueError(f"dose_per_frame must be a finite number >= 0, got {dose_per_frame!r}") from None
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ValueError(f"dose_per_frame must be a finite number >= 0, got {dose_per_frame!r}")
+    return v
+
+
+def _fused_sums(rm, lat, ps, rigid, dose, pre_exposure, voltage, want_plain, want_frames):
+    """(sum, plain sum or None, frames or None) of a RawMovie through `lat`: motion_correct_sum's three cases, the
+    warps reading the raw bytes.  Raises McorrUnsupported where a fused kernel is missing."""
+    warp = engine.warp_rigid_raw if rigid else engine.warp_field_raw
+    if dose is None:
+        frames, total = warp(rm, lat, ps, want_frames=want_frames, want_sum=True)
+        return total, None, frames
+    if want_frames:  # the frames are an output anyway: weight them as motion_correct_sum does
+        frames, plain = warp(rm, lat, ps, want_frames=True, want_sum=want_plain)
+        return engine.dose_weighted_sum(frames, ps, dose, float(pre_exposure), float(voltage)), plain, frames
+    total, plain = engine.warp_dose_weighted_sum_raw(rm, lat, ps, rigid, dose, float(pre_exposure), float(voltage),
+                                                     want_plain)
+    return total, plain, None
+
+
 def motion_correct_raw(movie, gain, pixel_spacing, reference_frame=None, b_factor=500, frequency_range=(300, 10),
                        grid_type="catmull_rom", mean_zero=True, return_frames=False, device=None,
-                       hot_pixel_threshold=None, return_hot_counts=False):
+                       hot_pixel_threshold=None, return_hot_counts=False, dose_per_frame=None, pre_exposure=0.0,
+                       voltage=300.0):
     """The reference pipeline's gain_correct -> set_frames_mean_zero -> estimate_global_motion -> correct_motion
     -> sum (examples/ttMotion.py:90-121, 180-199, 286-398) for a RAW uint8 / int16 movie, with the conditioning
     fused into the kernels that read the raw bytes: one statistics pass, then the estimator's row transform and
@@ -374,15 +404,22 @@ def motion_correct_raw(movie, gain, pixel_spacing, reference_frame=None, b_facto
     (examples/ttMotion.py:127-172) between the gain and the mean, with condition_movie's deterministic
     replacement; the fused route applies the few hot pixels as sparse corrections (engine.RawMovie).  A threshold
     that finds more hot pixels than the fused list holds takes the condition_movie route.  ``return_hot_counts``
-    appends the number of hot pixels per frame (zeros without a threshold)."""
+    appends the number of hot pixels per frame (zeros without a threshold).
+
+    ``dose_per_frame`` (e/A^2; with ``pre_exposure`` and ``voltage``) makes the returned sum the exposure-filtered
+    one, as ``motion_correct_sum(..., dose_per_frame=...)`` computes it: on the row-major frame sizes the frames are
+    warped from the raw bytes, transformed and weighted a chunk at a time (engine.warp_dose_weighted_sum_raw); the
+    field is the same.  For the plain sum as well, pass the field to ``motion_correct_sum_raw(...,
+    return_plain_sum=True)``."""
     thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # ValueError before any device is touched
+    dose = _check_dose(dose_per_frame)
     return _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, grid_type,
-                               mean_zero, return_frames, device, thr, return_hot_counts)
+                               mean_zero, return_frames, device, thr, return_hot_counts, dose, pre_exposure, voltage)
 
 
 @_on_gpu
 def _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, grid_type, mean_zero,
-                        return_frames, device, thr, return_hot_counts):
+                        return_frames, device, thr, return_hot_counts, dose, pre_exposure, voltage):
     out_dev = _out_device(movie, device)
     dev = require_gpu(out_dev)
     raw = movie.detach().to(dev)
@@ -398,7 +435,7 @@ def _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, f
             shifts = engine.global_shifts_raw(rm, ref, ps, float(b_factor), tuple(frequency_range))
             field = image_shifts_to_deformation_field(shifts, ps)
             lat = engine.frame_lattices(field.contiguous(), t, grid_type)
-            frames, total = engine.warp_rigid_raw(rm, lat, ps, want_frames=bool(return_frames), want_sum=True)
+            total, _, frames = _fused_sums(rm, lat, ps, True, dose, pre_exposure, voltage, False, bool(return_frames))
             counts = rm.hot_counts
         except McorrUnsupported:
             fused = False
@@ -409,7 +446,14 @@ def _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, f
         shifts = engine.global_shifts(img, ref, ps, float(b_factor), tuple(frequency_range))
         field = image_shifts_to_deformation_field(shifts, ps)
         lat = engine.frame_lattices(field.contiguous(), t, grid_type)
-        frames, total = engine.warp(img, lat, ps, want_frames=bool(return_frames), want_sum=True, rigid=True)
+        if dose is None:
+            frames, total = engine.warp(img, lat, ps, want_frames=bool(return_frames), want_sum=True, rigid=True)
+        elif return_frames:  # motion_correct_sum's two dose-weighted forms
+            frames, _ = engine.warp(img, lat, ps, want_frames=True, want_sum=False, rigid=True)
+            total = engine.dose_weighted_sum(frames, ps, dose, float(pre_exposure), float(voltage))
+        else:
+            frames = None
+            total = engine.warp_dose_weighted_sum(img, lat, ps, True, dose, float(pre_exposure), float(voltage))
     out = [field.to(out_dev), total.to(out_dev)]
     if return_frames:
         out.append(frames.to(out_dev))
@@ -427,7 +471,9 @@ def motion_correct_raw_patches(movie, gain, pixel_spacing, patch_sidelength=1024
     """The local-motion flow of the reference pipeline for a RAW uint8 / int16 movie: ``condition_movie(movie, gain,
     mean_zero, hot_pixel_threshold)`` then ``estimate_motion_cross_correlation_patches`` and ``motion_correct_sum``
     with the field it returns.  Returns ``(field (2,t,gh,gw) Angstrom, centres (t,gh,gw,3) int64, sum (h,w)[, frames
-    (t,h,w)][, hot counts (t,) int32])``.
+    (t,h,w)][, hot counts (t,) int32])``.  The exposure-filtered sum (the example's ``dose_weight`` step) of the same
+    movie comes from ``motion_correct_sum_raw(movie, gain, field, pixel_spacing, grid_type=grid_type,
+    dose_per_frame=..., return_plain_sum=True)`` with the field returned here: again no fp32 movie.
 
     Fused route (no conditioned fp32 movie is allocated): u8 / i16 movies, 1024-px patches, no prior
     ``deformation_field`` and no ``hot_pixel_threshold``.  The patch row pass and the field warp read the raw bytes
@@ -499,6 +545,71 @@ def _motion_correct_raw_patches(movie, gain, pixel_spacing, patch_sidelength, re
     if return_hot_counts:
         out.append(torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None else counts.to(out_dev))
     return tuple(out)
+
+
+def motion_correct_sum_raw(movie, gain, deformation_grid, pixel_spacing, grid_type="catmull_rom", mean_zero=True,
+                           hot_pixel_threshold=None, dose_per_frame=None, pre_exposure=0.0, voltage=300.0,
+                           return_plain_sum=False, return_frames=False, device=None):
+    """``motion_correct_sum`` of ``condition_movie(movie, gain, mean_zero, hot_pixel_threshold)`` for a RAW uint8 /
+    int16 movie and a (2,t,gh,gw) Angstrom field -- from ``motion_correct_raw``, ``motion_correct_raw_patches`` or
+    ``read_deformation_field_from_csv`` -- without the conditioned fp32 movie: the warps read the raw bytes and form
+    ``raw * gain - frame mean`` on the fly.  Without ``dose_per_frame`` the result is the plain aligned sum, bit for
+    bit the one motion_correct_raw / motion_correct_raw_patches return for that field.  With it (e/A^2; with
+    ``pre_exposure`` and ``voltage``) the sum is exposure-filtered as the example's ``dose_weight`` step
+    (examples/ttMotion.py:331-351, 398-404) and motion_correct_sum(..., dose_per_frame=...): on the row-major frame
+    sizes the frames are warped, transformed and weighted a chunk at a time, so the corrected movie is not held
+    either.  ``return_plain_sum`` (needs a dose) also returns the plain sum, accumulated by the same warp launches:
+    the example's two images for one pass over the movie.
+
+    Returns ``sum (h,w)``, or the tuple ``(sum[, plain sum][, frames (t,h,w)])``.  A (2,t,1,1) field takes the rigid
+    warp.  fp16 / fp32 movies, shapes without fused kernels, a local field with ``hot_pixel_threshold`` (the local
+    raw warp has no hot-pixel corrections) and a hot-pixel list overflow take exactly the conditioned route."""
+    dose = _check_dose(dose_per_frame)  # every argument rule before any device is touched
+    if return_plain_sum and dose is None:
+        raise ValueError("return_plain_sum needs dose_per_frame: without a dose the result is the plain sum")
+    thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)
+    field = deformation_grid
+    if not isinstance(field, torch.Tensor) or field.dim() != 4 or field.shape[0] != 2 or min(field.shape) < 1:
+        raise ValueError(f"deformation_grid must be a (2, nt, gh, gw) tensor, got {tuple(getattr(field, 'shape', ()))}")
+    if movie.dim() != 3:
+        raise ValueError(f"movie must be (t, h, w), got {tuple(movie.shape)}")
+    if gain is not None and tuple(gain.shape) != tuple(movie.shape[-2:]):
+        raise ValueError(f"gain reference has shape {tuple(gain.shape)}, frames are {tuple(movie.shape[-2:])}")
+    return _motion_correct_sum_raw(movie, gain, field, pixel_spacing, grid_type, mean_zero, thr, dose, pre_exposure,
+                                   voltage, bool(return_plain_sum), bool(return_frames), device)
+
+
+@_on_gpu
+def _motion_correct_sum_raw(movie, gain, field, pixel_spacing, grid_type, mean_zero, thr, dose, pre_exposure, voltage,
+                            want_plain, want_frames, device):
+    out_dev = _out_device(movie, device)
+    dev = require_gpu(out_dev)
+    raw = movie.detach().to(dev)
+    t = raw.shape[0]
+    ps = float(pixel_spacing)
+    gd = None if gain is None else gain.to(dev)
+    field = _stage(field, dev)
+    rigid = RIGID_FAST_PATH and _is_rigid(field)
+    fused = raw.dtype in (torch.uint8, torch.int16)
+    if fused:
+        try:
+            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
+            lat = engine.frame_lattices(field, t, grid_type)
+            total, plain, frames = _fused_sums(rm, lat, ps, rigid, dose, pre_exposure, voltage, want_plain, want_frames)
+        except McorrUnsupported:
+            fused = False
+    if not fused:  # exactly condition_movie, then motion_correct_sum (once more without the dose for the plain sum)
+        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr)
+        res = motion_correct_sum(img, field, ps, grid_type=grid_type, return_frames=want_frames, dose_per_frame=dose,
+                                 pre_exposure=pre_exposure, voltage=voltage)
+        total, frames = res if want_frames else (res, None)
+        plain = motion_correct_sum(img, field, ps, grid_type=grid_type) if want_plain else None
+    out = [total.to(out_dev)]
+    if want_plain:
+        out.append(plain.to(out_dev))
+    if want_frames:
+        out.append(frames.to(out_dev))
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 @_on_gpu

@@ -1509,7 +1509,9 @@ __device__ __forceinline__ rr_f2 rr_dot5(const rr_f2 (&wv)[5], rr_f2 e0, rr_f2 e
   return __builtin_elementwise_fma(wv[4], e4, r);
 }
 
-template <bool WRITE_FRAMES, bool WRITE_SUM, bool FULL, int KIND>
+// TAG = the calling kernel's ACCUM: the accumulating kernels inline strip instances of their own, so the other
+// kernels keep their code (sharing one instance with them changed those kernels' register allocation).
+template <bool WRITE_FRAMES, bool WRITE_SUM, bool FULL, int KIND, bool TAG = false>
 __device__ __forceinline__ void rigid_strip_raw(const RigidArgs& a, unsigned rawrow, int m, const float* gplane,
                                                 const int (&gofs)[8], float negmu, int f, int y0, int x0, float wyv,
                                                 const float (&wx)[5][4], float (&acc)[RIGID_ROWS][4]) {
@@ -1588,7 +1590,9 @@ __device__ __forceinline__ void rr_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <bool WRITE_FRAMES, bool WRITE_SUM, int KIND>
+// ACCUM: the sum store adds the tile's register sum to what out_sum holds (one writer per element: the tile's
+// owner lane), so a movie warped a chunk of frames at a time sums to ((s_0 + s_1) + s_2) + ... in launch order.
+template <bool WRITE_FRAMES, bool WRITE_SUM, int KIND, bool ACCUM = false>
 __global__ __launch_bounds__(RIGID_LANES * 8, 2) void warp_rigid_raw(RigidRawArgs ra) {
   using RW = RawWin<KIND>;
   constexpr int WX = 2, WY = 4, NWAVES = 8, NBUF = RW::NBUF;
@@ -1761,8 +1765,8 @@ __global__ __launch_bounds__(RIGID_LANES * 8, 2) void warp_rigid_raw(RigidRawArg
     const unsigned rawrow = (unsigned)reinterpret_cast<uintptr_t>((cur ? wb1 : wb0) + lane * 4 * RW::SB);  // LDS byte address
     const float negmu = -__int_as_float(par(f).z);
     RSTAMP(Q2);
-    if (full_tile) rigid_strip_raw<WRITE_FRAMES, WRITE_SUM, true, KIND>(a, rawrow, m, gplane, gofs, negmu, f, y0, x0, wyv, wx, acc);
-    else rigid_strip_raw<WRITE_FRAMES, WRITE_SUM, false, KIND>(a, rawrow, m, gplane, gofs, negmu, f, y0, x0, wyv, wx, acc);
+    if (full_tile) rigid_strip_raw<WRITE_FRAMES, WRITE_SUM, true, KIND, ACCUM>(a, rawrow, m, gplane, gofs, negmu, f, y0, x0, wyv, wx, acc);
+    else rigid_strip_raw<WRITE_FRAMES, WRITE_SUM, false, KIND, ACCUM>(a, rawrow, m, gplane, gofs, negmu, f, y0, x0, wyv, wx, acc);
     RSTAMP(Q3);
     if (f + 1 < a.nframes) {
       if constexpr (NBUF == 1) {
@@ -1800,7 +1804,16 @@ __global__ __launch_bounds__(RIGID_LANES * 8, 2) void warp_rigid_raw(RigidRawArg
       const int yo = y0 + ro;
       if (yo < h) {
         float* dst = a.out_sum + (int64_t)yo * w + x0;
-        if ((((uintptr_t)a.out_sum) & 15) == 0) {
+        if constexpr (ACCUM) {
+          if ((((uintptr_t)a.out_sum) & 15) == 0) {
+            const float4 o = *reinterpret_cast<const float4*>(dst);
+            *reinterpret_cast<float4*>(dst) = make_float4(o.x + acc[ro][0], o.y + acc[ro][1], o.z + acc[ro][2],
+                                                          o.w + acc[ro][3]);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dst[k] = dst[k] + acc[ro][k];
+          }
+        } else if ((((uintptr_t)a.out_sum) & 15) == 0) {
           *reinterpret_cast<float4*>(dst) = make_float4(acc[ro][0], acc[ro][1], acc[ro][2], acc[ro][3]);
         } else {
 #pragma unroll
@@ -2492,7 +2505,9 @@ __global__ __launch_bounds__(64) void warp_field_plan(FieldArgs fa, int unit_ps,
 // RAW (N2): 1 = u8, 2 = i16 frames, staged like fp16 (16-byte units from the unit-aligned column at or left
 // of the window) in the fp16 stage's space; the widening pass forms c = raw * gain - mu[f] with the gain read
 // at the same (clamped) pixel, so the fp32 window holds what mc_condition_movie would have written.
-template <bool WRITE_FRAMES, bool WRITE_SUM, bool UNIT_PS, bool HALF, int RAW = 0>
+// ACCUM: the sum store adds to what out_sum holds (old + tile sum, one writer per element), before the
+// warp_field_slow pass adds its tile-frames: a movie warped a chunk at a time sums in launch order.
+template <bool WRITE_FRAMES, bool WRITE_SUM, bool UNIT_PS, bool HALF, int RAW = 0, bool ACCUM = false>
 __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldArgs fa, const int4* __restrict__ plan) {
   static_assert(!(HALF && RAW), "fp16 or raw, not both");
   constexpr bool STAGED = HALF || RAW != 0;         // the DMA lands in a stage, a widening pass fills the window
@@ -2876,7 +2891,10 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int x = xt + lane + 64 * k;
-        if (x < w) a.out_sum[(int64_t)y * w + x] = acc[r][k];  // warp_field_slow adds its tile-frames afterwards
+        if (x < w) {  // warp_field_slow adds its tile-frames afterwards
+          float* dst = a.out_sum + (int64_t)y * w + x;
+          *dst = ACCUM ? *dst + acc[r][k] : acc[r][k];
+        }
       }
     }
   }
@@ -3242,9 +3260,28 @@ int mc_warp_frames_t(const void* frames_any, int storage, int nframes, int h, in
 
 // N2: the deformation-field warp fed from the RAW movie (warp_field3 / warp_field_slow with RAW = 1 / 2): the same
 // tables, plan and tiles as mc_warp_frames_t for fp16 frames, the raw window conditioned in the widening pass.
+static int warp_frames_raw_impl(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h,
+                                int w, const float* lattice, int GH, int GW, float pixel_spacing, float* scratch,
+                                float* out_frames, float* out_sum, bool accumulate, void* stream);
+
 int mc_warp_frames_raw(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h, int w,
                        const float* lattice, int GH, int GW, float pixel_spacing, float* scratch, float* out_frames,
                        float* out_sum, void* stream) {
+  return warp_frames_raw_impl(raw, storage, gain, mu, nframes, h, w, lattice, GH, GW, pixel_spacing, scratch, out_frames,
+                              out_sum, false, stream);
+}
+
+int mc_warp_frames_raw_accumulate(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h,
+                                  int w, const float* lattice, int GH, int GW, float pixel_spacing, float* scratch,
+                                  float* out_frames, float* out_sum, void* stream) {
+  if (!raw || !gain || !mu || !lattice || !scratch || !out_sum) return MC_ERR_ARG;
+  return warp_frames_raw_impl(raw, storage, gain, mu, nframes, h, w, lattice, GH, GW, pixel_spacing, scratch, out_frames,
+                              out_sum, true, stream);
+}
+
+static int warp_frames_raw_impl(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h,
+                                int w, const float* lattice, int GH, int GW, float pixel_spacing, float* scratch,
+                                float* out_frames, float* out_sum, bool accumulate, void* stream) {
   if (storage != MC_STORE_U8 && storage != MC_STORE_I16) return MC_ERR_UNSUPPORTED;
   if (!raw || !gain || !mu || !lattice || !scratch || (!out_frames && !out_sum)) return MC_ERR_ARG;
   if (nframes < 1 || h < 2 || w < 2 || GH < 1 || GW < 1 || !(pixel_spacing > 0.f)) return MC_ERR_ARG;
@@ -3286,22 +3323,24 @@ int mc_warp_frames_raw(const void* raw, int storage, const float* gain, const fl
   // windows at the exact column, as for fp16 (the widening pass places them)
   hipLaunchKernelGGL(warp_field_plan, dim3(a.tiles_x * a.tiles_y, nframes), dim3(64), 0, s, fa, unit ? 1 : 0, 1, plan);
   const size_t lds3 = (size_t)GW_QUADS_PAD * 16 + (size_t)2 * GW3_STAGE_UNITS * 16 + (size_t)2 * 2 * GW3_EROWS * 256 * 4;
-#define MC_GW3R_GO(F, S, U, R)                                                                    \
+#define MC_GW3R_GO(F, S, U, R, ACC)                                                               \
   do {                                                                                            \
-    auto k = warp_field3<F, S, U, false, R>;                                                      \
+    auto k = warp_field3<F, S, U, false, R, ACC>;                                                 \
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3); \
     hipLaunchKernelGGL(k, grid, block3, lds3, s, fa, (const int4*)plan);                          \
   } while (0)
-#define MC_GW3R_LAUNCH(F, S, R)                         \
+#define MC_GW3R_LAUNCH(F, S, R, ACC)                    \
   do {                                                  \
-    if (unit) MC_GW3R_GO(F, S, true, R);                \
-    else MC_GW3R_GO(F, S, false, R);                    \
+    if (unit) MC_GW3R_GO(F, S, true, R, ACC);           \
+    else MC_GW3R_GO(F, S, false, R, ACC);               \
   } while (0)
 #define MC_GW3R_MODE(R)                                                        \
   do {                                                                         \
-    if (out_frames && out_sum) MC_GW3R_LAUNCH(true, true, R);                  \
-    else if (out_frames) MC_GW3R_LAUNCH(true, false, R);                       \
-    else MC_GW3R_LAUNCH(false, true, R);                                       \
+    if (accumulate && out_frames) MC_GW3R_LAUNCH(true, true, R, true);         \
+    else if (accumulate) MC_GW3R_LAUNCH(false, true, R, true);                 \
+    else if (out_frames && out_sum) MC_GW3R_LAUNCH(true, true, R, false);      \
+    else if (out_frames) MC_GW3R_LAUNCH(true, false, R, false);                \
+    else MC_GW3R_LAUNCH(false, true, R, false);                                \
     if (unit) hipLaunchKernelGGL((warp_field_slow<true, false, R>), grid, block, 0, s, fa, out_frames ? 1 : 0, out_sum ? 1 : 0); \
     else hipLaunchKernelGGL((warp_field_slow<false, false, R>), grid, block, 0, s, fa, out_frames ? 1 : 0, out_sum ? 1 : 0); \
   } while (0)
@@ -3569,9 +3608,28 @@ int mc_rigid_tables_from_shifts(const float* shifts, float pixel_spacing, const 
 // N2: the rigid warp straight from a raw u8 / i16 movie + gain reference (warp_rigid_raw); phase as in
 // mc_warp_rigid_phase.  Shapes it has no kernel for (w % 4, unaligned buffers): MC_ERR_UNSUPPORTED -- the
 // caller conditions the movie into an fp32 copy first.
+static int warp_rigid_raw_impl(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h,
+                               int w, const float* shifts_px, float* scratch, float* out_frames, float* out_sum,
+                               int phase, bool accumulate, void* stream);
+
 int mc_warp_rigid_raw(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h, int w,
                       const float* shifts_px, float* scratch, float* out_frames, float* out_sum, int phase,
                       void* stream) {
+  return warp_rigid_raw_impl(raw, storage, gain, mu, nframes, h, w, shifts_px, scratch, out_frames, out_sum, phase,
+                             false, stream);
+}
+
+int mc_warp_rigid_raw_accumulate(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h,
+                                 int w, const float* shifts_px, float* scratch, float* out_frames, float* out_sum,
+                                 int phase, void* stream) {
+  if (!raw || !gain || !mu || !shifts_px || !scratch || !out_sum) return MC_ERR_ARG;
+  return warp_rigid_raw_impl(raw, storage, gain, mu, nframes, h, w, shifts_px, scratch, out_frames, out_sum, phase,
+                             true, stream);
+}
+
+static int warp_rigid_raw_impl(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h,
+                               int w, const float* shifts_px, float* scratch, float* out_frames, float* out_sum,
+                               int phase, bool accumulate, void* stream) {
   if (storage != MC_STORE_U8 && storage != MC_STORE_I16) return MC_ERR_UNSUPPORTED;
   if (!raw || !gain || !mu || !shifts_px || !scratch || (phase != 1 && !out_frames && !out_sum)) return MC_ERR_ARG;
   if (nframes < 1 || h < 2 || w < 2 || (((uintptr_t)scratch) & 15) || phase < 0 || phase > 2) return MC_ERR_ARG;
@@ -3596,9 +3654,13 @@ int mc_warp_rigid_raw(const void* raw, int storage, const float* gain, const flo
   ra.gain = gain; ra.mu = mu;
   const dim3 grid(ra.r.tiles_x * ra.r.tiles_y), block(RIGID_LANES, 8);
 #define MC_RAW_GO(F, SM, K) hipLaunchKernelGGL((warp_rigid_raw<F, SM, K>), grid, block, 0, s, ra) /* static LDS */
+#define MC_RAW_ACC(F, K) hipLaunchKernelGGL((warp_rigid_raw<F, true, K, true>), grid, block, 0, s, ra)
 #define MC_RAW_MODE(K)                                     \
   do {                                                     \
-    if (out_frames && out_sum) MC_RAW_GO(true, true, K);   \
+    if (accumulate) {                                      \
+      if (out_frames) MC_RAW_ACC(true, K);                 \
+      else MC_RAW_ACC(false, K);                           \
+    } else if (out_frames && out_sum) MC_RAW_GO(true, true, K); \
     else if (out_frames) MC_RAW_GO(true, false, K);        \
     else MC_RAW_GO(false, true, K);                        \
   } while (0)
@@ -3618,6 +3680,7 @@ int mc_warp_rigid_raw(const void* raw, int storage, const float* gain, const flo
   }
 #endif
 #undef MC_RAW_MODE
+#undef MC_RAW_ACC
 #undef MC_RAW_GO
   return mc_check_launch();
 }

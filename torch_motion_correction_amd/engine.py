@@ -1079,6 +1079,37 @@ class RawMovie:
                                       1 if mean_zero else 0, ptr(hstats), ptr(self.stats), ptr(self.mu),
                                       ptr(self.sub), ptr(self.mean_rstd), st), "mc_raw_hot_finalize")
 
+    def window(self, a, n):
+        """Frames [a, a+n) as a RawMovie of their own, without a copy of the movie: views of raw / mu / sub /
+        stats / hot_counts, the same gain and mean_rstd, and the hot pixels of those frames -- the slice of the
+        sorted `hot_keys` in [a*h*w, (a+n)*h*w), rebased to the window's first frame.  The warps and their hot-pixel
+        corrections (_warp_hot_correct) then work per window unchanged."""
+        t, h, w = self.shape
+        if not (0 <= a and n >= 1 and a + n <= t):
+            raise ValueError(f"frame window [{a}, {a + n}) outside a movie of {t} frames")
+        hw = h * w
+        win = object.__new__(RawMovie)
+        win.raw = self.raw[a:a + n]
+        # the raw kernels read 16-byte units from the first frame's first byte (h*w % 64 == 0 on every
+        # row-major shape, so every window of those is aligned)
+        assert win.raw.data_ptr() % 16 == 0, "frame window not 16-byte aligned"
+        win.gain, win.kind, win.shape = self.gain, self.kind, (n, h, w)
+        win.hot_pixel_threshold = self.hot_pixel_threshold
+        win.stats, win.mu, win.sub, win.mean_rstd = self.stats[a:a + n], self.mu[a:a + n], self.sub[a:a + n], self.mean_rstd
+        win.n_hot = 0
+        win.hot_keys = win.hot_rv = win.hot_counts = None
+        if self.hot_counts is not None:
+            win.hot_counts = self.hot_counts[a:a + n]
+        if self.n_hot:
+            if getattr(self, "_frame_starts", None) is None:  # one device-to-host copy per movie
+                bounds = torch.arange(t + 1, device=self.raw.device, dtype=torch.int64) * hw
+                self._frame_starts = torch.searchsorted(self.hot_keys, bounds).tolist()
+            lo, hi = self._frame_starts[a], self._frame_starts[a + n]
+            win.n_hot = hi - lo
+            win.hot_keys = self.hot_keys[lo:hi] - a * hw
+            win.hot_rv = self.hot_rv[lo:hi]
+        return win
+
     def device_tensors(self):
         """Every device tensor a consumer on another stream reads (for record_stream)."""
         return [x for x in (self.raw, self.gain, self.mu, self.sub, self.mean_rstd, self.hot_keys, self.hot_rv,
@@ -1140,13 +1171,20 @@ def global_shifts_raw(rm: RawMovie, reference_frame, pixel_spacing, b_factor, fr
     return _shifts_from_spectra(S, t, reference_frame, pl)
 
 
-def warp_rigid_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want_sum=False, tables=None):
-    """``warp(..., rigid=True)`` of the conditioned movie without materialising it (mc_warp_rigid_raw)."""
+def warp_rigid_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want_sum=False, tables=None,
+                   out_sum=None, accumulate=False):
+    """``warp(..., rigid=True)`` of the conditioned movie without materialising it (mc_warp_rigid_raw).
+    `out_sum`: the (h, w) buffer the sum goes to (implies want_sum); with `accumulate` the sum is added to what it
+    holds (mc_warp_rigid_raw_accumulate) -- the hot-pixel corrections of these frames too."""
+    if accumulate and out_sum is None:
+        raise ValueError("accumulate needs out_sum")
     lib = _lib.load()
     t, h, w = rm.shape
     dev = rm.raw.device
     frames = torch.empty((t, h, w), dtype=torch.float32, device=dev) if want_frames else None
-    total = torch.empty((h, w), dtype=torch.float32, device=dev) if want_sum else None
+    total = out_sum if out_sum is not None else (torch.empty((h, w), dtype=torch.float32, device=dev)
+                                                 if want_sum else None)
+    entry = lib.mc_warp_rigid_raw_accumulate if accumulate else lib.mc_warp_rigid_raw
     if tables is None:
         shifts_px = (lattices[:, :, 0, 0] / pixel_spacing).contiguous()
         nbytes = C.c_int64(0)
@@ -1156,9 +1194,8 @@ def warp_rigid_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want
     else:
         shifts_px, scratch = tables
         phase = 2
-    run = lambda: check(lib.mc_warp_rigid_raw(ptr(rm.raw), rm.kind, ptr(rm.gain), ptr(rm.mu), t, h, w, ptr(shifts_px),
-                                              ptr(scratch), ptr(frames), ptr(total), phase, stream_ptr(dev)),
-                        "mc_warp_rigid_raw")
+    run = lambda: check(entry(ptr(rm.raw), rm.kind, ptr(rm.gain), ptr(rm.mu), t, h, w, ptr(shifts_px), ptr(scratch),
+                              ptr(frames), ptr(total), phase, stream_ptr(dev)), "mc_warp_rigid_raw")
     if RIGID_KERNEL_HOOK is not None and phase == 2:
         RIGID_KERNEL_HOOK(run)
     else:
@@ -1222,23 +1259,56 @@ def patch_field_raw(rm: RawMovie, pixel_spacing, reference_frame, reference_stra
                              outlier_rejection, outlier_threshold, spectra)
 
 
-def warp_field_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want_sum=False):
+def warp_field_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want_sum=False, out_sum=None,
+                   accumulate=False):
     """``warp(img, lattices, ...)`` (deformation-field lattices) of the conditioned movie without materialising it
-    (mc_warp_frames_raw).  Raises McorrUnsupported outside the raw kernel's shapes."""
+    (mc_warp_frames_raw).  Raises McorrUnsupported outside the raw kernel's shapes.  `out_sum` / `accumulate` as in
+    warp_rigid_raw (mc_warp_frames_raw_accumulate)."""
     _local_raw_check(rm)
+    if accumulate and out_sum is None:
+        raise ValueError("accumulate needs out_sum")
     lib = _lib.load()
     t, h, w = rm.shape
     dev = rm.raw.device
     _, _, GH, GW = lattices.shape
     frames = torch.empty((t, h, w), dtype=torch.float32, device=dev) if want_frames else None
-    total = torch.empty((h, w), dtype=torch.float32, device=dev) if want_sum else None
+    total = out_sum if out_sum is not None else (torch.empty((h, w), dtype=torch.float32, device=dev)
+                                                 if want_sum else None)
     nbytes = C.c_int64(0)
     check(lib.mc_warp_scratch_bytes(t, h, w, GH, GW, C.byref(nbytes)), "mc_warp_scratch_bytes")
     scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
-    check(lib.mc_warp_frames_raw(ptr(rm.raw), rm.kind, ptr(rm.gain), ptr(rm.mu), t, h, w, ptr(lattices.contiguous()),
-                                 GH, GW, float(pixel_spacing), ptr(scratch), ptr(frames), ptr(total), stream_ptr(dev)),
-          "mc_warp_frames_raw")
+    entry = lib.mc_warp_frames_raw_accumulate if accumulate else lib.mc_warp_frames_raw
+    check(entry(ptr(rm.raw), rm.kind, ptr(rm.gain), ptr(rm.mu), t, h, w, ptr(lattices.contiguous()), GH, GW,
+                float(pixel_spacing), ptr(scratch), ptr(frames), ptr(total), stream_ptr(dev)), "mc_warp_frames_raw")
     return frames, total
+
+
+def warp_dose_weighted_sum_raw(rm: RawMovie, lattices, pixel_spacing, rigid, dose_per_frame, pre_exposure, voltage,
+                               want_plain):
+    """warp_dose_weighted_sum of the conditioned movie straight from a RawMovie: each chunk of frames (the
+    WORKSPACE_BYTES rule of _dose_weighted_sum_row_major) is warped from the raw bytes of its frame window,
+    transformed and weighted, then dropped -- neither the conditioned nor the corrected fp32 movie is held.
+    `want_plain`: the plain sum too, from the same warp launches (the first chunk stores it, the others add to it:
+    ((s_0 + s_1) + s_2) + ... in chunk order).  Returns (dose-weighted sum, plain sum or None).  Raises
+    McorrUnsupported for shapes outside the row-major kernels, with POLYPHASE_FOURIER_SHIFT, and for whatever the
+    raw warps refuse."""
+    t, h, w = rm.shape
+    if POLYPHASE_FOURIER_SHIFT or not _full_row_major_ok(h, w):
+        raise _lib.McorrUnsupported(f"no streamed dose weighting from raw frames of {h} x {w}")
+    if not rigid:
+        _local_raw_check(rm)  # before anything is launched
+    plain = torch.empty((h, w), dtype=torch.float32, device=rm.raw.device) if want_plain else None
+
+    def frames_of(a, n):
+        win = rm.window(a, n)
+        kw = dict(want_frames=True, out_sum=plain, accumulate=want_plain and a > 0)
+        if rigid:
+            return warp_rigid_raw(win, lattices[a:a + n], pixel_spacing, **kw)[0]
+        return warp_field_raw(win, lattices[a:a + n], pixel_spacing, **kw)[0]
+
+    dw = _dose_weighted_sum_row_major(rm.raw, pixel_spacing, dose_per_frame, pre_exposure, voltage,
+                                      frames_of=frames_of, shape=(t, h, w))
+    return dw, plain
 
 
 _HOT_NONE = (1 << 63) - 1
