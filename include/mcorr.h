@@ -475,6 +475,41 @@ int mc_full_cols_dose_cm(const void* ST, int nframes, int frame0, int total_fram
                          float voltage, int first, int last, float scale, void* stream);
 int mc_full_rows_inverse(const void* S, float* out, const int64_t* out_off, int64_t out_stride,
                          const void* tw_row, int njobs, int H, int W, int pitch, void* stream);
+/* Fused Fourier-shift sums (correct_motion_fast -> sum / dose_weighted_sum without the shifted frames):
+ * the sums are linear, so sum_f irfft2(R_f X_f) = irfft2(sum_f R_f X_f), R_f = exp(-2 pi i (fy sy_f + fx sx_f)),
+ * and the exposure-weighted sum of the shifted frames is irfft2(sum_f q_f R_f X_f) / sqrt(sum_f q_f^2).
+ *   mc_full_rows_forward_raw  mc_full_rows_forward of raw frames: kind 0 u8 / 1 i16 (else MC_ERR_UNSUPPORTED),
+ *                             sample = raw * gain - mu[j] rounded as mc_condition_movie rounds it (a product,
+ *                             then a difference), so the spectra are bit for bit those of the conditioned
+ *                             frames; frame j at element job_off[j] of raw, rows W samples apart; gain (H,W)
+ *                             fp32, 8-byte aligned; raw 2- (u8) / 4-byte (i16) aligned.
+ *   mc_full_rows_hot_correct  S[f][y][kx] += (r - v) exp(-2 pi i kx x / W), kx = 0 .. W/2, for the hot pixels
+ *                             of an engine RawMovie's sorted list (keys = f H W + y W + x relative to the first
+ *                             frame of S, rv = {replacement r, value v}) with frame0 <= f < frame0 + njobs:
+ *                             after mc_full_rows_forward_raw the spectra are those of the movie with its hot
+ *                             pixels replaced.  kx x is reduced mod W in integers; one writer per bin, in list
+ *                             order (reproducible).
+ *   mc_full_cols_shift_sum    per frame j of the chunk: fft along y, * exp(-2 pi i (fy sy + fx sx)) with
+ *                             shifts[j] = (sy, sx) px (mc_full_cols_shift's angle), then accumulated over the
+ *                             frames: into P plainly, into A weighted by q_f (mc_full_cols_dose's filter),
+ *                             either or both (NULL: not accumulated; at least one).  first / last / scale as
+ *                             mc_full_cols_dose: on the last chunk A is scaled by scale / sqrt(sum_f q_f^2), P
+ *                             by scale, and both are transformed back along y (then mc_full_rows_inverse gives
+ *                             the sums).  The dose arguments are read only with A.  Both sums come from one
+ *                             read of the spectra for H = 4096; other heights take one launch per sum.
+ *   mc_full_cols_shift_sum_cm the same reading the column-major copy of mc_full_transpose (H = 4096, 4092,
+ *                             8184). */
+int mc_full_rows_forward_raw(const void* raw, int kind, const float* gain, const float* mu, const int64_t* job_off,
+                             void* S, const void* tw_row, int njobs, int H, int W, int pitch, void* stream);
+int mc_full_rows_hot_correct(const long long* keys, const float* rv, int64_t n, int frame0, int njobs, int H, int W,
+                             void* S, int pitch, void* stream);
+int mc_full_cols_shift_sum(const void* S, const float* shifts, int nframes, int frame0, int total_frames, void* A,
+                           void* P, const void* tw_col, int H, int W, int pitch, float pixel_size, float pre_exposure,
+                           float dose_per_frame, float voltage, int first, int last, float scale, void* stream);
+int mc_full_cols_shift_sum_cm(const void* ST, const float* shifts, int nframes, int frame0, int total_frames, void* A,
+                              void* P, const void* tw_col, int H, int W, int pitch, float pixel_size,
+                              float pre_exposure, float dose_per_frame, float voltage, int first, int last, float scale,
+                              void* stream);
 
 /* correct_motion_fast (correct_motion.py:430-498): K3 variant multiplying spectrum
  * idx[p] by exp(-2*pi*i*(fy*sy+fx*sx)), shifts[p]=(sy,sx) px, then inverse columns. */

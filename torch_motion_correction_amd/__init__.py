@@ -19,8 +19,11 @@ from .api import (  # noqa: F401
     get_pixel_shifts,
     image_shifts_to_deformation_field,
     motion_correct_raw,
+    motion_correct_raw_fast,
     motion_correct_raw_patches,
     motion_correct_sum,
+    motion_correct_sum_fast,
+    motion_correct_sum_fast_raw,
     motion_correct_sum_raw,
     resample_deformation_field,
 )
@@ -47,6 +50,9 @@ __all__ = [
     "motion_correct_raw",
     "motion_correct_raw_patches",
     "motion_correct_sum_raw",
+    "motion_correct_sum_fast",
+    "motion_correct_sum_fast_raw",
+    "motion_correct_raw_fast",
     "dose_weighted_sum",
     "condition_movie",
     "evaluate_deformation_field_at_t",

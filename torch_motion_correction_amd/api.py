@@ -688,6 +688,190 @@ def correct_motion_fast(image, deformation_grid, device=None):
     return out.to(out_dev)
 
 
+def _check_fast_field(deformation_grid, t):
+    """A rigid (2, t, 1, 1) field for the Fourier-shift sums; ValueError otherwise (before any device is touched).  A
+    field with more than one patch gets correct_motion_fast's own message."""
+    field = deformation_grid
+    if not isinstance(field, torch.Tensor) or field.dim() != 4 or field.shape[0] != 2 or min(field.shape) < 1:
+        raise ValueError(f"deformation_grid must be a (2, t, 1, 1) tensor, got {tuple(getattr(field, 'shape', ()))}")
+    if tuple(field.shape[-2:]) != (1, 1):
+        raise ValueError(
+            f"Expected single patch deformation field with shape (2, t, 1, 1), "
+            f"but got shape {field.shape}. "
+            f"Final two dimensions must be (1, 1) for single patch correction."
+        )
+    if field.shape[1] != t:
+        raise ValueError(f"deformation_grid has {field.shape[1]} time points, the movie {t} frames")
+
+
+def _check_fast_sum_args(dose_per_frame, return_plain_sum):
+    dose = _check_dose(dose_per_frame)
+    if return_plain_sum and dose is None:
+        raise ValueError("return_plain_sum needs dose_per_frame: without a dose the result is the plain sum")
+    return dose
+
+
+def _fast_sums(img, field, ps, dose, pre_exposure, voltage, want_plain):
+    """(dose-weighted sum or None, plain sum or None) of the fp32 stack `img` (on the device) shifted by the
+    Angstrom `field` (on the device): the fused sums, or -- where they raise McorrUnsupported -- exactly
+    correct_motion_fast(img, field / ps) followed by .sum(0) and dose_weighted_sum."""
+    g = field / ps
+    shifts = engine.fast_shifts(g)
+    try:
+        return engine.fast_shift_sums(img, shifts, ps, dose, pre_exposure, voltage, want_plain)
+    except McorrUnsupported:
+        cor = engine.fourier_shift(img, shifts)
+        dw = None if dose is None else engine.dose_weighted_sum(cor, ps, dose, float(pre_exposure), float(voltage))
+        plain = cor.sum(0) if (dose is None or want_plain) else None
+        return dw, plain
+
+
+def _fast_result(dw, plain, want_plain, out_dev):
+    if dw is None:
+        return plain.to(out_dev)
+    return (dw.to(out_dev), plain.to(out_dev)) if want_plain else dw.to(out_dev)
+
+
+def motion_correct_sum_fast(image, deformation_grid, pixel_spacing, dose_per_frame=None, pre_exposure=0.0,
+                            voltage=300.0, return_plain_sum=False, device=None):
+    """The whole-image route of the example's pipeline after the estimate (examples/ttMotion.py:242-262, 390-404):
+    ``correct_motion_fast`` (a Fourier phase ramp, no interpolation) followed by ``torch.sum`` and ``dose_weight``,
+    without the shifted movie.  `image`: an fp32 or fp16 (t, h, w) stack; `deformation_grid`: a rigid (2, t, 1, 1)
+    field in Angstrom, as for ``motion_correct_sum``.  With ``g = deformation_grid / float(pixel_spacing)`` (a torch
+    op on the device) the result is ``correct_motion_fast(image, g).sum(0)``, or with ``dose_per_frame`` (e/A^2;
+    with ``pre_exposure`` and ``voltage``) ``dose_weighted_sum(correct_motion_fast(image, g), pixel_spacing,
+    dose_per_frame, pre_exposure, voltage)``.  ``return_plain_sum`` (needs a dose) returns ``(dose-weighted sum,
+    plain sum)`` from the same pass.  The caller's grid is never modified.
+
+    The example passes its Angstrom field straight to ``correct_motion_fast``, which reads the values as pixels;
+    its literal result is ``motion_correct_sum_fast(img, field * ps, ps, ...)``.
+
+    Both sums are linear: each frame is transformed forward once, its phase ramp applied and the sums accumulated
+    in the forward column pass (engine.fast_shift_sums), then one inverse transform per sum -- no shifted frame
+    is stored.  Frame shapes outside the row-major transforms (engine._full_row_major_ok) take exactly the
+    composition above.  A field with more than one patch raises ValueError, as correct_motion_fast does."""
+    dose = _check_fast_sum_args(dose_per_frame, return_plain_sum)  # every argument rule before any device
+    if image.dim() != 3:
+        raise ValueError(f"image must be (t, h, w), got {tuple(image.shape)}")
+    _check_fast_field(deformation_grid, image.shape[0])
+    return _motion_correct_sum_fast(image, deformation_grid, pixel_spacing, dose, pre_exposure, voltage,
+                                    bool(return_plain_sum), device)
+
+
+@_on_gpu
+def _motion_correct_sum_fast(image, deformation_grid, pixel_spacing, dose, pre_exposure, voltage, want_plain, device):
+    out_dev = _out_device(image, device)
+    dev = require_gpu(out_dev)
+    dw, plain = _fast_sums(_stage(image, dev), deformation_grid.detach().to(dev), float(pixel_spacing), dose,
+                           pre_exposure, voltage, want_plain)
+    return _fast_result(dw, plain, want_plain, out_dev)
+
+
+def _check_raw_args(movie, gain):
+    if movie.dim() != 3:
+        raise ValueError(f"movie must be (t, h, w), got {tuple(movie.shape)}")
+    if gain is not None and tuple(gain.shape) != tuple(movie.shape[-2:]):
+        raise ValueError(f"gain reference has shape {tuple(gain.shape)}, frames are {tuple(movie.shape[-2:])}")
+
+
+def motion_correct_sum_fast_raw(movie, gain, deformation_grid, pixel_spacing, mean_zero=True, hot_pixel_threshold=None,
+                                dose_per_frame=None, pre_exposure=0.0, voltage=300.0, return_plain_sum=False,
+                                device=None):
+    """``motion_correct_sum_fast(condition_movie(movie, gain, mean_zero, hot_pixel_threshold), ...)`` for a RAW
+    uint8 / int16 movie, without the conditioned movie: the row transform reads the raw bytes and forms
+    ``raw * gain - frame mean`` as condition_movie rounds it, and the hot pixels (``hot_pixel_threshold``, the
+    example uses 10.0) enter the spectra as sparse corrections (engine.RawMovie).  Without hot pixels the sums are
+    bit for bit those of the conditioned route.  Returns the sum, or ``(dose-weighted sum, plain sum)`` with
+    ``return_plain_sum``.  fp16 / fp32 movies, frame shapes outside the row-major transforms and a hot-pixel list
+    overflow take exactly condition_movie followed by motion_correct_sum_fast."""
+    dose = _check_fast_sum_args(dose_per_frame, return_plain_sum)  # every argument rule before any device
+    thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)
+    _check_raw_args(movie, gain)
+    _check_fast_field(deformation_grid, movie.shape[0])
+    return _motion_correct_sum_fast_raw(movie, gain, deformation_grid, pixel_spacing, mean_zero, thr, dose,
+                                        pre_exposure, voltage, bool(return_plain_sum), device)
+
+
+@_on_gpu
+def _motion_correct_sum_fast_raw(movie, gain, deformation_grid, pixel_spacing, mean_zero, thr, dose, pre_exposure,
+                                 voltage, want_plain, device):
+    out_dev = _out_device(movie, device)
+    dev = require_gpu(out_dev)
+    raw = movie.detach().to(dev)
+    ps = float(pixel_spacing)
+    gd = None if gain is None else gain.to(dev)
+    field = deformation_grid.detach().to(dev)
+    res = None
+    if raw.dtype in (torch.uint8, torch.int16):
+        try:
+            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
+            res = engine.fast_shift_sums(rm, engine.fast_shifts(field / ps), ps, dose, pre_exposure, voltage,
+                                         want_plain)
+        except McorrUnsupported:
+            res = None
+    if res is None:  # exactly condition_movie, then motion_correct_sum_fast
+        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr)
+        res = _fast_sums(img, field, ps, dose, pre_exposure, voltage, want_plain)
+    return _fast_result(*res, want_plain, out_dev)
+
+
+def motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame=None, b_factor=500, frequency_range=(300, 10),
+                            mean_zero=True, hot_pixel_threshold=None, dose_per_frame=None, pre_exposure=0.0,
+                            voltage=300.0, return_plain_sum=False, return_hot_counts=False, device=None):
+    """The example's whole-image route for a RAW uint8 / int16 movie: condition_movie -> estimate_global_motion ->
+    correct_motion_fast -> sum / dose_weight (examples/ttMotion.py:90-121, 174-199, 242-262, 390-404), with one
+    engine.RawMovie for the estimate and the sums: no conditioned and no shifted fp32 movie.  Returns ``(field
+    (2,t,1,1) Angstrom, sum (h,w)[, plain sum][, hot counts (t,) int32])``; the field is bit for bit
+    ``motion_correct_raw``'s (the same estimator on the same RawMovie).  The sums are motion_correct_sum_fast's of
+    the conditioned movie with that field (``correct_motion_fast`` with the field in pixels -- note the example
+    itself passes the Angstrom field).  fp16 / fp32 movies, shapes without the fused kernels and a hot-pixel list
+    overflow take exactly condition_movie, estimate_global_motion and motion_correct_sum_fast."""
+    dose = _check_fast_sum_args(dose_per_frame, return_plain_sum)  # every argument rule before any device
+    thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)
+    _check_raw_args(movie, gain)
+    return _motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, mean_zero,
+                                    thr, dose, pre_exposure, voltage, bool(return_plain_sum), bool(return_hot_counts),
+                                    device)
+
+
+@_on_gpu
+def _motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, mean_zero, thr,
+                             dose, pre_exposure, voltage, want_plain, want_counts, device):
+    out_dev = _out_device(movie, device)
+    dev = require_gpu(out_dev)
+    raw = movie.detach().to(dev)
+    t = raw.shape[0]
+    ref = t // 2 if reference_frame is None else int(reference_frame)
+    ps = float(pixel_spacing)
+    gd = None if gain is None else gain.to(dev)
+    res = counts = None
+    if raw.dtype in (torch.uint8, torch.int16):
+        try:
+            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
+            shifts = engine.global_shifts_raw(rm, ref, ps, float(b_factor), tuple(frequency_range))
+            field = image_shifts_to_deformation_field(shifts, ps)  # as motion_correct_raw
+            res = engine.fast_shift_sums(rm, engine.fast_shifts(field / ps), ps, dose, pre_exposure, voltage,
+                                         want_plain)
+            counts = rm.hot_counts
+        except McorrUnsupported:
+            res = counts = None
+    if res is None:  # exactly condition_movie, estimate_global_motion, motion_correct_sum_fast
+        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr,
+                                     return_hot_counts=thr is not None)
+        if thr is not None:
+            img, counts = img
+        shifts = engine.global_shifts(img, ref, ps, float(b_factor), tuple(frequency_range))
+        field = image_shifts_to_deformation_field(shifts, ps)
+        res = _fast_sums(img, field, ps, dose, pre_exposure, voltage, want_plain)
+    dw, plain = res
+    out = [field.to(out_dev), (plain if dw is None else dw).to(out_dev)]
+    if want_plain:
+        out.append(plain.to(out_dev))
+    if want_counts:
+        out.append(torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None else counts.to(out_dev))
+    return tuple(out)
+
+
 @_on_gpu
 def get_pixel_shifts(frame, pixel_spacing, frame_deformation_grid, pixel_grid=None):
     """(h,w,2) per-pixel shifts in px from a (2,G_h,G_w) Angstrom lattice

@@ -1311,6 +1311,75 @@ def warp_dose_weighted_sum_raw(rm: RawMovie, lattices, pixel_spacing, rigid, dos
     return dw, plain
 
 
+def fast_shifts(grid_px):
+    """The (t, 2) fp32 shifts (sy, sx) the Fourier-shift routes apply for a rigid (2, t, 1, 1) field in pixels: the
+    field negated, as correct_motion_fast forms them (correct_motion.py:473-476).  One helper for the fused sums of
+    fp32 frames and of raw movies, so both routes use the same shift tensor."""
+    return (-grid_px.detach()[:, :, 0, 0].transpose(0, 1).to(torch.float32)).contiguous()
+
+
+def fast_shift_sums(src, shifts, pixel_spacing=1.0, dose_per_frame=None, pre_exposure=0.0, voltage=300.0,
+                    want_plain=False):
+    """fourier_shift(frames, shifts) followed by its plain sum and / or dose_weighted_sum, without the shifted
+    frames: both are linear, so each chunk of frames (the WORKSPACE_BYTES rule and column-major copy of
+    _dose_weighted_sum_row_major) is transformed forward once and the column pass multiplies each frame's
+    spectrum by its phase ramp and accumulates the plain and / or exposure-weighted sums (mc_full_cols_shift_sum);
+    one inverse transform per sum at the end.  `src`: an fp32 (t, h, w) tensor, or a RawMovie, whose chunks are
+    transformed from the raw bytes of their frame window (mc_full_rows_forward_raw, then the window's hot pixels,
+    mc_full_rows_hot_correct) -- the same launches on the same samples otherwise.  Returns (dose-weighted sum or
+    None, plain sum or None): the plain sum without a dose, or with `want_plain`.  Raises McorrUnsupported for
+    shapes outside the row-major kernels and with POLYPHASE_FOURIER_SHIFT, before any launch."""
+    raw = isinstance(src, RawMovie)
+    t, h, w = src.shape
+    if POLYPHASE_FOURIER_SHIFT or not _full_row_major_ok(h, w):
+        raise _lib.McorrUnsupported(f"no fused Fourier-shift sums for frames of {h} x {w}")
+    lib = _lib.load()
+    dev = src.raw.device if raw else src.device
+    with_dose = dose_per_frame is not None
+    want_plain = want_plain or not with_dose
+    pitch = lib.mc_full_spectrum_pitch(w)
+    tw_row, tw_col = planmod.get_twiddles(w, dev), planmod.get_twiddles(h, dev)
+    per_frame = h * pitch * 8
+    colmajor = DOSE_COLUMN_MAJOR and h in (4096, 4092)  # as _dose_weighted_sum_row_major
+    chunk = max(1, min(t, WORKSPACE_BYTES // ((2 if colmajor else 1) * per_frame)))
+    S = torch.empty((chunk, h, pitch, 2), dtype=torch.float32, device=dev)
+    ST = torch.empty((chunk, w // 2 + 1, h, 2), dtype=torch.float32, device=dev) if colmajor else None
+    sums = torch.empty((int(with_dose) + int(want_plain), h, pitch, 2), dtype=torch.float32, device=dev)
+    A = sums[0] if with_dose else None
+    P = sums[-1] if want_plain else None
+    shifts = shifts.to(dev, torch.float32).contiguous()
+    st = stream_ptr(dev)
+    for a in range(0, t, chunk):
+        n = min(chunk, t - a)
+        if raw:
+            win = src.window(a, n)
+            off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
+            check(lib.mc_full_rows_forward_raw(ptr(win.raw), win.kind, ptr(win.gain), ptr(win.mu), ptr(off), ptr(S),
+                                               ptr(tw_row), n, h, w, pitch, st), "mc_full_rows_forward_raw")
+            if win.n_hot:
+                check(lib.mc_full_rows_hot_correct(ptr(win.hot_keys), ptr(win.hot_rv), win.n_hot, 0, n, h, w, ptr(S),
+                                                   pitch, st), "mc_full_rows_hot_correct")
+        else:
+            off = torch.arange(a, a + n, device=dev, dtype=torch.int64) * (h * w)
+            check(lib.mc_full_rows_forward(ptr(src), ptr(off), w, ptr(S), ptr(tw_row), n, h, w, pitch, st),
+                  "mc_full_rows_forward")
+        sum_args = (ptr(shifts[a:a + n]), n, a, t, ptr(A), ptr(P), ptr(tw_col), h, w, pitch, float(pixel_spacing),
+                    float(pre_exposure), float(dose_per_frame) if with_dose else 0.0, float(voltage),
+                    1 if a == 0 else 0, 1 if a + n >= t else 0, 1.0 / (h * w), st)
+        if colmajor:
+            check(lib.mc_full_transpose(ptr(S), ptr(ST), n, h, w, pitch, st), "mc_full_transpose")
+            check(lib.mc_full_cols_shift_sum_cm(ptr(ST), *sum_args), "mc_full_cols_shift_sum_cm")
+        else:
+            check(lib.mc_full_cols_shift_sum(ptr(S), *sum_args), "mc_full_cols_shift_sum")
+    del S, ST
+    n = sums.shape[0]
+    out = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+    off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
+    check(lib.mc_full_rows_inverse(ptr(sums), ptr(out), ptr(off), w, ptr(tw_row), n, h, w, pitch, st),
+          "mc_full_rows_inverse")
+    return (out[0] if with_dose else None), (out[-1] if want_plain else None)
+
+
 _HOT_NONE = (1 << 63) - 1
 
 
