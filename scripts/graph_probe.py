@@ -9,8 +9,8 @@ for (t, n) in ((8, 512), (16, 1024), (40, 4096)):
     stack, dy, dx = bench.synth_stack(t, n, n, 3, dev)
     pipe = pipeline.MoviePipeline(dev, 1.0, return_frames=True, overlap=False)
     def step():
-        f = pipe._estimate(stack)
-        return f, pipe._correct(stack, f)
+        f, args = pipe._estimate(stack)
+        return f, pipe._correct(stack, args)
     for _ in range(3): out = step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()

@@ -13,8 +13,8 @@ def run(nstreams, n):
     out = None
     for i in range(n):
         with torch.cuda.stream(streams[i % nstreams]):
-            f = pipe._estimate(stack)
-            out = pipe._correct(stack, f)
+            f, args = pipe._estimate(stack)
+            out = pipe._correct(stack, args)
     for s in streams: torch.cuda.current_stream().wait_stream(s)
     return out
 for ns in (1, 2, 3, 4, 2, 3):

@@ -775,6 +775,19 @@ def test_movie_pipeline_equals_sequential_calls(mc, dev, overlap):
         mc.motion_correct_movies([movies[0][0]], 1.0)
 
 
+def test_global_shifts_after_k1_is_called_once(dev):
+    """The movie pipeline's K1 callback: called exactly once on the fused-statistics path, shifts unchanged."""
+    from torch_motion_correction_amd import engine
+
+    st = drift_stack(6, 512, 512, seed=7)[0].to(dev)
+    calls = []
+    got = engine.global_shifts(st, 3, 1.0, 500.0, (300, 10), after_k1=lambda: calls.append(1))
+    ref = engine.global_shifts(st, 3, 1.0, 500.0, (300, 10))
+    torch.cuda.synchronize()
+    assert calls == [1]
+    assert torch.equal(got, ref)
+
+
 # ------------------------------------------------------------------ near-window search + fallback
 
 

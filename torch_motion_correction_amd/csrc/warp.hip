@@ -756,7 +756,7 @@ __device__ __forceinline__ void rigid_strip_dma(const RigidArgs& a, const float4
 #ifndef RIGID_DMA_MINW
 #define RIGID_DMA_MINW 4
 #endif
-#if !defined(RIGID_DMA_VGPRS) || defined(MC_EXPERIMENTS)
+#ifndef RIGID_DMA_VGPRS
 #define RIGID_DMA_VGPR_ATTR
 #else
 #define RIGID_DMA_VGPR_ATTR __attribute__((amdgpu_num_vgpr(RIGID_DMA_VGPRS)))
@@ -939,291 +939,6 @@ RIGID_DMA_VGPR_ATTR void warp_rigid_dma(RigidArgs a) {
     }
   }
 }
-
-#ifdef MC_EXPERIMENTS
-// ------------------------------------------------------------------ rigid warp, loader wave + compute waves
-// EXPERIMENT (built only with -DMC_EXPERIMENTS, selected with MC_RIGID_LS=1; scripts/build_variant.sh).
-// Round 3.  In-kernel stamps of warp_rigid_dma (MC_RIGID_STAMP) showed where a frame step goes: 46 % of
-// a wave's cycles sit in the ISSUE of its LDS-DMA instructions (the vector-memory queue is full, the
-// wave cannot do anything else while it waits for a slot), 14 % in pure arithmetic, 13 % in store
-// back-pressure, the rest in waits and barriers -- and double-buffering inside those waves does not
-// help, because the "asynchronous" DMA blocks the issuing wave all the same.  Here the two jobs are
-// different waves of one workgroup per CU:
-//   * ONE loader wave issues every LDS-DMA of the workgroup, one unit ahead, from per-lane byte offsets
-//     it computed once (73 VGPRs: a loader has nothing else to keep) and a scalar base per unit, so an
-//     interior unit costs it no vector arithmetic at all; it sits in the back-pressured issue so that
-//     nobody else has to, and the CU's read path never runs dry;
-//   * 8 compute waves (2 x 4, 256 columns x 8 rows each) only read LDS, compute and store: reads and
-//     writes flow at the same time, which is what a copy needs to reach the chip's mixed ceiling
-//     (scripts/ubench/stream_copy.hip: 6.2 TB/s for a plain copy against 5.5-5.7 read-only).
-// A tile is 512 x 64 output pixels, processed per frame as two 32-row halves ("units") that alternate
-// between two LDS windows; the four rows the halves share are fetched twice by the same CU within
-// microseconds (an L2 hit), so the y-halo reaching the fabric is 68 / 64 instead of 36 / 32, and the
-// 512 tiles of a 4096^2 frame are exactly two per CU.  One barrier per unit: when it releases, unit
-// u + 1 has landed (the loader waited for its own DMAs) and unit u's window is free for unit u + 2.
-// The weight rows of a frame reach LDS the same way (loaded during the previous frame's second unit,
-// moved to registers at the start of the frame), so the compute waves issue no loads at all.
-// Requires w % 4 == 0 and 16-byte aligned frames (host checks; else warp_rigid_dma / warp_rigid).
-// MEASURED (40 x 4096^2, same box, non-temporal stores in both): bit-identical output; alone 1.039-1.051 ms
-// against 1.054-1.058 for warp_rigid_dma; one loader wave is NOT enough (1.28 ms: vmcnt allows 63 DMAs in
-// flight per wave), two give 1.11, four 1.13.  Stamps: the loader spends 80 % of a unit back-pressured in
-// issue, the compute waves idle half of the time -- the launch is bound by what the memory system gives
-// this access pattern (36 x 2 KB row pieces per window), not by anything a CU does.  Under the two-stream
-// pipeline it LOSES (step 1.78-1.81 against 1.74-1.76 ms): a 10-wave workgroup holding all 160 KB of LDS
-// leaves the estimator's column kernels (32 KB of LDS per workgroup) nowhere to run.  Not the default.
-#define RLS_WX 2
-#define RLS_WY 4
-#define RLS_NC (RLS_WX * RLS_WY)                 // compute waves
-#define RLS_TROWS (RLS_WY * RIGID_ROWS + 4)      // window rows per unit (36)
-#define RLS_Q (RLS_WX * RIGID_LANES + 1)         // float4 columns per window row (129)
-#define RLS_NQ (RLS_TROWS * RLS_Q)               // 4644
-#define RLS_CHUNKS ((RLS_NQ + 63) / 64)          // 73 DMA instructions per unit
-#define RLS_PADQ (RLS_CHUNKS * 64)
-#define RLS_TW (RLS_WX * RIGID_LANES * 4)        // 512
-#define RLS_TH (2 * RLS_WY * RIGID_ROWS)         // 64
-#define RLS_LDS_BYTES ((2 * RLS_PADQ + 5 * RLS_TW / 4) * 16 + RLS_TH * 5 * 4)
-
-template <bool WRITE_FRAMES, bool WRITE_SUM, int NLOAD>
-__global__ __launch_bounds__(RIGID_LANES*(RLS_NC + NLOAD), 3) void warp_rigid_ls(RigidArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_rd[];
-  float4* const buf0 = reinterpret_cast<float4*>(smem_rd);
-  float4* const buf1 = buf0 + RLS_PADQ;
-  float4* const wxs = buf1 + RLS_PADQ;                        // [5][128] quads: Wx[f][j][xt .. xt + 512)
-  float* const wys = reinterpret_cast<float*>(wxs + 5 * RLS_TW / 4);  // [64][5]: Wy[f][yt .. yt + 64)[5]
-  const int nt = a.tiles_x * a.tiles_y;
-  const int b = blockIdx.x;
-  int tile = b;
-  if ((nt & 7) == 0) tile = (b & 7) * (nt >> 3) + (b >> 3);  // one band of tile rows per XCD
-  const int tyi = tile / a.tiles_x, txi = tile - tyi * a.tiles_x;
-  const int h = a.h, w = a.w;
-  const int lane = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.y);
-  const int xt = txi * RLS_TW, yt = tyi * RLS_TH;
-  const int64_t hw = (int64_t)h * w;
-  const int nframes = a.nframes;
-
-  if (wave >= RLS_NC) {
-    // ---------------------------------------------------------------- loader wave(s): chunk i belongs to loader i % NLOAD
-    const int lw = wave - RLS_NC;
-    constexpr int MYCH = (RLS_CHUNKS + NLOAD - 1) / NLOAD;
-    unsigned off[MYCH];  // byte offset of this lane's quad of chunk i from the window's first sample
-#pragma unroll
-    for (int m = 0; m < MYCH; ++m) {
-      int q = (m * NLOAD + lw) * 64 + lane;
-      q = q < RLS_NQ ? q : RLS_NQ - 1;  // tail lanes re-load the last quad into the pad
-      const int tr = q / RLS_Q, qc = q - tr * RLS_Q;
-      off[m] = (unsigned)(tr * w + 4 * qc) * 4u;
-    }
-    auto load_unit = [&](int f, int hf, float4* dst) {
-      const float* fr = a.frames + (int64_t)f * hw;
-      const int Sy = a.S[2 * f], Sx = a.S[2 * f + 1];
-      const int ry = yt + hf * (RLS_TH / 2) + Sy - 1;  // image row of window row 0
-      const int ax = xt + Sx - 1;                       // image column of window column 0
-      const bool interior = ry >= 0 && ry + RLS_TROWS <= h && ax >= 0 && ax + 4 * RLS_Q <= w;
-      if (interior) {
-        const char* ub = reinterpret_cast<const char*>(fr + (int64_t)ry * w + ax);
-#pragma unroll
-        for (int m = 0; m < MYCH; ++m) {
-          const int i = m * NLOAD + lw;
-          if (i >= RLS_CHUNKS) break;
-          // the 32-bit offset is made opaque at the point of use: otherwise its zero-extension is
-          // hoisted out of the frame loop, the table becomes 146 registers and spills (and a reload
-          // in the middle of the DMA stream waits for vmcnt(0))
-          unsigned o = off[m];
-          asm volatile("" : "+v"(o));
-          __builtin_amdgcn_global_load_lds(reinterpret_cast<const float*>(ub + o), (lds_vptr)(dst + i * 64), 16, 0, 0);
-        }
-        return;
-      }
-      // edge unit: rows clipped to the image (border padding), quads kept whole inside the row; the
-      // quads that had to move are patched element by element below
-#pragma unroll 1
-      for (int i = lw; i < RLS_CHUNKS; i += NLOAD) {
-        int q = i * 64 + lane;
-        q = q < RLS_NQ ? q : RLS_NQ - 1;
-        const int tr = q / RLS_Q, qc = q - tr * RLS_Q;
-        int r = ry + tr;
-        r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
-        int c = ax + 4 * qc;
-        c = c < 0 ? 0 : (c > w - 4 ? w - 4 : c);
-        __builtin_amdgcn_global_load_lds(fr + (int64_t)r * w + c, (lds_vptr)(dst + i * 64), 16, 0, 0);
-      }
-      // columns outside the row: [0, nl) and [nr, RLS_Q) quads of every window row hold the wrong
-      // samples; re-fetch their elements at the clipped column (own DMAs: one wave, one vmcnt)
-      int nl = ax < 0 ? (-ax + 3) >> 2 : 0;
-      nl = nl > RLS_Q ? RLS_Q : nl;
-      int nr = w - 4 - ax >= 0 ? ((w - 4 - ax) >> 2) + 1 : 0;
-      nr = nr > RLS_Q ? RLS_Q : (nr < nl ? nl : nr);
-      const int nbad = nl + (RLS_Q - nr);
-      if (nbad == 0) return;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      float* t = reinterpret_cast<float*>(dst);
-      const int per_row = 4 * nbad, items = RLS_TROWS * per_row;
-      for (int it = lane; it < items; it += 64) {
-        const int tr = it / per_row, k = it - tr * per_row;
-        const int bq = k >> 2, e = k & 3;
-        const int qc = bq < nl ? bq : nr + (bq - nl);
-        if (NLOAD > 1 && ((tr * RLS_Q + qc) >> 6) % NLOAD != lw) continue;  // only quads this wave's DMAs wrote
-        int r = ry + tr;
-        r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
-        int c = ax + 4 * qc + e;
-        c = c < 0 ? 0 : (c > w - 1 ? w - 1 : c);
-        t[(tr * RLS_Q + qc) * 4 + e] = fr[(int64_t)r * w + c];
-      }
-    };
-    // weight rows: uniform base per (frame, tap) + a 32-bit lane offset (columns past the row end are
-    // clipped: their outputs are never stored)
-    unsigned wxo[RLS_WX], wyo[RLS_TH * 5 / 64];
-#pragma unroll
-    for (int i = 0; i < RLS_WX; ++i) {
-      int c = xt + 4 * (64 * i + lane);
-      c = c > w - 4 ? w - 4 : c;
-      wxo[i] = (unsigned)c * 4u;
-    }
-#pragma unroll
-    for (int i = 0; i < RLS_TH * 5 / 64; ++i) {
-      int idx = yt * 5 + i * 64 + lane;
-      idx = idx > h * 5 - 1 ? h * 5 - 1 : idx;
-      wyo[i] = (unsigned)idx * 4u;
-    }
-    auto load_weights = [&](int f) {
-#pragma unroll
-      for (int j = 0; j < 5; ++j) {
-        const char* base = reinterpret_cast<const char*>(a.Wx + ((int64_t)f * 5 + j) * w);
-#pragma unroll
-        for (int i = 0; i < RLS_WX; ++i) {
-          unsigned o = wxo[i];
-          asm volatile("" : "+v"(o));
-          __builtin_amdgcn_global_load_lds(reinterpret_cast<const float*>(base + o),
-                                           (lds_vptr)(wxs + j * (RLS_TW / 4) + i * 64), 16, 0, 0);
-        }
-      }
-      const char* base = reinterpret_cast<const char*>(a.Wy + (int64_t)f * 5 * h);
-#pragma unroll
-      for (int i = 0; i < RLS_TH * 5 / 64; ++i) {
-        unsigned o = wyo[i];
-        asm volatile("" : "+v"(o));
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const float*>(base + o), (lds_vptr)(wys + i * 64), 4, 0, 0);
-      }
-    };
-    load_unit(0, 0, buf0);
-    if (lw == NLOAD - 1) load_weights(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#ifdef MC_RIGID_STAMP
-    unsigned long long T0, T1, T2, T3, sli = 0, slw = 0, slb = 0;
-#endif
-    for (int f = 0; f < nframes; ++f) {
-      RSTAMP(T0);
-      load_unit(f, 1, buf1);  // under the first half of frame f
-      RSTAMP(T1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      RSTAMP(T2);
-      __syncthreads();
-      RSTAMP(T3);
-#ifdef MC_RIGID_STAMP
-      sli += T1 - T0; slw += T2 - T1; slb += T3 - T2;
-#endif
-      if (f + 1 < nframes) {  // under the second half: the next frame's first window and its weights
-        load_unit(f + 1, 0, buf0);
-        if (lw == NLOAD - 1) load_weights(f + 1);
-        RSTAMP(T1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        RSTAMP(T2);
-#ifdef MC_RIGID_STAMP
-        sli += T1 - T3; slw += T2 - T1;
-#endif
-      }
-      __syncthreads();
-#ifdef MC_RIGID_STAMP
-      RSTAMP(T3);
-      slb += T3 - T2;
-#endif
-    }
-#ifdef MC_RIGID_STAMP
-    if (lane == 0) {
-      atomicAdd(&g_rigid_stamps[2], sli); atomicAdd(&g_rigid_stamps[3], slw); atomicAdd(&g_rigid_stamps[4], slb);
-      atomicAdd(&g_rigid_stamps[6], 1ull);
-    }
-#endif
-    return;
-  }
-
-  // ------------------------------------------------------------------ compute waves
-  const int wvx = wave % RLS_WX, wvy = wave / RLS_WX;
-  const int x0 = xt + wvx * (RIGID_LANES * 4) + lane * 4;
-  float acc0[RIGID_ROWS][4], acc1[RIGID_ROWS][4];
-#pragma unroll
-  for (int r = 0; r < RIGID_ROWS; ++r)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc0[r][k] = acc1[r][k] = 0.f;
-  const int ya = yt + wvy * RIGID_ROWS, yb = ya + RLS_TH / 2;
-  const bool full_x = xt + RLS_TW <= w;
-  const bool full_a = full_x && yt + RLS_TH / 2 <= h, full_b = full_x && yt + RLS_TH <= h;
-  const int strip = (wvy * RIGID_ROWS) * RLS_Q + wvx * RIGID_LANES + lane;  // this lane's first quad
-  float wx[5][4];
-#ifdef MC_RIGID_STAMP
-  unsigned long long st_c = 0, st_b = 0;
-#endif
-  __syncthreads();  // first window and the first frame's weights have landed
-  for (int f = 0; f < nframes; ++f) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const float4 t = wxs[j * (RLS_TW / 4) + wvx * RIGID_LANES + lane];
-      wx[j][0] = t.x; wx[j][1] = t.y; wx[j][2] = t.z; wx[j][3] = t.w;
-    }
-    // both halves' row weights now: the loader overwrites them during the second half
-    float wya = 0.f, wyb = 0.f;
-    if (lane < 5 * RIGID_ROWS) {
-      wya = wys[(wvy * RIGID_ROWS) * 5 + lane];
-      wyb = wys[(RLS_TH / 2 + wvy * RIGID_ROWS) * 5 + lane];
-    }
-#ifdef MC_RIGID_STAMP
-    unsigned long long C0, C1, C2, C3, C4;
-#endif
-    RSTAMP(C0);
-    if (full_a) rigid_strip_dma<WRITE_FRAMES, WRITE_SUM, true, RLS_Q>(a, buf0 + strip, f, ya, x0, wya, wx, acc0);
-    else rigid_strip_dma<WRITE_FRAMES, WRITE_SUM, false, RLS_Q>(a, buf0 + strip, f, ya, x0, wya, wx, acc0);
-    RSTAMP(C1);
-    __syncthreads();
-    RSTAMP(C2);
-    if (full_b) rigid_strip_dma<WRITE_FRAMES, WRITE_SUM, true, RLS_Q>(a, buf1 + strip, f, yb, x0, wyb, wx, acc1);
-    else rigid_strip_dma<WRITE_FRAMES, WRITE_SUM, false, RLS_Q>(a, buf1 + strip, f, yb, x0, wyb, wx, acc1);
-    RSTAMP(C3);
-    __syncthreads();
-    RSTAMP(C4);
-#ifdef MC_RIGID_STAMP
-    st_c += (C1 - C0) + (C3 - C2); st_b += (C2 - C1) + (C4 - C3);
-#endif
-  }
-#ifdef MC_RIGID_STAMP
-  if (lane == 0) {
-    atomicAdd(&g_rigid_stamps[0], st_c); atomicAdd(&g_rigid_stamps[1], st_b); atomicAdd(&g_rigid_stamps[5], 1ull);
-  }
-#endif
-  if (WRITE_SUM && x0 < w) {
-    const bool al = (((uintptr_t)a.out_sum) & 15) == 0;  // w % 4 == 0 on this path
-#pragma unroll
-    for (int ro = 0; ro < RIGID_ROWS; ++ro) {
-      if (ya + ro < h) {
-        float* dst = a.out_sum + (int64_t)(ya + ro) * w + x0;
-        if (al) *reinterpret_cast<float4*>(dst) = make_float4(acc0[ro][0], acc0[ro][1], acc0[ro][2], acc0[ro][3]);
-        else
-#pragma unroll
-          for (int k = 0; k < 4; ++k) dst[k] = acc0[ro][k];
-      }
-      if (yb + ro < h) {
-        float* dst = a.out_sum + (int64_t)(yb + ro) * w + x0;
-        if (al) *reinterpret_cast<float4*>(dst) = make_float4(acc1[ro][0], acc1[ro][1], acc1[ro][2], acc1[ro][3]);
-        else
-#pragma unroll
-          for (int k = 0; k < 4; ++k) dst[k] = acc1[ro][k];
-      }
-    }
-  }
-}
-
-#endif  // MC_EXPERIMENTS
 
 // ------------------------------------------------------------------ rigid warp, LDS-DMA, fp16 frames
 // The same kernel for frames stored as fp16 (N2: fp16 storage read natively): the window goes
@@ -1887,228 +1602,9 @@ __device__ __forceinline__ float wave_max_f(float v) {
   return v;
 }
 
-#ifdef MC_EXPERIMENTS  // the first LDS-tile kernel (MC_WARP_FIELD=1): superseded by warp_field2 / warp_field3
-template <bool WRITE_FRAMES, bool WRITE_SUM, bool UNIT_PS>
-__global__ __launch_bounds__(RIGID_LANES* RIGID_WAVES, 2) void warp_field(FieldArgs fa) {
-  const WarpArgs& a = fa.w;
-  extern __shared__ __attribute__((aligned(16))) char smem_gw[];
-  float4* const tile4 = reinterpret_cast<float4*>(smem_gw);
-  float* const tile = reinterpret_cast<float*>(smem_gw);
-  __shared__ int s_ytap[RIGID_WAVES * RIGID_ROWS][4];
-  __shared__ float s_ycoef[RIGID_WAVES * RIGID_ROWS][4];
-  const int nt = a.tiles_x * a.tiles_y;
-  const int b = blockIdx.x;
-  int tl = b;
-  if ((nt & 7) == 0) tl = (b & 7) * (nt >> 3) + (b >> 3);
-  const int tyi = tl / a.tiles_x, txi = tl - tyi * a.tiles_x;
-  const int h = a.h, w = a.w;
-  const float fh = (float)h, fw = (float)w;
-  const int lane = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.y);
-  const int tid = wave * RIGID_LANES + lane;
-  const int xt = txi * (RIGID_LANES * 4);
-  const int yt = tyi * (RIGID_WAVES * RIGID_ROWS);
-  const int y0 = yt + wave * RIGID_ROWS;
-  const int64_t hw = (int64_t)h * w;
-  // frame-invariant per-row lattice taps of this tile
-  if (tid < RIGID_WAVES * RIGID_ROWS) {
-    const int y = yt + tid < h ? yt + tid : h - 1;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      s_ytap[tid][k] = a.ytap[4 * y + k];
-      s_ycoef[tid][k] = a.ycoef[4 * y + k];
-    }
-  }
-  // lattice footprint of the tile (frame-invariant): node rows [R0,R1], node columns [C0,C1]
-  int R0, R1, C0, C1;
-  {
-    int lo = 0x7fffffff, hi = -1;
-    if (lane < RIGID_WAVES * RIGID_ROWS) {
-      const int y = yt + lane < h ? yt + lane : h - 1;
-      for (int k = 0; k < 4; ++k) {
-        const int v = a.ytap[4 * y + k];
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-      }
-    }
-    R0 = wave_min_i(lo);
-    R1 = wave_max_i(hi);
-    lo = 0x7fffffff;
-    hi = -1;
-    for (int k = 0; k < 4; ++k) {
-      const int x = xt + lane + 64 * k;
-      const int xs = x < w ? x : w - 1;
-      for (int j = 0; j < 4; ++j) {
-        const int v = fa.xtap[4 * xs + j];
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-      }
-    }
-    C0 = wave_min_i(lo);
-    C1 = wave_max_i(hi);
-  }
-  // centre pixel of the tile (clipped to the image)
-  const int yc = (yt + 16 < h) ? yt + 16 : h - 1;
-  const int xc = (xt + 128 < w) ? xt + 128 : w - 1;
-  const int4 ytc = *reinterpret_cast<const int4*>(a.ytap + 4 * yc);
-  const float4 ycc = *reinterpret_cast<const float4*>(a.ycoef + 4 * yc);
-  float acc[RIGID_ROWS][4];
-#pragma unroll
-  for (int r = 0; r < RIGID_ROWS; ++r)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[r][k] = 0.f;
-  __syncthreads();
-
-  for (int f = 0; f < a.nframes; ++f) {
-    const float* fr = a.frames + (int64_t)f * hw;
-    const float* E = a.etab + (int64_t)f * 2 * a.GH * w;
-    const int64_t chs = (int64_t)a.GH * w;  // channel stride of E
-    // 0. regularity: range of the lattice nodes that can influence this tile
-    {
-      const float* L = fa.lattice + (int64_t)f * 2 * a.GH * fa.GW;
-      const int ncol = C1 - C0 + 1, nnode = (R1 - R0 + 1) * ncol;
-      float lo_y = 3.0e38f, hi_y = -3.0e38f, lo_x = 3.0e38f, hi_x = -3.0e38f;
-      for (int i = lane; i < nnode; i += RIGID_LANES) {
-        const int R = R0 + i / ncol, Cc = C0 + i % ncol;
-        const float vy = L[(int64_t)R * fa.GW + Cc], vx = L[(int64_t)(a.GH + R) * fa.GW + Cc];
-        lo_y = fminf(lo_y, vy); hi_y = fmaxf(hi_y, vy);
-        lo_x = fminf(lo_x, vx); hi_x = fmaxf(hi_x, vx);
-      }
-      const float ry = 0.5f * (wave_max_f(hi_y) - wave_min_f(lo_y)) / a.pixel_spacing;
-      const float rx = 0.5f * (wave_max_f(hi_x) - wave_min_f(lo_x)) / a.pixel_spacing;
-      // |shift - shift_centre| <= 3.8*rho; taps span [-1,+2] around floor(); coordinate
-      // rounding adds < 0.01 px.  NaNs fail the comparison and go to the slow kernel.
-      const bool regular = (3.8f * ry + 1.05f <= (float)GW_MG) && (3.8f * rx + 1.05f <= (float)GW_MG);
-      if (!regular) {  // workgroup-uniform: every wave computed the same numbers
-        if (tid == 0) fa.flags[(int64_t)f * nt + tl] = 1;
-        continue;
-      }
-    }
-    // 1. window origin from the shift at the tile centre (identical in every lane)
-    int wy0, ax;
-    {
-      const float* Ec = E + xc;
-      float sy = dot4(ycc, Ec[(int64_t)ytc.x * w], Ec[(int64_t)ytc.y * w], Ec[(int64_t)ytc.z * w],
-                      Ec[(int64_t)ytc.w * w]);
-      float sx = dot4(ycc, Ec[chs + (int64_t)ytc.x * w], Ec[chs + (int64_t)ytc.y * w],
-                      Ec[chs + (int64_t)ytc.z * w], Ec[chs + (int64_t)ytc.w * w]);
-      if (!UNIT_PS) {
-        sy = div_invariant(sy, a.pixel_spacing);
-        sx = div_invariant(sx, a.pixel_spacing);
-      }
-      const float lim = 4.f * (fh + fw);
-      const float dy = fminf(fmaxf(floorf(grid_chain((float)yc + sy, fh)) - (float)yc, -lim), lim);
-      const float dx = fminf(fmaxf(floorf(grid_chain((float)xc + sx, fw)) - (float)xc, -lim), lim);
-      wy0 = __builtin_amdgcn_readfirstlane(yt + (int)dy - 1 - GW_MG);
-      ax = __builtin_amdgcn_readfirstlane((xt + (int)dx - 1 - GW_MG) & ~3);
-    }
-    // 2. window -> LDS (the previous frame's reads are behind the barrier at the loop's end)
-    for (int i = wave; i < GW_QUADS_PAD / 64; i += RIGID_WAVES) {
-      int q = i * 64 + lane;
-      q = q < GW_NQ ? q : GW_NQ - 1;
-      const int tr = q / GW_QUADS, qc = q - tr * GW_QUADS;
-      int r = wy0 + tr;
-      r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
-      int c = ax + 4 * qc;
-      c = c < 0 ? 0 : (c > w - 4 ? w - 4 : c);
-      __builtin_amdgcn_global_load_lds(fr + (int64_t)r * w + c, (lds_vptr)(tile4 + i * 64), 16, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (ax < 0 || ax + GW_STRIDE > w) {  // border padding: clipped columns (edge tiles only)
-      for (int i = tid; i < GW_ROWS * GW_STRIDE; i += RIGID_LANES * RIGID_WAVES) {
-        const int tr = i / GW_STRIDE, e = i - tr * GW_STRIDE;
-        const int c = ax + e;
-        if (c < 0 || c > w - 1) {
-          const int cc = c < 0 ? 0 : w - 1;
-          int qsrc = (cc & ~3) - ax;
-          qsrc = qsrc < 0 ? 0 : (qsrc > GW_STRIDE - 4 ? GW_STRIDE - 4 : qsrc);
-          tile[tr * GW_STRIDE + e] = tile[tr * GW_STRIDE + qsrc + (cc & 3)];
-        }
-      }
-      __syncthreads();
-    }
-    // 3. pixels
-    int4 ycache = make_int4(-1, -1, -1, -1);
-    float ey[4][4], ex[4][4];  // [lattice tap][pixel k]
-#pragma unroll
-    for (int r = 0; r < RIGID_ROWS; ++r) {
-      const int y = y0 + r;
-      if (y >= h) break;
-      const int row = wave * RIGID_ROWS + r;
-      const int4 yt4 = make_int4(s_ytap[row][0], s_ytap[row][1], s_ytap[row][2], s_ytap[row][3]);
-      const float4 yc4 = make_float4(s_ycoef[row][0], s_ycoef[row][1], s_ycoef[row][2], s_ycoef[row][3]);
-      if (yt4.x != ycache.x || yt4.y != ycache.y || yt4.z != ycache.z || yt4.w != ycache.w) {
-        ycache = yt4;  // wave-uniform: depends on y only
-        const int rows4[4] = {yt4.x, yt4.y, yt4.z, yt4.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int x = xt + lane + 64 * k;
-            const int xs = x < w ? x : w - 1;
-            ey[i][k] = E[(int64_t)rows4[i] * w + xs];
-            ex[i][k] = E[chs + (int64_t)rows4[i] * w + xs];
-          }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        // one pixel at a time: without this the scheduler interleaves all 32 unrolled
-        // pixel bodies and the kernel spills
-        __builtin_amdgcn_sched_barrier(0);
-        const int x = xt + lane + 64 * k;
-        if (x >= w) continue;
-        float sy = dot4(yc4, ey[0][k], ey[1][k], ey[2][k], ey[3][k]);
-        float sx = dot4(yc4, ex[0][k], ex[1][k], ex[2][k], ex[3][k]);
-        if (!UNIT_PS) {
-          sy = div_invariant(sy, a.pixel_spacing);
-          sx = div_invariant(sx, a.pixel_spacing);
-        }
-        const float cy = (float)y + sy, cx = (float)x + sx;
-        const bool inside = (cy >= 0.f) && (cy <= fh - 1.f) && (cx >= 0.f) && (cx <= fw - 1.f);
-        const float uy = grid_chain(cy, fh), ux = grid_chain(cx, fw);
-        const float fy = floorf(uy), fx = floorf(ux);
-        float wy[4], wx[4];
-        cubic_coeffs_fast(uy - fy, wy);
-        cubic_coeffs_fast(ux - fx, wx);
-        // in range by the regularity test; the clamp only keeps a NaN/garbage coordinate
-        // from reading outside the LDS tile
-        int ly = (int)fy - 1 - wy0, lx = (int)fx - 1 - ax;
-        ly = ly < 0 ? 0 : (ly > GW_ROWS - 4 ? GW_ROWS - 4 : ly);
-        lx = lx < 0 ? 0 : (lx > GW_STRIDE - 4 ? GW_STRIDE - 4 : lx);
-        const float* t0 = tile + ly * GW_STRIDE + lx;
-        float rowv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float* t = t0 + i * GW_STRIDE;
-          rowv[i] = gw_dot4(wx, t[0], t[1], t[2], t[3]);
-        }
-        float o = gw_dot4(wy, rowv[0], rowv[1], rowv[2], rowv[3]);
-        o = inside ? o : 0.f;
-        if (WRITE_FRAMES) a.out_frames[(int64_t)f * hw + (int64_t)y * w + x] = o;
-        if (WRITE_SUM) acc[r][k] += o;
-      }
-    }
-    __syncthreads();  // everyone is done with the tile before the next frame overwrites it
-  }
-  if (WRITE_SUM) {
-#pragma unroll
-    for (int r = 0; r < RIGID_ROWS; ++r) {
-      const int y = y0 + r;
-      if (y >= h) break;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int x = xt + lane + 64 * k;
-        if (x < w) a.out_sum[(int64_t)y * w + x] = acc[r][k];  // warp_field_slow adds its tile-frames afterwards
-      }
-    }
-  }
-}
-#endif  // MC_EXPERIMENTS
-
 // ------------------------------------------------------------------ general warp, second version
-// Same tiling, window DMA and per-pixel chain as warp_field, rebuilt around what limits it -- VALU
-// issue and the number of window bytes:
+// Same tiling, window DMA and per-pixel chain as the first LDS-tile kernel (warp_field, since removed),
+// rebuilt around what limits it -- VALU issue and the number of window bytes:
 //  * the window margin follows the field: mg = ceil(3.8 rho + 1.05) per axis and tile-frame (2 for
 //    the smooth fields of real movies) instead of the fixed 6, lanes outside the needed window
 //    issue no DMA (window bytes 1.6x -> 1.3x of the tile);
@@ -2900,7 +2396,7 @@ __global__ __launch_bounds__(RIGID_LANES* GW3_WAVES, 4) void warp_field3(FieldAr
   }
 }
 
-// Tile-frames warp_field flagged as irregular: generic per-pixel gathers from global
+// Tile-frames warp_field2 / warp_field3 flagged as irregular: generic per-pixel gathers from global
 // memory (border padding by clipping every tap coordinate).  One workgroup per tile, so
 // the += on out_sum cannot race.
 // RAW (N2): u8 / i16 frames, every tap conditioned as raw * gain - mu[f] at its clamped pixel (the zero
@@ -3170,16 +2666,12 @@ int mc_warp_frames_t(const void* frames_any, int storage, int nframes, int h, in
     hipError_t e = hipMemsetAsync(fa.flags, 0, (size_t)field_flag_bytes(nframes, h, w), s);
     if (e != hipSuccess) return (int)e;
     dim3 grid(a.tiles_x * a.tiles_y), block(RIGID_LANES, RIGID_WAVES);
-    const size_t lds = (size_t)GW_QUADS_PAD * 16;
-    int field_version = 3;  // 3: warp_field3; dense lattices fall back to warp_field2
-#ifdef MC_EXPERIMENTS
-    if (const char* v = getenv("MC_WARP_FIELD")) field_version = atoi(v);  // 1: the first LDS-tile kernel
-#endif
-    // version 3 stages <= GW3_EROWS lattice rows per tile: 32 pixel rows must span <= 1.5 lattice
-    // cells (always for the reference's 10 nodes per patch; not for a per-pixel lattice)
+    // warp_field3 stages <= GW3_EROWS lattice rows per tile: 32 pixel rows must span <= 1.5 lattice
+    // cells (always for the reference's 10 nodes per patch; not for a per-pixel lattice); dense
+    // lattices fall back to warp_field2
     // (warp_field3 addresses a frame with 32-bit element offsets built by 24-bit multiplies)
     const bool small32 = h < (1 << 24) && w < (1 << 24) && (int64_t)h * w < ((int64_t)1 << 31);
-    if ((field_version == 3 || half) && small32 && (int64_t)32 * (GH - 1) * 2 <= (int64_t)3 * (h - 1)) {
+    if (small32 && (int64_t)32 * (GH - 1) * 2 <= (int64_t)3 * (h - 1)) {
       int4* plan = reinterpret_cast<int4*>(fa.flags + field_flag_bytes(nframes, h, w));
       hipLaunchKernelGGL(warp_field_plan, dim3(a.tiles_x * a.tiles_y, nframes), dim3(64), 0, s, fa, unit ? 1 : 0,
                          half ? 1 : 0, plan);
@@ -3213,24 +2705,12 @@ int mc_warp_frames_t(const void* frames_any, int storage, int nframes, int h, in
       return mc_check_launch();
     }
     if (half) return MC_ERR_UNSUPPORTED;
-#ifdef MC_EXPERIMENTS
-#define MC_GW_LAUNCH(F, S)                                                                  \
-  do {                                                                                      \
-    if (field_version == 1) {  /* (version 3 falls back to 2 for dense lattices) */          \
-      if (unit) hipLaunchKernelGGL((warp_field<F, S, true>), grid, block, lds, s, fa);      \
-      else hipLaunchKernelGGL((warp_field<F, S, false>), grid, block, lds, s, fa);          \
-    } else {                                                                                \
-      if (unit) hipLaunchKernelGGL((warp_field2<F, S, true>), grid, block, lds, s, fa);     \
-      else hipLaunchKernelGGL((warp_field2<F, S, false>), grid, block, lds, s, fa);         \
-    }                                                                                       \
-  } while (0)
-#else
+    const size_t lds = (size_t)GW_QUADS_PAD * 16;
 #define MC_GW_LAUNCH(F, S)                                                                  \
   do {                                                                                      \
     if (unit) hipLaunchKernelGGL((warp_field2<F, S, true>), grid, block, lds, s, fa);       \
     else hipLaunchKernelGGL((warp_field2<F, S, false>), grid, block, lds, s, fa);           \
   } while (0)
-#endif
     if (out_frames && out_sum) MC_GW_LAUNCH(true, true);
     else if (out_frames) MC_GW_LAUNCH(true, false);
     else MC_GW_LAUNCH(false, true);
@@ -3429,19 +2909,11 @@ static int warp_rigid_impl(const void* frames_any, int storage, int nframes, int
   RigidArgs a;
   a.frames = frames; a.nframes = nframes; a.h = h; a.w = w; a.S = S; a.Wy = Wy; a.Wx = Wx;
   a.out_frames = out_frames; a.out_sum = out_sum;
-  // 512 x 32 tiles, single-buffered, 2 workgroups of 8 waves per CU.  Other tile shapes and the
-  // double-buffered form exist in -DMC_EXPERIMENTS builds only (MC_RIGID_GEOM = "WXWY" as two digits,
-  // MC_RIGID_NBUF, MC_RIGID_DMA=0; measured in DESIGN.md section 4: none is faster)
-  int use_dma = 1, geom = 24, nbuf = 1;
-#ifdef MC_EXPERIMENTS
-  if (const char* v = getenv("MC_RIGID_DMA")) use_dma = atoi(v);
-  if (const char* v = getenv("MC_RIGID_GEOM")) geom = atoi(v);
-  if (const char* v = getenv("MC_RIGID_NBUF")) nbuf = atoi(v);
-#endif
-  (void)nbuf;
-  const bool dma_ok = use_dma && (w % 4 == 0) && ((((uintptr_t)frames) & 15) == 0) &&
+  // 512 x 32 tiles, single-buffered, 2 workgroups of 8 waves per CU (other tile shapes and the
+  // double-buffered form were measured in DESIGN.md section 4: none is faster)
+  const bool dma_ok = (w % 4 == 0) && ((((uintptr_t)frames) & 15) == 0) &&
                       (!out_frames || ((((uintptr_t)out_frames) & 15) == 0));
-  const int WX = dma_ok ? geom / 10 : 1, WY = dma_ok ? geom % 10 : RIGID_WAVES;
+  const int WX = dma_ok ? 2 : 1, WY = dma_ok ? 4 : RIGID_WAVES;
   a.tiles_x = (w + RIGID_LANES * 4 * WX - 1) / (RIGID_LANES * 4 * WX);
   a.tiles_y = (h + WY * RIGID_ROWS - 1) / (WY * RIGID_ROWS);
   // Without the fused sum every frame is its own block: blocks are dispatched frame-major, so the
@@ -3471,92 +2943,15 @@ static int warp_rigid_impl(const void* frames_any, int storage, int nframes, int
 #undef MC_RDH_GO
     return mc_check_launch();
   }
-#ifdef MC_EXPERIMENTS
-  static int use_ls = -1;
-  if (use_ls < 0) {
-    const char* v = getenv("MC_RIGID_LS");
-    use_ls = v ? atoi(v) : 0;
-  }
-  if (dma_ok && use_ls && out_sum && (out_frames || use_ls > 1)) {
-    // fused sum: one loader wave + 8 compute waves per 512 x 64 tile (warp_rigid_ls)
-    a.tiles_x = (w + RLS_TW - 1) / RLS_TW;
-    a.tiles_y = (h + RLS_TH - 1) / RLS_TH;
-    a.frames_in_grid = 0;
-    static int nload = -1;
-    if (nload < 0) {
-      const char* v = getenv("MC_RIGID_NLOAD");
-      nload = v ? atoi(v) : 2;  // one wave's 63 outstanding DMAs (vmcnt) are not enough: 1.28 / 1.11 / 1.13 ms at 1 / 2 / 4
-    }
-    const dim3 gl(a.tiles_x * a.tiles_y), bl(RIGID_LANES, RLS_NC + nload);
-#ifdef MC_RIGID_STAMP
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rigid_stamps), z, sizeof z);
-#endif
-#define MC_RLS_GO(F, NL)                                                                                      \
-  do {                                                                                                        \
-    auto k = warp_rigid_ls<F, true, NL>;                                                                       \
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, RLS_LDS_BYTES);      \
-    hipLaunchKernelGGL(k, gl, bl, RLS_LDS_BYTES, s, a);                                                       \
-  } while (0)
-    if (out_frames) {
-      if (nload == 1) MC_RLS_GO(true, 1);
-      else if (nload == 2) MC_RLS_GO(true, 2);
-      else MC_RLS_GO(true, 4);
-    } else {
-      if (nload == 1) MC_RLS_GO(false, 1);
-      else if (nload == 2) MC_RLS_GO(false, 2);
-      else MC_RLS_GO(false, 4);
-    }
-#undef MC_RLS_GO
-#ifdef MC_RIGID_STAMP
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(z, HIP_SYMBOL(g_rigid_stamps), sizeof z);
-    if (z[5] && z[6]) {
-      const double dc = (double)z[5] * nframes * 2, dl = (double)z[6] * nframes * 2;
-      fprintf(stderr, "rigid_ls stamps (cycles per wave and UNIT): compute+stores %.0f  compute-barrier %.0f | loader: issue %.0f  vmcnt-wait %.0f  barrier %.0f\n",
-              z[0] / dc, z[1] / dc, z[2] / dl, z[3] / dl, z[4] / dl);
-    }
-#endif
-    return mc_check_launch();
-  }
-#endif  // MC_EXPERIMENTS
   if (dma_ok) {
-#define MC_RD_GO(F, S, NB, GX, GY)                                                                  \
-  do {                                                                                              \
-    auto k = warp_rigid_dma<F, S, NB, GX, GY>;                                                       \
-    const size_t lds = (size_t)NB * ((((GY * RIGID_ROWS + 4) * (GX * RIGID_LANES + 4)) + 63) / 64) * 64 * 16; \
+    // one 512 x 32 tile's window: (4 RIGID_ROWS + 4) rows of (2 RIGID_LANES + 4) float4, whole wave-units
+    constexpr size_t lds = (size_t)((((4 * RIGID_ROWS + 4) * (2 * RIGID_LANES + 4)) + 63) / 64) * 64 * 16;
+#define MC_RD_LAUNCH(F, S)                                                                         \
+  do {                                                                                             \
+    auto k = warp_rigid_dma<F, S, 1, 2, 4>;                                                        \
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, grid, block, lds, s, a);                                                  \
+    hipLaunchKernelGGL(k, grid, block, lds, s, a);                                                 \
   } while (0)
-#ifdef MC_EXPERIMENTS
-#define MC_RD_GEOM(F, S, NB)                                   \
-  do {                                                         \
-    if (geom == 14) MC_RD_GO(F, S, NB, 1, 4);                  \
-    else if (geom == 22) MC_RD_GO(F, S, NB, 2, 2);             \
-    else if (geom == 24) MC_RD_GO(F, S, NB, 2, 4);             \
-    else if (geom == 23) MC_RD_GO(F, S, NB, 2, 3);             \
-    else if (geom == 43) MC_RD_GO(F, S, NB, 4, 3);             \
-    else if (geom == 41) MC_RD_GO(F, S, NB, 4, 1);             \
-    else if (geom == 42) MC_RD_GO(F, S, NB, 4, 2);             \
-    else if (geom == 18) MC_RD_GO(F, S, NB, 1, 8);             \
-    else if (geom == 16) MC_RD_GO(F, S, NB, 1, 6);             \
-    else if (geom == 12) MC_RD_GO(F, S, NB, 1, 2);             \
-    else if (geom == 28) MC_RD_GO(F, S, NB, 2, 8);             \
-    else if (geom == 26) MC_RD_GO(F, S, NB, 2, 6);             \
-    else return MC_ERR_UNSUPPORTED;                                   \
-  } while (0)
-#else
-#define MC_RD_GEOM(F, S, NB) MC_RD_GO(F, S, NB, 2, 4)  /* 512 x 32 tiles, 2 workgroups of 8 waves per CU */
-#endif
-#ifdef MC_EXPERIMENTS
-#define MC_RD_LAUNCH(F, S)                                     \
-  do {                                                         \
-    if (nbuf == 1) MC_RD_GEOM(F, S, 1);                        \
-    else MC_RD_GEOM(F, S, 2);                                  \
-  } while (0)
-#else
-#define MC_RD_LAUNCH(F, S) MC_RD_GEOM(F, S, 1)
-#endif
 #ifdef MC_RIGID_STAMP
     unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rigid_stamps), z, sizeof z);
@@ -3574,8 +2969,6 @@ static int warp_rigid_impl(const void* frames_any, int storage, int nframes, int
     }
 #endif
 #undef MC_RD_LAUNCH
-#undef MC_RD_GEOM
-#undef MC_RD_GO
     return mc_check_launch();
   }
   if (out_frames && out_sum) hipLaunchKernelGGL((warp_rigid<true, true>), grid, block, 0, s, a);

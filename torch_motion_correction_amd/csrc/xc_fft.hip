@@ -1804,12 +1804,6 @@ static size_t rows_lds_bytes(int N, const XcGeom& g) {
 
 extern "C" {
 
-static void* g_after_k3n_event = nullptr;
-int mc_xc_after_k3n_event(void* event) {
-  g_after_k3n_event = event;
-  return MC_OK;
-}
-
 int mc_xc_col_engine(int mode) {
   if (mode < 0 || mode > 1) return MC_ERR_ARG;
   g_col_engine = mode;
@@ -2290,7 +2284,6 @@ int mc_xc_correlate_argmax(const void* S_cur, const int* cur_idx, const void* S_
   });
   rc = mc_check_launch();
   if (rc) return rc;
-  if (g_after_k3n_event) (void)hipEventRecord((hipEvent_t)g_after_k3n_event, st);  // pipeline schedules (mc_xc_after_k3n_event)
   const int nfar = ngrp - 2 * near;
   MC_DISPATCH_LOG(logn, {
     auto k = xc_rows_inv<L, 0>;

@@ -232,10 +232,12 @@ def mask_spectrum(pl, dev):
     return pl.mhat
 
 
-def _global_spectra(img, pl, split=False):
+def _global_spectra(img, pl, after_k1=None):
     """Filtered pruned spectra of all frames, (t, nkx, nky, 2), with normalize_image's
     statistics gathered inside K1 whenever the central box lies in the region K1 reads
-    (always for near-square frames); otherwise a separate statistics pass."""
+    (always for near-square frames); otherwise a separate statistics pass.  `after_k1()`, if
+    given, is called right after K1 has been enqueued on the fused path (the movie pipeline
+    records an event there); the other path never calls it."""
     lib = _lib.load()
     t, h, w = img.shape
     dev, g = img.device, pl.geom
@@ -274,15 +276,11 @@ def _global_spectra(img, pl, split=False):
         if img.dtype == torch.float32:
             raise
         del T1, S
-        return _global_spectra(img.float(), pl, split)
-    if AFTER_K1_HOOK is not None and not HOOK_AFTER_K2:
-        AFTER_K1_HOOK()
-    if split:  # the caller enqueues the column pass itself, possibly on another stream (global_stage_b)
-        return ("k2_pending", T1, S, fix, mhat)
+        return _global_spectra(img.float(), pl, after_k1)
+    if after_k1 is not None:
+        after_k1()
     check(lib.mc_xc_cols_forward_fix(ptr(T1), ptr(pl.filt), ptr(S), ptr(pl.tw_col), t, g, ptr(fix),
                                      ptr(mhat), st), "mc_xc_cols_forward_fix")
-    if AFTER_K1_HOOK is not None and HOOK_AFTER_K2:
-        AFTER_K1_HOOK()
     return S
 
 
@@ -311,44 +309,17 @@ def _box_chords(pl, hl, hu, wl, wu):
 USE_ROW_CHORDS = _os_env_flag("MC_ROW_CHORDS", True)
 
 
-def global_shifts(img, reference_frame, pixel_spacing, b_factor, frequency_range):
+def global_shifts(img, reference_frame, pixel_spacing, b_factor, frequency_range, after_k1=None):
     """Integer-pixel (t,2) shifts of every frame against `reference_frame`
     (estimate_motion_xc.py:57-123); the reference frame's row is exactly zero.
     `reference_frame` follows the reference's Python indexing (xc.py:101,107): a negative value
     selects from the end but never equals a loop index, so that frame is NOT skipped (it is
-    correlated with itself); anything outside [-t, t) raises IndexError."""
+    correlated with itself); anything outside [-t, t) raises IndexError.  `after_k1`: see
+    ``_global_spectra``."""
     t, h, w = img.shape
     dev = img.device
     pl = planmod.get_xc_plan(h, w, pixel_spacing, b_factor, frequency_range, dev)
-    S = _global_spectra(img, pl)
-    return _shifts_from_spectra(S, t, reference_frame, pl)
-
-
-def global_stage_a(img, pixel_spacing, b_factor, frequency_range):
-    """First stage of global_shifts for the three-stage movie pipeline: the plan and K1 (the HBM-bound row
-    pass over the frames) on the current stream.  Returns an opaque state for ``global_stage_b``; its
-    tensors must be made known to the stream stage b runs on (``stage_tensors``)."""
-    t, h, w = img.shape
-    pl = planmod.get_xc_plan(h, w, pixel_spacing, b_factor, frequency_range, img.device)
-    return (t, pl, _global_spectra(img, pl, split=True))
-
-
-def stage_tensors(state):
-    r = state[2]
-    return [x for x in (r[1:] if isinstance(r, tuple) else (r,)) if isinstance(x, torch.Tensor)]
-
-
-def global_stage_b(state, reference_frame):
-    """Second stage: the column pass (when stage a left it pending), K3, K4 -> (t, 2) shifts, on the current stream."""
-    lib = _lib.load()
-    t, pl, r = state
-    if isinstance(r, tuple):
-        _, T1, S, fix, mhat = r
-        g = pl.geom
-        check(lib.mc_xc_cols_forward_fix(ptr(T1), ptr(pl.filt), ptr(S), ptr(pl.tw_col), t, g, ptr(fix),
-                                         ptr(mhat), stream_ptr(S.device)), "mc_xc_cols_forward_fix")
-    else:
-        S = r
+    S = _global_spectra(img, pl, after_k1)
     return _shifts_from_spectra(S, t, reference_frame, pl)
 
 
@@ -544,8 +515,6 @@ def frame_lattices(field, t, grid_type):
 
 
 RIGID_KERNEL_HOOK = None  # callable(fn) -> calls fn(); set by bench.py to time warp_rigid_dma alone
-HOOK_AFTER_K2 = False
-AFTER_K1_HOOK = None  # callable() invoked right after the global estimate's K1 has been enqueued (pipeline schedules)
 
 
 def rigid_tables(img, lattices, pixel_spacing):
@@ -1128,10 +1097,11 @@ def raw_fused_supported(raw, pl):
     return raw.dtype in (torch.uint8, torch.int16) and rows_ok and w % 4 == 0 and t <= 256 and raw.data_ptr() % 16 == 0
 
 
-def global_shifts_raw(rm: RawMovie, reference_frame, pixel_spacing, b_factor, frequency_range):
+def global_shifts_raw(rm: RawMovie, reference_frame, pixel_spacing, b_factor, frequency_range, after_k1=None):
     """global_shifts for a RawMovie: K1 reads the raw bytes (mc_xc_rows_forward_raw / mc_xcg_rows_forward_raw), the
     statistics are known beforehand, so the plain column pass follows.  Raises McorrUnsupported for shapes
-    without a fused kernel."""
+    without a fused kernel.  `after_k1()`, if given, is called once the last chunk's K1 (and hot-pixel fix-up)
+    has been enqueued."""
     lib = _lib.load()
     t, h, w = rm.shape
     dev = rm.raw.device
@@ -1164,8 +1134,8 @@ def global_shifts_raw(rm: RawMovie, reference_frame, pixel_spacing, b_factor, fr
         if rm.n_hot:  # hot pixels of these frames: sparse correction of T1 (no fp32 movie)
             check(lib.mc_xc_rows_hot_correct(ptr(rm.hot_keys), ptr(rm.hot_rv), rm.n_hot, a, n, h, w, ptr(pl.mask),
                                              ptr(rm.mean_rstd), ptr(T1), g, st), "mc_xc_rows_hot_correct")
-        if a + n >= t and AFTER_K1_HOOK is not None:
-            AFTER_K1_HOOK()
+        if a + n >= t and after_k1 is not None:
+            after_k1()
         check(_k2(lib, g, dev, T1, pl.filt, S[a:a + n], pl.tw_col, n, st), "xc cols forward")
     del T1
     return _shifts_from_spectra(S, t, reference_frame, pl)

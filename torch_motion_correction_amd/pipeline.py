@@ -46,36 +46,24 @@ class MoviePipeline:
         # the estimator's stream gets the higher priority: its short, latency-bound kernels then
         # slot in between the waves of the long HBM-bound warp instead of queueing behind them
         # (measured: 19.4-19.7 k -> 20.1-20.4 k frames/s on 40 x 4096^2 stacks)
-        import os
-
-        pe, pw = (int(x) for x in os.environ.get("MC_PIPE_PRIORITIES", "-1,0").split(","))
-        self._s_est = torch.cuda.Stream(self.device, priority=pe) if overlap else None
-        self._s_warp = torch.cuda.Stream(self.device, priority=pw) if overlap else None
-        self._s_rest = None  # third stream of the three-stage schedule, created on first use
-        self._tables = {}
+        self._s_est = torch.cuda.Stream(self.device, priority=-1) if overlap else None
+        self._s_warp = torch.cuda.Stream(self.device, priority=0) if overlap else None
 
     # the two stages, each enqueued on whatever stream is current
-    def _estimate(self, img: torch.Tensor) -> torch.Tensor:
+    def _estimate(self, img: torch.Tensor, after_k1: Optional[Callable[[], None]] = None):
+        """-> ((2,t,1,1) Angstrom field (dfu.py:129-162), warp_args for ``_correct``).  Everything of
+        correct_motion that only needs the field -- the per-frame lattice values and the rigid warp's weight
+        tables -- is built right here, on the ESTIMATOR's stream, in two launches (mc_rigid_tables_from_shifts;
+        it used to be seven, each waiting for a wave slot under the previous movie's warp).  Every tensor in
+        warp_args is record_stream()ed on the warp stream.  `after_k1()` runs once K1 is enqueued."""
         t = img.shape[0]
         ref = t // 2 if self.reference_frame is None else int(self.reference_frame)
-        shifts = engine.global_shifts(img, ref, self.pixel_spacing, self.b_factor, self.frequency_range)
-        return self._field_and_tables(img, shifts)
+        shifts = engine.global_shifts(img, ref, self.pixel_spacing, self.b_factor, self.frequency_range, after_k1)
+        return engine.rigid_tables_from_shifts(shifts, tuple(img.shape), self.pixel_spacing, self.grid_type)
 
-    def _field_and_tables(self, img: torch.Tensor, shifts: torch.Tensor) -> torch.Tensor:
-        """(t,2) px shifts -> the (2,t,1,1) Angstrom field (dfu.py:129-162); everything of correct_motion that
-        only needs the field -- the per-frame lattice values and the rigid warp's weight tables -- is built
-        right here, on the ESTIMATOR's stream, in two launches (mc_rigid_tables_from_shifts; it used to be
-        seven, each waiting for a wave slot under the previous movie's warp), and handed to ``_prepare``."""
-        field, tables = engine.rigid_tables_from_shifts(shifts, tuple(img.shape), self.pixel_spacing, self.grid_type)
-        self._tables[id(img)] = tables
-        return field
-
-    def _prepare(self, img: torch.Tensor, field: torch.Tensor):
-        return self._tables.pop(id(img))
-
-    def _correct(self, img: torch.Tensor, tables):
+    def _correct(self, img: torch.Tensor, warp_args):
         return engine.warp(img, None, self.pixel_spacing, want_frames=self.return_frames, want_sum=True,
-                           rigid=True, tables=tables)
+                           rigid=True, tables=warp_args)
 
     def iterate(self, movies: Iterable[torch.Tensor],
                 around_warp: Optional[Callable[[Callable[[], object]], object]] = None):
@@ -93,9 +81,8 @@ class MoviePipeline:
             for img in movies:
                 with device_scope(dev):
                     img = self._check(img)
-                    field = self._estimate(img)
-                    tables = self._prepare(img, field)
-                    frames, total = call(lambda: self._correct(img, tables))
+                    field, warp_args = self._estimate(img)
+                    frames, total = call(lambda: self._correct(img, warp_args))
                 yield MovieResult(field, total, frames)
             return
         with device_scope(dev):
@@ -104,167 +91,48 @@ class MoviePipeline:
             start.record(caller)
             self._s_est.wait_event(start)
             self._s_warp.wait_event(start)
-        import os
 
-        # MC_PIPE_SCHEDULE: k1first (default), abc (three stages, the warp alone), all (round 2: the whole
-        # estimator under the previous warp), k2first -- measured on 40 x 4096^2 (same box): 1.70 / 1.92 /
-        # 1.76-1.79 / 1.72-1.73 ms per step
-        if os.environ.get("MC_PIPE_SCHEDULE", "k1first") == "abc" and type(self) is MoviePipeline:
-            yield from self._iterate_three_stage(movies, call, caller)
-            return
-        sched = os.environ.get("MC_PIPE_SCHEDULE", "k1first")
-        k1_first = sched in ("k1first", "k2first", "k3first")
-        engine.HOOK_AFTER_K2 = sched == "k2first"
-        from . import _lib
-        lib = _lib.load()
+        def enqueue_warp(img, field, warp_args, ready, next_k1_done):
+            # the warp of movie k waits for its estimate and, when there is one, for movie k+1's K1
+            # (which has then left the HBM to this warp)
+            with torch.cuda.stream(self._s_warp):
+                self._s_warp.wait_event(ready)
+                if next_k1_done is not None:
+                    self._s_warp.wait_event(next_k1_done)
+                field.record_stream(self._s_warp)
+                for x in warp_args:
+                    if isinstance(x, torch.Tensor):
+                        x.record_stream(self._s_warp)
+                frames, total = call(lambda: self._correct(img, warp_args))
+            return MovieResult(field, total, frames)
+
         try:
-            pending = None  # k1first: (img, field, tables, ready) of the movie whose warp is not enqueued yet
-            warp_done = None
+            pending = None  # (img, field, warp_args, ready) of the movie whose warp is not enqueued yet
             for img in movies:
+                res = None
                 with device_scope(dev):
                     img = self._check(img)
                     img.record_stream(self._s_est)
                     img.record_stream(self._s_warp)
-                    k1_done = torch.cuda.Event() if k1_first else None
+                    k1_done = torch.cuda.Event()
                     with torch.cuda.stream(self._s_est):
-                        if sched == "k3first":
-                            # the previous warp waits until every machine-filling kernel of this estimate (K1,
-                            # K2, the near-window column pass) has run; the C library records the event.  And
-                            # this estimate starts once the warp before that one has finished: strict alternation
-                            # [K1 K2 K3n](k+1) -> [warp(k) || rest of the search(k+1)] -> [K1 K2 K3n](k+2) ...
-                            if warp_done is not None:
-                                self._s_est.wait_event(warp_done)
-                            k1_done.record(self._s_est)  # creates the hipEvent
-                            lib.mc_xc_after_k3n_event(k1_done.cuda_event)
-                        elif k1_first:
-                            engine.AFTER_K1_HOOK = lambda: k1_done.record(self._s_est)
-                        try:
-                            field = self._estimate(img)
-                        finally:
-                            engine.AFTER_K1_HOOK = None
-                            if sched == "k3first":
-                                lib.mc_xc_after_k3n_event(None)
-                        tables = self._prepare(img, field)
+                        field, warp_args = self._estimate(img, lambda: k1_done.record(self._s_est))
                         ready = torch.cuda.Event()
                         ready.record(self._s_est)
-
-                    def enqueue_warp(img_, field_, tables_, ready_, extra=None):
-                        with torch.cuda.stream(self._s_warp):
-                            self._s_warp.wait_event(ready_)
-                            if extra is not None:
-                                self._s_warp.wait_event(extra)  # the NEXT movie's K1 has left the HBM to this warp
-                            field_.record_stream(self._s_warp)
-                            for x in tables_:
-                                if isinstance(x, torch.Tensor):
-                                    x.record_stream(self._s_warp)
-                            return call(lambda: self._correct(img_, tables_))
-
-                    if not k1_first:
-                        frames, total = enqueue_warp(img, field, tables, ready)
-                        res = MovieResult(field, total, frames)
-                    else:
-                        res = None
-                        if pending is not None:
-                            pimg, pfield, ptables, pready = pending
-                            frames, total = enqueue_warp(pimg, pfield, ptables, pready, k1_done)
-                            res = MovieResult(pfield, total, frames)
-                            if sched == "k3first":
-                                warp_done = torch.cuda.Event()
-                                warp_done.record(self._s_warp)
-                        pending = (img, field, tables, ready)
+                    if pending is not None:
+                        res = enqueue_warp(*pending, k1_done)
+                    pending = (img, field, warp_args, ready)
                 if res is not None:
                     yield res
-            if k1_first and pending is not None:
+            if pending is not None:
                 with device_scope(dev):
-                    pimg, pfield, ptables, pready = pending
-                    with torch.cuda.stream(self._s_warp):
-                        self._s_warp.wait_event(pready)
-                        pfield.record_stream(self._s_warp)
-                        for x in ptables:
-                            if isinstance(x, torch.Tensor):
-                                x.record_stream(self._s_warp)
-                        frames, total = call(lambda: self._correct(pimg, ptables))
-                yield MovieResult(pfield, total, frames)
+                    res = enqueue_warp(*pending, None)
+                yield res
         finally:
             with device_scope(dev):
                 for s in (self._s_est, self._s_warp):
                     done = torch.cuda.Event()
                     done.record(s)
-                    caller.wait_event(done)
-
-    def _iterate_three_stage(self, movies, call, caller):
-        """Three stages on three streams: A = K1 (the estimator's HBM-bound row pass), B = the rest of the
-        estimator and the warp's tables (latency-bound kernels with 32 KB of LDS per workgroup), C = the
-        warp.  Per period   [ A(m) || B(m-1) ]  then  [ C(m-1) ] :  the warp has the chip to itself (under
-        the two-stream overlap its launch stretched from 1.09 to 1.44-1.65 ms: K1 took its HBM share, K2-K4
-        only fit into a CU once a warp tile had retired), and B's workgroups fit beside K1's, which hold
-        64 KB of LDS per CU.  Events only; no host synchronisation."""
-        dev = self.device
-        if self._s_rest is None:
-            self._s_rest = torch.cuda.Stream(dev)
-        s_a, s_b, s_c = self._s_est, self._s_rest, self._s_warp
-        with device_scope(dev):
-            start = torch.cuda.Event()
-            start.record(caller)
-            s_b.wait_event(start)
-        t_ref = lambda img: (img.shape[0] // 2 if self.reference_frame is None else int(self.reference_frame))  # noqa: E731
-        pending = None   # (img, state, evA) of the movie whose stages B and C are not enqueued yet
-        ev_c = None      # end of the last enqueued warp
-
-        def stage_bc(p, ev_a_next):
-            nonlocal ev_c
-            pimg, pstate, pev_a = p
-            with torch.cuda.stream(s_b):
-                s_b.wait_event(pev_a)
-                if ev_c is not None:
-                    s_b.wait_event(ev_c)
-                for x in engine.stage_tensors(pstate):
-                    x.record_stream(s_b)
-                shifts = engine.global_stage_b(pstate, t_ref(pimg))
-                field = self._field_and_tables(pimg, shifts)
-                tables = self._prepare(pimg, field)
-                ev_b = torch.cuda.Event()
-                ev_b.record(s_b)
-            with torch.cuda.stream(s_c):
-                s_c.wait_event(ev_b)
-                if ev_a_next is not None:
-                    s_c.wait_event(ev_a_next)  # the next movie's K1 has left the HBM to this warp
-                field.record_stream(s_c)
-                for x in tables:
-                    if isinstance(x, torch.Tensor):
-                        x.record_stream(s_c)
-                frames, total = call(lambda: self._correct(pimg, tables))
-                ev_c = torch.cuda.Event()
-                ev_c.record(s_c)
-            return MovieResult(field, total, frames)
-
-        try:
-            for img in movies:
-                res = None
-                with device_scope(dev):
-                    img = self._check(img)
-                    for s_ in (s_a, s_b, s_c):
-                        img.record_stream(s_)
-                    with torch.cuda.stream(s_a):
-                        if ev_c is not None:
-                            s_a.wait_event(ev_c)
-                        state = engine.global_stage_a(img, self.pixel_spacing, self.b_factor, self.frequency_range)
-                        ev_a = torch.cuda.Event()
-                        ev_a.record(s_a)
-                    if pending is not None:
-                        res = stage_bc(pending, ev_a)
-                    pending = (img, state, ev_a)
-                if res is not None:
-                    yield res
-            if pending is not None:
-                with device_scope(dev):
-                    res = stage_bc(pending, None)
-                yield res
-        finally:
-            with device_scope(dev):
-                for s_ in (s_a, s_b, s_c):
-                    done = torch.cuda.Event()
-                    done.record(s_)
                     caller.wait_event(done)
 
     def run(self, movies: Iterable[torch.Tensor],
@@ -312,7 +180,6 @@ class RawMoviePipeline(MoviePipeline):
                          return_frames, overlap)
         self.gain = None if gain is None else gain.detach().to(device=self.device, dtype=torch.float32).contiguous()
         self.mean_zero = bool(mean_zero)
-        self._rm = {}
 
     def _check(self, img: torch.Tensor) -> torch.Tensor:
         if img.dim() != 3:
@@ -323,24 +190,20 @@ class RawMoviePipeline(MoviePipeline):
             img = img.detach().to(device=self.device).contiguous()
         return img
 
-    def _estimate(self, img: torch.Tensor) -> torch.Tensor:
+    def _estimate(self, img: torch.Tensor, after_k1: Optional[Callable[[], None]] = None):
         t = img.shape[0]
         ref = t // 2 if self.reference_frame is None else int(self.reference_frame)
         # the statistics (and hot-pixel) passes, on the estimator's stream
         rm = engine.RawMovie(img, self.gain, mean_zero=self.mean_zero, hot_pixel_threshold=self.hot_pixel_threshold)
-        self._rm[id(img)] = rm
-        shifts = engine.global_shifts_raw(rm, ref, self.pixel_spacing, self.b_factor, self.frequency_range)
-        return self._field_and_tables(img, shifts)
-
-    def _prepare(self, img: torch.Tensor, field: torch.Tensor):
-        rm = self._rm.pop(id(img))
-        shifts_px, scratch = self._tables.pop(id(img))
+        shifts = engine.global_shifts_raw(rm, ref, self.pixel_spacing, self.b_factor, self.frequency_range, after_k1)
+        field, (shifts_px, scratch) = engine.rigid_tables_from_shifts(shifts, tuple(img.shape), self.pixel_spacing,
+                                                                      self.grid_type)
         # every tensor the warp stream reads that was made on the estimator's stream (the all-ones gain of
-        # gain=None, the hot-pixel list, ...) is in the tuple: the caller record_stream()s them all
-        return (shifts_px, scratch, *rm.device_tensors(), rm)
+        # gain=None, the hot-pixel list, ...) is in the tuple: iterate() record_stream()s them all
+        return field, (shifts_px, scratch, *rm.device_tensors(), rm)
 
-    def _correct(self, img: torch.Tensor, tables):
-        shifts_px, scratch, rm = tables[0], tables[1], tables[-1]
+    def _correct(self, img: torch.Tensor, warp_args):
+        shifts_px, scratch, rm = warp_args[0], warp_args[1], warp_args[-1]
         return engine.warp_rigid_raw(rm, None, self.pixel_spacing, want_frames=self.return_frames, want_sum=True,
                                      tables=(shifts_px, scratch))
 
