@@ -446,27 +446,15 @@ int mc_pixel_shifts_at(const float* lattice, int GH, int GW, int h, int w, float
  *                          floats apart) -> S
  *   mc_full_cols_shift     per job: fft along y, * exp(-2 pi i (fy sy + fx sx)) * scale,
  *                          shifts[j] = (sy, sx) px, ifft along y, in place
- *   mc_full_cols_dose      A += sum_f q_f(k) fft_y(S_f) over the nframes frames of S (frames frame0..
- *                          of total_frames; first: A starts at zero); last: A *= scale / sqrt(sum_f
- *                          q_f^2) over ALL frames and is transformed back along y (then
- *                          mc_full_rows_inverse(A) is the exposure-filtered sum).  q_f as in
- *                          mc_dose_accumulate.  A: H * pitch complex.
  *   mc_full_rows_inverse   irfft along x (c2r, unscaled) of S -> real rows at out + out_off[j] */
 int mc_full_spectrum_pitch(int W);
 int mc_full_rows_forward(const float* src, const int64_t* job_off, int64_t row_stride, void* S,
                          const void* tw_row, int njobs, int H, int W, int pitch, void* stream);
 int mc_full_cols_shift(void* S, const float* shifts, const void* tw_col, float scale, int njobs, int H, int W,
                        int pitch, void* stream);
-int mc_full_cols_dose(const void* S, int nframes, int frame0, int total_frames, void* A, const void* tw_col,
-                      int H, int W, int pitch, float pixel_size, float pre_exposure, float dose_per_frame,
-                      float voltage, int first, int last, float scale, void* stream);
-/* Column-major copy of a chunk of row-major spectra, ST[job][kx][y] (kx <= W/2), and the exposure-weighted
- * pass reading it (H = 4096, 4092 or 8184: contiguous columns instead of 8 bytes of every 128-byte line;
- * A stays row-major; otherwise as mc_full_cols_dose). */
+/* Column-major copy of a chunk of row-major spectra, ST[job][kx][y] (kx <= W/2), for the accumulating
+ * column passes (mc_full_cols_shift_sum_cm: contiguous columns instead of 8 bytes of every 128-byte line). */
 int mc_full_transpose(const void* S, void* ST, int njobs, int H, int W, int pitch, void* stream);
-int mc_full_cols_dose_cm(const void* ST, int nframes, int frame0, int total_frames, void* A, const void* tw_col,
-                         int H, int W, int pitch, float pixel_size, float pre_exposure, float dose_per_frame,
-                         float voltage, int first, int last, float scale, void* stream);
 int mc_full_rows_inverse(const void* S, float* out, const int64_t* out_off, int64_t out_stride,
                          const void* tw_row, int njobs, int H, int W, int pitch, void* stream);
 /* Fused Fourier-shift sums (correct_motion_fast -> sum / dose_weighted_sum without the shifted frames):
@@ -483,13 +471,16 @@ int mc_full_rows_inverse(const void* S, float* out, const int64_t* out_off, int6
  *                             after mc_full_rows_forward_raw the spectra are those of the movie with its hot
  *                             pixels replaced.  kx x is reduced mod W in integers; one writer per bin, in list
  *                             order (reproducible).
- *   mc_full_cols_shift_sum    per frame j of the chunk: fft along y, * exp(-2 pi i (fy sy + fx sx)) with
- *                             shifts[j] = (sy, sx) px (mc_full_cols_shift's angle), then accumulated over the
- *                             frames: into P plainly, into A weighted by q_f (mc_full_cols_dose's filter),
- *                             either or both (NULL: not accumulated; at least one).  first / last / scale as
- *                             mc_full_cols_dose: on the last chunk A is scaled by scale / sqrt(sum_f q_f^2), P
- *                             by scale, and both are transformed back along y (then mc_full_rows_inverse gives
- *                             the sums).  The dose arguments are read only with A.  Both sums come from one
+ *   mc_full_cols_shift_sum    per frame j of the nframes frames of S (frames frame0.. of total_frames): fft
+ *                             along y, * exp(-2 pi i (fy sy + fx sx)) with shifts[j] = (sy, sx) px
+ *                             (mc_full_cols_shift's angle), then accumulated over the frames: into P plainly,
+ *                             into A weighted by the exposure filter q_f(k) (as mc_dose_accumulate), either or
+ *                             both (NULL: not accumulated; at least one).  shifts == NULL: no phase ramp, the
+ *                             exposure-weighted sum of the frames themselves -- valid with A alone (P set:
+ *                             MC_ERR_ARG).  first: the sums start at zero, else add to what A / P hold; last: A
+ *                             is scaled by scale / sqrt(sum_f q_f^2) over ALL frames, P by scale, and both are
+ *                             transformed back along y (then mc_full_rows_inverse gives the sums).  A, P: H *
+ *                             pitch complex.  The dose arguments are read only with A.  Both sums come from one
  *                             read of the spectra for H = 4096; other heights take one launch per sum.
  *   mc_full_cols_shift_sum_cm the same reading the column-major copy of mc_full_transpose (H = 4096, 4092,
  *                             8184). */

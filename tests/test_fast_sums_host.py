@@ -177,6 +177,17 @@ def test_shift_sum_validates_on_the_host():
     assert run(ps=0.0) == -1 and run(dose=-1.0) == -1 and run(dose=float("nan")) == -1
     assert run(W=1000) == -2 and run(H=300) == -2
     assert run(cm=True) == -2  # the column-major feed: 4096 / 4092 / 8184 rows only
+    # shifts=None: no phase ramp, the exposure-weighted sum alone (P set: -1); the other rules hold as they are
+    assert run(shifts=None, A=None) == -1
+    for cm in (False, True):
+        def bare(**kw):
+            return run(shifts=None, P=None, cm=cm, **kw)
+
+        assert bare(S=None) == -1 and bare(tw=None) == -1 and bare(A=None) == -1
+        assert bare(n=0) == -1 and bare(f0=-1) == -1 and bare(total=1) == -1
+        assert bare(ps=0.0) == -1 and bare(dose=-1.0) == -1 and bare(dose=float("nan")) == -1
+        assert bare(W=1000) == -2 and bare(H=300) == -2
+    assert run(shifts=None, P=None, cm=True) == -2  # the column-major feed: 4096 / 4092 / 8184 rows only
 
 
 def _ramp(h, w, sy, sx):

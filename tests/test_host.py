@@ -227,7 +227,7 @@ def test_abi_rejects_bad_arguments_without_touching_the_gpu():
     assert lib.mc_warp_frames(None, 1, 64, 64, None, 10, 10, 1.0, None, None, None, None) == -1
 
 
-def test_full_spectrum_and_storage_entry_points_validate_on_the_host():
+def test_full_spectrum_and_storage_entry_points_check_arguments_on_the_host():
     """The round-2 entry points (row-major full-spectrum transforms, fp16 storage tags) check sizes,
     pointers and storage tags before any launch: pitch rule, supported row / column lengths (powers of
     two and the K3 formats), MC_ERR_ARG for null pointers, MC_ERR_UNSUPPORTED for sizes the library has
@@ -240,7 +240,8 @@ def test_full_spectrum_and_storage_entry_points_validate_on_the_host():
         assert lib.mc_full_rows_forward(None, one, w, one, one, 1, h, w, pitch, None) == -1  # null src
         assert lib.mc_full_cols_shift(None, one, one, 1.0, 1, h, w, pitch, None) == -1
         assert lib.mc_full_rows_inverse(one, None, one, w, one, 1, h, w, pitch, None) == -1
-        assert lib.mc_full_cols_dose(one, 0, 0, 1, one, one, h, w, pitch, 1.0, 0.0, 1.0, 300.0, 1, 1, 1.0, None) == -1
+        assert lib.mc_full_cols_shift_sum(one, None, 0, 0, 1, one, None, one, h, w, pitch, 1.0, 0.0, 1.0, 300.0, 1,
+                                          1, 1.0, None) == -1
     for (h, w) in ((4000, 4096), (4096, 4000), (128, 64), (8192, 64), (4092, 32)):  # no kernel for these
         pitch = lib.mc_full_spectrum_pitch(w)
         assert lib.mc_full_rows_forward(one, one, w, one, one, 1, h, w, pitch, None) == -2

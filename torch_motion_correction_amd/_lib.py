@@ -78,8 +78,6 @@ SIGNATURES = {
     "mc_full_spectrum_pitch": [i32],
     "mc_full_rows_forward": [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp],
     "mc_full_cols_shift": [vp, vp, vp, f32, i32, i32, i32, i32, vp],
-    "mc_full_cols_dose": [vp, i32, i32, i32, vp, vp, i32, i32, i32, f32, f32, f32, f32, i32, i32, f32, vp],
-    "mc_full_cols_dose_cm": [vp, i32, i32, i32, vp, vp, i32, i32, i32, f32, f32, f32, f32, i32, i32, f32, vp],
     "mc_full_transpose": [vp, vp, i32, i32, i32, i32, vp],
     "mc_full_rows_inverse": [vp, vp, vp, i64, vp, i32, i32, i32, i32, vp],
     "mc_full_rows_forward_raw": [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],

@@ -17,8 +17,9 @@
 //
 //   full_rows_fwd   rows:  samples -> real FFT(W) -> S[job][y][0..W/2]
 //   full_cols_shift cols:  S column pair -> FFT(H) -> * exp(-2 pi i (fy sy + fx sx)) / (H W) -> IFFT(H) -> S
-//   full_cols_dose  cols:  sum_f q_f(k) FFT_H(S_f column) accumulated in registers over the frames
-//                          of a chunk (+ A) -> A; on the last chunk / sqrt(sum q^2), IFFT(H), / (H W)
+//   full_cols_shift_sum  cols:  sum_f q_f(k) [R_f(k)] FFT_H(S_f column) accumulated in registers over
+//                          the frames of a chunk (+ A) -> A; on the last chunk / sqrt(sum q^2), IFFT(H), / (H W)
+//                          -- with or without the frames' phase ramps R_f; the plain sum likewise into P
 //   full_rows_inv   rows:  S[job][y][0..W/2] -> c2r pack -> IFFT(W/2) -> real rows
 //
 // Sizes: rows of W = 64 .. 8192 (powers of two), 5760 and 11520 columns (W / 2 = 2^a 3^2 5);
@@ -28,9 +29,10 @@
 #include "mc_fft.h"
 #include "mcorr.h"
 
-// FULL_FFT_PART (the build compiles this file twice, as xcg_fft.hip): 0 the transforms of
-// correct_motion_fast and dose_weighted_sum, 1 the fused shift-and-sum entry points; undefined: both.
-// Each object instantiates only its own kernels, so neither part changes the other's code.
+// FULL_FFT_PART (the build compiles this file twice, as xcg_fft.hip): 0 the per-frame transforms of
+// correct_motion_fast, 1 the accumulating column passes (the sums of dose_weighted_sum and of the fused
+// shift-and-sum) and the raw row pass; undefined: both.  Each object instantiates only its own kernels,
+// so neither part changes the other's code (one object holding both changed untouched kernels' code).
 #if !defined(FULL_FFT_PART) || FULL_FFT_PART == 0
 #define FULL_FFT_BASE 1
 #else
@@ -263,131 +265,6 @@ __host__ __device__ constexpr int full_last_slots() {
   return ((H / r + WG - 1) / WG) * r;  // iterations of the last pass x its radix
 }
 
-// Input strides (in complex elements): element (frame j, row y, column kx) of S sits at
-// j sf + y sr + kx sc -- row-major spectra: (H pitch, pitch, 1); column-major copies made by
-// full_transpose: (ncols H, 1, H), read with NC = 1 as contiguous columns.
-template <int H, int NC, int WG>
-__global__ __launch_bounds__(WG) void full_cols_dose(const cfloat* __restrict__ S, int nframes, int frame0,
-                                                        int total_frames, cfloat* __restrict__ A, int W,
-                                                        int pitch, const cfloat* __restrict__ tw_col,
-                                                        float pixel_size, float pre_exposure,
-                                                        float dose_per_frame, float vscale, int first, int last,
-                                                        float scale, int64_t sf, int64_t sr, int64_t sc) {
-  constexpr int SLOTS = full_last_slots<H, WG>();
-  extern __shared__ __attribute__((aligned(16))) char smem_fc[];
-  cfloat* lines[2] = {reinterpret_cast<cfloat*>(smem_fc), reinterpret_cast<cfloat*>(smem_fc) + lds_len(H)};
-  const int tid = threadIdx.x;
-  const int kx0 = full_col_of_block<NC>(blockIdx.x, pitch);
-  if (kx0 > W / 2) return;  // padding columns of the pitch (workgroup-uniform)
-  // mixed-radix lines (one column per workgroup): the exposure exponents of the column's rows sit in
-  // LDS behind the line instead of in 24-33 registers per thread
-  constexpr bool MH_LDS = (H & (H - 1)) != 0;
-  static_assert(!MH_LDS || NC == 1, "mixed-radix exposure pass: one column per workgroup");
-  float* mhl = reinterpret_cast<float*>(lines[0] + NC * lds_len(H));
-  if constexpr (MH_LDS) {
-    for (int ky = tid; ky < H; ky += WG) mhl[ky] = full_dose_mh(kx0, ky, W, H, pixel_size, vscale);
-  }
-  cfloat acc[NC][SLOTS];
-  float mh[NC][MH_LDS ? 1 : SLOTS];
-  int kys[SLOTS];  // output row of a slot (power-of-two lines: recorded; mixed radix: computed, see below)
-  int nslots = 0;
-#pragma unroll
-  for (int s = 0; s < SLOTS; ++s) kys[s] = 0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-      acc[c][s] = cmake(0.f, 0.f);
-      if constexpr (!MH_LDS) mh[c][s] = 0.f;
-    }
-  for (int j = 0; j < nframes; ++j) {
-    full_cols_load<H, NC, WG>(lines, S + (int64_t)j * sf + (int64_t)kx0 * sc, sr, tid);
-    __syncthreads();
-    const float dose = pre_exposure + dose_per_frame * (float)(frame0 + j + 1);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      cfloat* line = lines[c];
-      auto rd = [&](int i) { return line[lpad(i)]; };
-      auto take3 = [&](int ky, cfloat v, int slot) {
-        float m;
-        if constexpr (MH_LDS) {
-          m = mhl[ky];
-        } else {
-          if (j == 0) {
-            kys[slot] = ky;
-            mh[c][slot] = full_dose_mh(kx0 + c, ky, W, H, pixel_size, vscale);
-          }
-          m = mh[c][slot];
-        }
-        const float q = expf(m * dose);
-        acc[c][slot].x += q * v.x;
-        acc[c][slot].y += q * v.y;
-      };
-      if constexpr ((H & (H - 1)) == 0) {
-        int slot = 0;  // the last pass calls `take` SLOTS times per thread, in a fixed (unrolled) order
-        auto take = [&](int ky, cfloat v) {
-          take3(ky, v, slot);
-          ++slot;
-        };
-        wg_fft_any_inplace<H, -1, WG>(line, full_opaque(tid), tw_col, 1, rd, take);
-        nslots = slot;
-      } else {
-        // mixed radix: the pass itself names the slot (iteration x radix + output), a compile-time
-        // constant at every call site; the last iteration only runs on the threads that have a butterfly
-        wg_fft_any_inplace<H, -1, WG>(line, full_opaque(tid), tw_col, 1, rd, take3);
-        constexpr int R = full_last_radix<H>();
-        nslots = (tid + (SLOTS / R - 1) * WG < H / R) ? SLOTS : SLOTS - R;
-      }
-    }
-    __syncthreads();  // the next frame overwrites the lines
-  }
-  // accumulator columns: add what earlier chunks left in A, on the last chunk "restore the power"
-  // (/ sqrt(sum_f q_f^2) over ALL frames), transform back and scale
-  cfloat* abase = A + kx0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-      if (s >= nslots) continue;
-      cfloat a = acc[c][s];
-      int ky = kys[s];
-      if constexpr ((H & (H - 1)) != 0) {  // last mixed-radix pass: output j + m H/R of butterfly j = tid + it WG
-        constexpr int R = full_last_radix<H>();
-        ky = tid + (s / R) * WG + (s % R) * (H / R);
-      }
-      if (!first) {
-        const cfloat prev = abase[(int64_t)ky * pitch + c];
-        a.x += prev.x;
-        a.y += prev.y;
-      }
-      if (last) {
-        const float m = MH_LDS ? mhl[ky] : mh[c][MH_LDS ? 0 : s];
-        float qq = 0.f;
-        for (int f = 0; f < total_frames; ++f) {
-          const float q = expf(m * (pre_exposure + dose_per_frame * (float)(f + 1)));
-          qq += q * q;
-        }
-        const float r = scale / sqrtf(qq);
-        a.x *= r;
-        a.y *= r;
-      }
-      lines[c][lpad(ky)] = a;
-    }
-  }
-  __syncthreads();
-  if (last) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      cfloat* line = lines[c];
-      auto rd = [&](int i) { return line[lpad(i)]; };
-      auto back = [&](int y, cfloat v) { line[lpad(y)] = v; };
-      wg_fft_any_inplace<H, +1, WG>(line, full_opaque(tid), tw_col, 1, rd, back);
-      __syncthreads();
-    }
-  }
-  full_cols_store<H, NC, WG>(lines, abase, pitch, tid);
-}
-
 // ---- H = 4096: the register-resident radix-16 transform (mc_fft.h: 16 x 16 x 16, three passes,
 // two exchanges through ONE 32 KiB line, 4 barriers).  Thread tid owns inputs 256 n1 + tid and
 // outputs tid + 256 k3 -- the same rows -- so a column pair goes global -> registers -> forward ->
@@ -435,106 +312,11 @@ __global__ __launch_bounds__(MC_WG) void full_cols_shift_r16(cfloat* __restrict_
         make_float4(v[0][n1].x, v[0][n1].y, v[1][n1].x, v[1][n1].y);
 }
 
-#endif  // FULL_FFT_BASE
-
-template <int NC>
-__global__ __launch_bounds__(MC_WG) void full_cols_dose_r16(const cfloat* __restrict__ S, int nframes, int frame0,
-                                                            int total_frames, cfloat* __restrict__ A, int W,
-                                                            int pitch, const cfloat* __restrict__ tw_col,
-                                                            float pixel_size, float pre_exposure,
-                                                            float dose_per_frame, float vscale, int first, int last,
-                                                            float scale, int64_t sf, int64_t sr, int64_t sc) {
-  // NC = 1: one column per workgroup (8-byte loads; 130 registers instead of 256 + spills to AGPRs:
-  // three wavefronts per SIMD instead of one)
-  constexpr int H = 4096;
-  __shared__ __attribute__((aligned(16))) cfloat line[H];
-  const int tid = threadIdx.x;
-  const int kx0 = full_col_of_block<NC>(blockIdx.x, pitch);
-  if (kx0 > W / 2) return;  // padding columns of the pitch (workgroup-uniform)
-  cfloat acc[NC][16];
-  float mh[NC][16];
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int k3 = 0; k3 < 16; ++k3) {
-      acc[c][k3] = cmake(0.f, 0.f);
-      mh[c][k3] = full_dose_mh(kx0 + c, tid + 256 * k3, W, H, pixel_size, vscale);
-    }
-  for (int j = 0; j < nframes; ++j) {
-    const cfloat* base = S + (int64_t)j * sf + (int64_t)kx0 * sc;
-    cfloat v[NC][16];
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) {
-      if constexpr (NC == 2) {
-        const float4 q = *reinterpret_cast<const float4*>(base + (int64_t)(256 * n1 + tid) * sr);
-        v[0][n1] = cmake(q.x, q.y);
-        v[1][n1] = cmake(q.z, q.w);
-      } else {
-        v[0][n1] = base[(int64_t)(256 * n1 + tid) * sr];
-      }
-    }
-    const float dose = pre_exposure + dose_per_frame * (float)(frame0 + j + 1);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      auto in = [&](int n1, int) { return v[c][n1]; };
-      auto take = [&](int k, cfloat x) {
-        const int k3 = (k - tid) >> 8;
-        const float q = expf(mh[c][k3] * dose);
-        acc[c][k3].x += q * x.x;
-        acc[c][k3].y += q * x.y;
-      };
-      wg_fft4096_r16<-1, 8, 8>(line, tid, tw_col, in, take);
-      __syncthreads();
-    }
-  }
-  cfloat* abase = A + kx0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int k3 = 0; k3 < 16; ++k3) {
-      cfloat a = acc[c][k3];
-      if (!first) {
-        const cfloat prev = abase[(int64_t)(tid + 256 * k3) * pitch + c];
-        a.x += prev.x;
-        a.y += prev.y;
-      }
-      if (last) {
-        float qq = 0.f;
-        for (int f = 0; f < total_frames; ++f) {
-          const float q = expf(mh[c][k3] * (pre_exposure + dose_per_frame * (float)(f + 1)));
-          qq += q * q;
-        }
-        const float r = scale / sqrtf(qq);
-        a.x *= r;
-        a.y *= r;
-      }
-      acc[c][k3] = a;
-    }
-  if (last) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      auto in = [&](int n1, int) { return acc[c][n1]; };
-      auto back = [&](int k, cfloat x) { acc[c][(k - tid) >> 8] = x; };
-      wg_fft4096_r16<+1, 8, 8>(line, tid, tw_col, in, back);
-      __syncthreads();
-    }
-  }
-#pragma unroll
-  for (int n1 = 0; n1 < 16; ++n1) {
-    if constexpr (NC == 2)
-      *reinterpret_cast<float4*>(abase + (int64_t)(256 * n1 + tid) * pitch) =
-          make_float4(acc[0][n1].x, acc[0][n1].y, acc[1][n1].x, acc[1][n1].y);
-    else
-      abase[(int64_t)(256 * n1 + tid) * pitch] = acc[0][n1];
-  }
-}
-
 // S[job][y][pitch] (row-major) -> ST[job][kx][y] (column-major, kx <= W/2) through 64 x 64 LDS tiles:
 // whole 512-byte row pieces in, whole 512-byte column pieces out.  The column passes use 8 or 16
 // bytes of every 128-byte line of a row-major spectrum (L2 -> L1 traffic 8-16x the data: what
 // bounds them); the exposure-weighted pass, which only READS the spectra of a chunk of frames,
 // is fed from this copy instead: contiguous columns, one read + write pass more, less time.
-#if FULL_FFT_BASE
 __global__ __launch_bounds__(256) void full_transpose(const cfloat* __restrict__ S, cfloat* __restrict__ ST, int H,
                                                       int ncols, int pitch) {
   __shared__ __attribute__((aligned(16))) cfloat tile[64][66];
@@ -667,55 +449,6 @@ int mc_full_transpose(const void* S, void* ST, int njobs, int H, int W, int pitc
   return mc_check_launch();
 }
 
-static int full_cols_dose_impl(const void* S, bool colmajor, int nframes, int frame0, int total_frames, void* A,
-                               const void* tw_col, int H, int W, int pitch, float pixel_size, float pre_exposure,
-                               float dose_per_frame, float voltage, int first, int last, float scale, void* stream);
-
-int mc_full_cols_dose(const void* S, int nframes, int frame0, int total_frames, void* A, const void* tw_col,
-                      int H, int W, int pitch, float pixel_size, float pre_exposure, float dose_per_frame,
-                      float voltage, int first, int last, float scale, void* stream) {
-  return full_cols_dose_impl(S, false, nframes, frame0, total_frames, A, tw_col, H, W, pitch, pixel_size, pre_exposure,
-                             dose_per_frame, voltage, first, last, scale, stream);
-}
-
-int mc_full_cols_dose_cm(const void* ST, int nframes, int frame0, int total_frames, void* A, const void* tw_col,
-                         int H, int W, int pitch, float pixel_size, float pre_exposure, float dose_per_frame,
-                         float voltage, int first, int last, float scale, void* stream) {
-  if (H != 4096 && H != 4092 && H != 8184) return MC_ERR_UNSUPPORTED;  // the one-column-per-workgroup kernels
-  return full_cols_dose_impl(ST, true, nframes, frame0, total_frames, A, tw_col, H, W, pitch, pixel_size, pre_exposure,
-                             dose_per_frame, voltage, first, last, scale, stream);
-}
-
-static int full_cols_dose_impl(const void* S, bool colmajor, int nframes, int frame0, int total_frames, void* A,
-                               const void* tw_col, int H, int W, int pitch, float pixel_size, float pre_exposure,
-                               float dose_per_frame, float voltage, int first, int last, float scale, void* stream) {
-  if (!S || !A || !tw_col || nframes < 1 || frame0 < 0 || total_frames < frame0 + nframes || !(pixel_size > 0.f) ||
-      !(dose_per_frame >= 0.f))
-    return MC_ERR_ARG;
-  if (!full_sizes_ok(H, W, pitch)) return MC_ERR_UNSUPPORTED;
-  const float vscale = voltage >= 300.f ? 1.0f : (voltage >= 200.f ? 0.8f : 0.75f);
-  const int64_t sf = colmajor ? (int64_t)(W / 2 + 1) * H : (int64_t)H * pitch;
-  const int64_t sr = colmajor ? 1 : pitch, sc = colmajor ? H : 1;
-  if (H == 4096) {
-    hipLaunchKernelGGL(full_cols_dose_r16<1>, dim3(pitch), dim3(MC_WG), 0, (hipStream_t)stream, (const cfloat*)S,
-                       nframes, frame0, total_frames, (cfloat*)A, W, pitch, (const cfloat*)tw_col, pixel_size,
-                       pre_exposure, dose_per_frame, vscale, first, last, scale, sf, sr, sc);
-    return mc_check_launch();
-  }
-  MC_FULL_DISPATCH_COLS(H, {
-    // mixed-radix columns: one column per workgroup (two columns' accumulators and exposure exponents
-    // on top of the radix-31 pass need 300 registers: one wavefront per SIMD)
-    constexpr int NC = (L & (L - 1)) ? 1 : full_nc<L>(), WG = full_wg<L>();
-    auto k = full_cols_dose<L, NC, WG>;
-    const size_t lds = NC * sizeof(cfloat) * (size_t)lds_len(L) + ((L & (L - 1)) ? sizeof(float) * (size_t)L : 0);
-    MC_FULL_SET_LDS(k, lds);
-    hipLaunchKernelGGL(k, dim3(pitch / NC), dim3(WG), lds, (hipStream_t)stream, (const cfloat*)S, nframes, frame0,
-                       total_frames, (cfloat*)A, W, pitch, (const cfloat*)tw_col, pixel_size, pre_exposure,
-                       dose_per_frame, vscale, first, last, scale, sf, sr, sc);
-  });
-  return mc_check_launch();
-}
-
 }  // extern "C"
 #endif  // FULL_FFT_BASE
 
@@ -724,7 +457,8 @@ static int full_cols_dose_impl(const void* S, bool colmajor, int nframes, int fr
 // linear, so   sum_f irfft2(R_f X_f) = irfft2(sum_f R_f X_f)  and the exposure-weighted sum of the shifted
 // frames is  irfft2(sum_f q_f R_f X_f) / sqrt(sum_f q_f^2)  (q_f is real and even in ky, and irfft2 ignores
 // what rfft2(irfft2(.)) would project away): one forward transform per frame with the ramp R_f applied
-// and both sums accumulated inside the forward column pass, then one inverse transform per sum.
+// and both sums accumulated inside the forward column pass, then one inverse transform per sum.  Without
+// the ramp the same pass gives the exposure-weighted sum of the frames themselves (dose_weighted_sum).
 #if FULL_FFT_SUMS
 // The conditioning of mc_condition_movie, c = raw * gain - mu_f, as it rounds it: a product, then a
 // difference (cond_vec_kernel compiles to v_pk_mul_f32 + v_pk_add_f32, no fma) -- so a raw row pass
@@ -792,18 +526,23 @@ __device__ __forceinline__ cfloat full_ramp(cfloat v, int ky, int H, float fx, f
   return z;
 }
 
-// full_cols_dose with the phase ramp: each frame's forward column transform is multiplied by its ramp
-// (shifts[j] = (sy, sx) px of frame j of the chunk), then accumulated over the frames -- MODE 1: plainly
-// into P, 2: exposure-weighted into A (as full_cols_dose), 3: both from one read of the spectra.  The first /
-// last chunk logic and the inverse column transform are full_cols_dose's; the plain sum's last chunk is only
-// scaled (no exposure normalisation).
+// Each frame's forward column transform is multiplied by its phase ramp (shifts[j] = (sy, sx) px of frame j of
+// the chunk), then accumulated over the frames in registers -- MODE 1: plainly into P, 2: exposure-weighted into
+// A, 3: both from one read of the spectra; 2 | FULL_NO_RAMP: exposure-weighted without the ramp (shifts not read),
+// the exposure-filtered sum of the frames as they are.  The accumulators add what earlier chunks left in A / P
+// (first = 0); on the last chunk they are normalised, transformed back along the columns and scaled (the plain
+// sum only scaled).
+constexpr int FULL_NO_RAMP = 4;
 template <int MODE>
 struct full_mode {
-  static_assert(MODE >= 1 && MODE <= 3, "plain (1), exposure-weighted (2) or both (3)");
-  static constexpr bool dose = (MODE & 2) != 0, plain = (MODE & 1) != 0;
+  static_assert(MODE == 1 || MODE == 2 || MODE == 3 || MODE == (2 | FULL_NO_RAMP),
+                "plain (1), exposure-weighted (2) or both (3) with the phase ramp; exposure-weighted without it (6)");
+  static constexpr bool dose = (MODE & 2) != 0, plain = (MODE & 1) != 0, ramp = (MODE & FULL_NO_RAMP) == 0;
 };
 
-// Input strides as full_cols_dose's (row-major spectra or the column-major copy of full_transpose).
+// Input strides (in complex elements): element (frame j, row y, column kx) of S sits at
+// j sf + y sr + kx sc -- row-major spectra: (H pitch, pitch, 1); column-major copies made by
+// full_transpose: (ncols H, 1, H), read with NC = 1 as contiguous columns.
 template <int H, int NC, int WG, int MODE>
 __global__ __launch_bounds__(WG) void full_cols_shift_sum(const cfloat* __restrict__ S, const float* __restrict__ shifts,
                                               int nframes, int frame0, int total_frames, cfloat* __restrict__ A,
@@ -845,7 +584,11 @@ __global__ __launch_bounds__(WG) void full_cols_shift_sum(const cfloat* __restri
     full_cols_load<H, NC, WG>(lines, S + (int64_t)j * sf + (int64_t)kx0 * sc, sr, tid);
     __syncthreads();
     const float dose = pre_exposure + dose_per_frame * (float)(frame0 + j + 1);
-    const float sy = shifts[2 * j], sx = shifts[2 * j + 1];
+    float sy = 0.f, sx = 0.f;
+    if constexpr (M::ramp) {
+      sy = shifts[2 * j];
+      sx = shifts[2 * j + 1];
+    }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       cfloat* line = lines[c];
@@ -862,7 +605,7 @@ __global__ __launch_bounds__(WG) void full_cols_shift_sum(const cfloat* __restri
           }
           if constexpr (M::dose) m = mh[c][slot];
         }
-        v = full_ramp(v, ky, H, fx, sy, sx);
+        if constexpr (M::ramp) v = full_ramp(v, ky, H, fx, sy, sx);
         if constexpr (M::plain) {
           pacc[c][slot].x += v.x;
           pacc[c][slot].y += v.y;
@@ -988,14 +731,18 @@ __global__ __launch_bounds__(MC_WG) void full_cols_shift_sum_r16(const cfloat* _
       }
     }
     const float dose = pre_exposure + dose_per_frame * (float)(frame0 + j + 1);
-    const float sy = shifts[2 * j], sx = shifts[2 * j + 1];
+    float sy = 0.f, sx = 0.f;
+    if constexpr (M::ramp) {
+      sy = shifts[2 * j];
+      sx = shifts[2 * j + 1];
+    }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const float fx = (float)(kx0 + c) * (float)(1.0 / (double)W);
       auto in = [&](int n1, int) { return v[c][n1]; };
       auto take = [&](int k, cfloat x) {
         const int k3 = (k - tid) >> 8;
-        x = full_ramp(x, k, H, fx, sy, sx);
+        if constexpr (M::ramp) x = full_ramp(x, k, H, fx, sy, sx);
         if constexpr (M::plain) {
           pacc[c][k3].x += x.x;
           pacc[c][k3].y += x.y;
@@ -1032,8 +779,15 @@ __global__ __launch_bounds__(MC_WG) void full_cols_shift_sum_r16(const cfloat* _
             }
             r = scale / sqrtf(qq);
           }
-          a.x *= r;
-          a.y *= r;
+          if constexpr (M::ramp) {
+            a.x *= r;
+            a.y *= r;
+          } else {  // rounded on its own, not fused into the inverse transform's first butterfly: the
+                    // bits of the exposure-weighted sum this pass replaced
+#pragma clang fp contract(off)
+            a.x *= r;
+            a.y *= r;
+          }
         }
         ac[c][k3] = a;
       }
@@ -1124,8 +878,9 @@ static int full_cols_shift_sum_impl(const void* S, bool colmajor, const float* s
                                     int total_frames, void* A, void* P, const void* tw_col, int H, int W, int pitch,
                                     float pixel_size, float pre_exposure, float dose_per_frame, float voltage,
                                     int first, int last, float scale, void* stream) {
-  if (!S || !shifts || (!A && !P) || !tw_col || nframes < 1 || frame0 < 0 || total_frames < frame0 + nframes)
+  if (!S || (!A && !P) || !tw_col || nframes < 1 || frame0 < 0 || total_frames < frame0 + nframes)
     return MC_ERR_ARG;
+  if (!shifts && P) return MC_ERR_ARG;  // no phase ramp: the exposure-weighted sum alone
   if (A && !(pixel_size > 0.f && dose_per_frame >= 0.f)) return MC_ERR_ARG;
   if (!full_sizes_ok(H, W, pitch)) return MC_ERR_UNSUPPORTED;
   if (colmajor && H != 4096 && H != 4092 && H != 8184) return MC_ERR_UNSUPPORTED;
@@ -1137,7 +892,7 @@ static int full_cols_shift_sum_impl(const void* S, bool colmajor, const float* s
                                    pre_exposure, dose_per_frame, vscale, first, last, scale, sf, sr, sc, stream)
   if (A && P) {
     // Both sums from one read of the spectra: the register-resident 4096-row kernel (252 VGPRs, two waves per
-    // SIMD as full_cols_dose_r16).  The staged kernels take one launch per sum and read the spectra twice:
+    // SIMD as the exposure-weighted pass alone: 207).  The staged kernels take one launch per sum and read the spectra twice:
     // on the mixed-radix columns (one column per workgroup, already register-bound) both accumulators spill
     // (8184 rows) or fall to one wave per SIMD (4092); on the power-of-two columns the kernel with both
     // accumulators live rounds the plain sum differently in its last bits (1024 rows), and the plain sum
@@ -1148,6 +903,7 @@ static int full_cols_shift_sum_impl(const void* S, bool colmajor, const float* s
     }
     return MC_SHIFT_SUM(3, A, P);
   }
+  if (!shifts) return MC_SHIFT_SUM(2 | FULL_NO_RAMP, A, nullptr);
   return A ? MC_SHIFT_SUM(2, A, nullptr) : MC_SHIFT_SUM(1, nullptr, P);
 #undef MC_SHIFT_SUM
 }

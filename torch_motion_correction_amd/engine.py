@@ -660,31 +660,15 @@ def _fourier_shift_polyphase(img, shifts):
     S = torch.empty((2 * chunk, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
     st = stream_ptr(dev)
     shifts = shifts.to(dev, torch.float32).contiguous()
-    zero = torch.zeros((2 * chunk, 2), dtype=torch.float32, device=dev)
     for a in range(0, t, chunk):
         n = min(chunk, t - a)
         sub = torch.cat([img[a:a + n, :, 0::2], img[a:a + n, :, 1::2]], dim=0).contiguous()  # (2n, h, w2)
         off = torch.arange(2 * n, device=dev, dtype=torch.int64) * (h * w2)
-        idx = torch.arange(2 * n, device=dev, dtype=torch.int32)
         check(_k1(lib, g, dev, sub, off, w2, None, None, None, T1, tw_row, 2 * n, st), "xc rows forward")
         check(_k2(lib, g, dev, T1, None, S, tw_col, 2 * n, st), "xc cols forward")
         check(lib.mc_polyphase_fourier_shift(ptr(S), ptr(shifts[a:a + n]), n, g.nkx, h, w, st),
               "mc_polyphase_fourier_shift")
-        if planmod.native_height(g.H):
-            check(lib.mc_fourier_shift_cols_inverse(ptr(S), ptr(idx), ptr(zero), ptr(T1), ptr(tw_col),
-                                                    1.0 / (h * w2), 2 * n, g, st), "mc_fourier_shift_cols_inverse")
-        else:
-            line, _ = planmod.line_plan(g.H, +1, dev)
-            check(lib.mc_xcg_cols_inverse(ptr(S), ptr(idx), None, None, ptr(zero), ptr(T1), line,
-                                          1.0 / (h * w2), 2 * n, g, st), "mc_xcg_cols_inverse")
-        res = torch.empty_like(sub)
-        if planmod.native_rows(g):
-            check(lib.mc_xc_rows_inverse_store(ptr(T1), ptr(res), ptr(off), w2, ptr(tw_row), 2 * n, g, st),
-                  "mc_xc_rows_inverse_store")
-        else:
-            line, _ = planmod.line_plan(planmod.row_line_length(g.W), +1, dev)
-            check(lib.mc_xcg_rows_inverse(ptr(T1), None, None, None, None, ptr(res), ptr(off), w2,
-                                          ptr(tw_row), line, 2 * n, g, st), "mc_xcg_rows_inverse")
+        res = _inverse_frames(lib, g, S, 2 * n, h, w2, dev, st, out=torch.empty_like(sub), off=off, T2=T1)
         out[a:a + n, :, 0::2] = res[:n]
         out[a:a + n, :, 1::2] = res[n:]
     return out
@@ -729,53 +713,62 @@ def _fourier_shift_row_major(img, shifts):
     return out
 
 
-def _dose_weighted_sum_row_major(img, pixel_spacing, dose_per_frame, pre_exposure, voltage, frames_of=None,
-                                 shape=None):
-    """dose_weighted_sum on the row-major kernels: rows forward per chunk, the exposure-weighted
-    accumulation inside the forward column pass (frame loop in registers), one inverse per movie.
-    `frames_of(a, n)` -> the (n, h, w) fp32 frames a .. a+n-1 (default: slices of `img`); a caller
-    that produces the frames on the fly (motion_correct_sum: warp a chunk, transform it, drop it)
-    never holds more than one chunk of corrected frames."""
+def _rows_forward(src, first, n, S):
+    """mc_full_rows_forward of the fp32 frames first .. first+n-1 of `src` (t, h, w) into S (chunk, h, pitch, 2)."""
     lib = _lib.load()
-    t, h, w = img.shape if shape is None else shape
-    dev = img.device
+    _, h, w = src.shape
+    dev = src.device
+    off = torch.arange(first, first + n, device=dev, dtype=torch.int64) * (h * w)
+    check(lib.mc_full_rows_forward(ptr(src), ptr(off), w, ptr(S), ptr(planmod.get_twiddles(w, dev)), n, h, w,
+                                   S.shape[2], stream_ptr(dev)), "mc_full_rows_forward")
+
+
+def _row_major_sums(shape, dev, forward_rows, shifts=None, pixel_spacing=1.0, dose_per_frame=None, pre_exposure=0.0,
+                    voltage=300.0, want_plain=False):
+    """Frame sums on the row-major kernels with ONE inverse transform per sum.  Per chunk of frames (the
+    WORKSPACE_BYTES rule) `forward_rows(a, n, S)` enqueues the row transforms of frames a .. a+n-1 into S (chunk, h,
+    pitch, 2); the forward column pass (mc_full_cols_shift_sum) then multiplies each frame by its phase ramp
+    (`shifts`, (t, 2) fp32 px; None: no ramp) and accumulates, in registers over the chunk's frames, the
+    exposure-weighted sum (with `dose_per_frame`) and / or the plain sum (`want_plain`, with shifts only).  A caller
+    that makes the frames on the fly (warp a chunk, transform it, drop it) never holds more than one chunk of them.
+    Returns (dose-weighted sum or None, plain sum or None)."""
+    lib = _lib.load()
+    t, h, w = shape
+    with_dose = dose_per_frame is not None
     pitch = lib.mc_full_spectrum_pitch(w)
     tw_row, tw_col = planmod.get_twiddles(w, dev), planmod.get_twiddles(h, dev)
     per_frame = h * pitch * 8
-    # 4096 / 4092 rows: the exposure-weighted pass reads a column-major copy of the chunk's spectra
-    # (mc_full_transpose): contiguous columns instead of 8 bytes of every 128-byte line -- 4.4 -> 3.6 ms
-    # per 40 x 4096^2, 8.6 -> 7.4 ms per 40 x 4092 x 5760 with the copy's own read + write pass paid.
-    # Not for 8184 rows (14.4 -> 15.2 ms per 12 frames: that column kernel is bound by its radix-31
-    # pass on 512-thread workgroups, not by how it is fed).
+    # 4096 / 4092 rows: the column pass reads a column-major copy of the chunk's spectra (mc_full_transpose):
+    # contiguous columns instead of 8 bytes of every 128-byte line -- 4.4 -> 3.6 ms per 40 x 4096^2 exposure-weighted
+    # sum, 8.6 -> 7.4 ms per 40 x 4092 x 5760 with the copy's own read + write pass paid.  Not for 8184 rows (14.4 ->
+    # 15.2 ms per 12 frames: that column kernel is bound by its radix-31 pass on 512-thread workgroups, not by how it
+    # is fed).
     colmajor = DOSE_COLUMN_MAJOR and h in (4096, 4092)
     chunk = max(1, min(t, WORKSPACE_BYTES // ((2 if colmajor else 1) * per_frame)))
     S = torch.empty((chunk, h, pitch, 2), dtype=torch.float32, device=dev)
     ST = torch.empty((chunk, w // 2 + 1, h, 2), dtype=torch.float32, device=dev) if colmajor else None
-    A = torch.empty((h, pitch, 2), dtype=torch.float32, device=dev)
+    sums = torch.empty((int(with_dose) + int(want_plain), h, pitch, 2), dtype=torch.float32, device=dev)
+    A = sums[0] if with_dose else None
+    P = sums[-1] if want_plain else None
     st = stream_ptr(dev)
     for a in range(0, t, chunk):
         n = min(chunk, t - a)
-        if frames_of is None:
-            src, first = img, a
-        else:
-            src, first = frames_of(a, n), 0
-        off = torch.arange(first, first + n, device=dev, dtype=torch.int64) * (h * w)
-        check(lib.mc_full_rows_forward(ptr(src), ptr(off), w, ptr(S), ptr(tw_row), n, h, w, pitch, st),
-              "mc_full_rows_forward")
-        dose_args = (n, a, t, ptr(A), ptr(tw_col), h, w, pitch, float(pixel_spacing), float(pre_exposure),
-                     float(dose_per_frame), float(voltage), 1 if a == 0 else 0, 1 if a + n >= t else 0,
-                     1.0 / (h * w), st)
+        forward_rows(a, n, S)
+        sum_args = (None if shifts is None else ptr(shifts[a:a + n]), n, a, t, ptr(A), ptr(P), ptr(tw_col), h, w,
+                    pitch, float(pixel_spacing), float(pre_exposure), float(dose_per_frame) if with_dose else 0.0,
+                    float(voltage), 1 if a == 0 else 0, 1 if a + n >= t else 0, 1.0 / (h * w), st)
         if colmajor:
             check(lib.mc_full_transpose(ptr(S), ptr(ST), n, h, w, pitch, st), "mc_full_transpose")
-            check(lib.mc_full_cols_dose_cm(ptr(ST), *dose_args), "mc_full_cols_dose_cm")
+            check(lib.mc_full_cols_shift_sum_cm(ptr(ST), *sum_args), "mc_full_cols_shift_sum_cm")
         else:
-            check(lib.mc_full_cols_dose(ptr(S), *dose_args), "mc_full_cols_dose")
-        del src
-    out = torch.empty((h, w), dtype=torch.float32, device=dev)
-    off0 = torch.zeros(1, device=dev, dtype=torch.int64)
-    check(lib.mc_full_rows_inverse(ptr(A), ptr(out), ptr(off0), w, ptr(tw_row), 1, h, w, pitch, st),
+            check(lib.mc_full_cols_shift_sum(ptr(S), *sum_args), "mc_full_cols_shift_sum")
+    del S, ST
+    n = sums.shape[0]
+    out = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+    off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
+    check(lib.mc_full_rows_inverse(ptr(sums), ptr(out), ptr(off), w, ptr(tw_row), n, h, w, pitch, st),
           "mc_full_rows_inverse")
-    return out
+    return (out[0] if with_dose else None), (out[-1] if want_plain else None)
 
 
 def warp_dose_weighted_sum(img, lattices, pixel_spacing, rigid, dose_per_frame, pre_exposure, voltage):
@@ -788,12 +781,12 @@ def warp_dose_weighted_sum(img, lattices, pixel_spacing, rigid, dose_per_frame, 
         frames, _ = warp(img, lattices, pixel_spacing, want_frames=True, want_sum=False, rigid=rigid)
         return dose_weighted_sum(frames, pixel_spacing, dose_per_frame, pre_exposure, voltage)
 
-    def frames_of(a, n):
-        return warp(img[a:a + n], lattices[a:a + n], pixel_spacing, want_frames=True, want_sum=False,
-                    rigid=rigid)[0]
+    def forward_rows(a, n, S):  # the chunk's warped frames are released on return, before the next chunk's warp
+        frames = warp(img[a:a + n], lattices[a:a + n], pixel_spacing, want_frames=True, want_sum=False, rigid=rigid)[0]
+        _rows_forward(frames, 0, n, S)
 
-    return _dose_weighted_sum_row_major(img, pixel_spacing, dose_per_frame, pre_exposure, voltage,
-                                        frames_of=frames_of, shape=(t, h, w))
+    return _row_major_sums(img.shape, img.device, forward_rows, pixel_spacing=pixel_spacing,
+                           dose_per_frame=dose_per_frame, pre_exposure=pre_exposure, voltage=voltage)[0]
 
 
 def fourier_shift(img, shifts):
@@ -818,7 +811,6 @@ def fourier_shift(img, shifts):
     chunk = max(1, min(t, WORKSPACE_BYTES // (2 * per_frame)))
     T1 = torch.empty((chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
     S = torch.empty((chunk, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
-    idx = torch.arange(chunk, device=dev, dtype=torch.int32)
     st = stream_ptr(dev)
     shifts = shifts.to(dev, torch.float32).contiguous()
     for a in range(0, t, chunk):
@@ -827,38 +819,31 @@ def fourier_shift(img, shifts):
         check(_k1(lib, g, dev, img, off, w, None, None, None, T1, tw_row, n, st), "xc rows forward")
         check(_k2(lib, g, dev, T1, None, S, tw_col, n, st), "xc cols forward")
         # T1 is dead now and has the same footprint as T2: reuse it
-        if planmod.native_height(g.H):
-            check(lib.mc_fourier_shift_cols_inverse(ptr(S), ptr(idx), ptr(shifts[a : a + n]), ptr(T1),
-                                                    ptr(tw_col), 1.0 / (h * w), n, g, st),
-                  "mc_fourier_shift_cols_inverse")
-        else:
-            line, _ = planmod.line_plan(g.H, +1, dev)
-            check(lib.mc_xcg_cols_inverse(ptr(S), ptr(idx), None, None, ptr(shifts[a : a + n]), ptr(T1),
-                                          line, 1.0 / (h * w), n, g, st), "mc_xcg_cols_inverse")
-        if planmod.native_rows(g):
-            check(lib.mc_xc_rows_inverse_store(ptr(T1), ptr(out), ptr(off), w, ptr(tw_row), n, g, st),
-                  "mc_xc_rows_inverse_store")
-        else:
-            line, _ = planmod.line_plan(planmod.row_line_length(g.W), +1, dev)
-            check(lib.mc_xcg_rows_inverse(ptr(T1), None, None, None, None, ptr(out), ptr(off), w,
-                                          ptr(tw_row), line, n, g, st), "mc_xcg_rows_inverse")
+        _inverse_frames(lib, g, S, n, h, w, dev, st, shifts=shifts[a:a + n], out=out, off=off, T2=T1)
     return out
 
 
-def _inverse_frames(lib, g, S, n, h, w, dev, st):
-    """irfft2 of n full spectra S (n, nkx, H) -> (n, h, w) frames (zero-shift Fourier-shift path)."""
+def _inverse_frames(lib, g, S, n, h, w, dev, st, shifts=None, out=None, off=None, T2=None):
+    """irfft2 of n full spectra S (n, nkx, nky) of the pruned engine, each multiplied by its phase ramp (`shifts`
+    (n, 2) fp32 px; None: zero shifts): the column inverse (mc_fourier_shift_cols_inverse on native heights,
+    mc_xcg_cols_inverse otherwise) into T2 (n, nkx, H; default: a new buffer), then the row inverse
+    (mc_xc_rows_inverse_store on native rows, mc_xcg_rows_inverse otherwise) into `out` at element offsets `off`
+    (default: a new (n, h, w) tensor).  Returns out."""
     tw_row, tw_col = planmod.get_twiddles(w, dev), planmod.get_twiddles(h, dev)
-    out = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+        off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
     idx = torch.arange(n, device=dev, dtype=torch.int32)
-    zero = torch.zeros((n, 2), device=dev, dtype=torch.float32)
-    off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
-    T2 = torch.empty((n, g.nkx, g.H, 2), dtype=torch.float32, device=dev)
+    if shifts is None:
+        shifts = torch.zeros((n, 2), device=dev, dtype=torch.float32)
+    if T2 is None:
+        T2 = torch.empty((n, g.nkx, g.H, 2), dtype=torch.float32, device=dev)
     if planmod.native_height(g.H):
-        check(lib.mc_fourier_shift_cols_inverse(ptr(S), ptr(idx), ptr(zero), ptr(T2), ptr(tw_col),
+        check(lib.mc_fourier_shift_cols_inverse(ptr(S), ptr(idx), ptr(shifts), ptr(T2), ptr(tw_col),
                                                 1.0 / (h * w), n, g, st), "mc_fourier_shift_cols_inverse")
     else:
         line, _ = planmod.line_plan(g.H, +1, dev)
-        check(lib.mc_xcg_cols_inverse(ptr(S), ptr(idx), None, None, ptr(zero), ptr(T2), line,
+        check(lib.mc_xcg_cols_inverse(ptr(S), ptr(idx), None, None, ptr(shifts), ptr(T2), line,
                                       1.0 / (h * w), n, g, st), "mc_xcg_cols_inverse")
     if planmod.native_rows(g):
         check(lib.mc_xc_rows_inverse_store(ptr(T2), ptr(out), ptr(off), w, ptr(tw_row), n, g, st),
@@ -914,7 +899,9 @@ def dose_weighted_sum(img, pixel_spacing, dose_per_frame, pre_exposure=0.0, volt
     if POLYPHASE_FOURIER_SHIFT:
         return _dose_weighted_sum_polyphase(img, pixel_spacing, dose_per_frame, pre_exposure, voltage)
     if _full_row_major_ok(h, w):
-        return _dose_weighted_sum_row_major(img, pixel_spacing, dose_per_frame, pre_exposure, voltage)
+        return _row_major_sums(img.shape, dev, lambda a, n, S: _rows_forward(img, a, n, S),
+                               pixel_spacing=pixel_spacing, dose_per_frame=dose_per_frame, pre_exposure=pre_exposure,
+                               voltage=voltage)[0]
     try:
         g = planmod.full_geometry(h, w)
     except NotImplementedError:
@@ -937,26 +924,8 @@ def dose_weighted_sum(img, pixel_spacing, dose_per_frame, pre_exposure=0.0, volt
                                      float(dose_per_frame), float(voltage), 1 if a == 0 else 0,
                                      1 if a + n >= t else 0, st), "mc_dose_accumulate")
     # inverse of the single accumulated spectrum: Fourier-shift path with a zero shift
-    out = torch.empty((1, h, w), dtype=torch.float32, device=dev)
-    idx = torch.zeros(1, device=dev, dtype=torch.int32)
-    zero = torch.zeros((1, 2), device=dev, dtype=torch.float32)
-    off0 = torch.zeros(1, device=dev, dtype=torch.int64)
-    T2 = T1[:1] if g.ny == g.H else torch.empty((1, g.nkx, g.H, 2), dtype=torch.float32, device=dev)
-    if planmod.native_height(g.H):
-        check(lib.mc_fourier_shift_cols_inverse(ptr(A), ptr(idx), ptr(zero), ptr(T2), ptr(tw_col),
-                                                1.0 / (h * w), 1, g, st), "mc_fourier_shift_cols_inverse")
-    else:
-        line, _ = planmod.line_plan(g.H, +1, dev)
-        check(lib.mc_xcg_cols_inverse(ptr(A), ptr(idx), None, None, ptr(zero), ptr(T2), line,
-                                      1.0 / (h * w), 1, g, st), "mc_xcg_cols_inverse")
-    if planmod.native_rows(g):
-        check(lib.mc_xc_rows_inverse_store(ptr(T2), ptr(out), ptr(off0), w, ptr(tw_row), 1, g, st),
-              "mc_xc_rows_inverse_store")
-    else:
-        line, _ = planmod.line_plan(planmod.row_line_length(g.W), +1, dev)
-        check(lib.mc_xcg_rows_inverse(ptr(T2), None, None, None, None, ptr(out), ptr(off0), w,
-                                      ptr(tw_row), line, 1, g, st), "mc_xcg_rows_inverse")
-    return out[0]
+    T2 = T1[:1] if g.ny == g.H else None
+    return _inverse_frames(lib, g, A, 1, h, w, dev, st, T2=T2)[0]
 
 
 _RAW_KINDS = {torch.uint8: 0, torch.int16: 1, torch.float16: 2, torch.float32: 3}
@@ -1256,8 +1225,8 @@ def warp_field_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want
 def warp_dose_weighted_sum_raw(rm: RawMovie, lattices, pixel_spacing, rigid, dose_per_frame, pre_exposure, voltage,
                                want_plain):
     """warp_dose_weighted_sum of the conditioned movie straight from a RawMovie: each chunk of frames (the
-    WORKSPACE_BYTES rule of _dose_weighted_sum_row_major) is warped from the raw bytes of its frame window,
-    transformed and weighted, then dropped -- neither the conditioned nor the corrected fp32 movie is held.
+    WORKSPACE_BYTES rule of _row_major_sums) is warped from the raw bytes of its frame window, transformed and
+    weighted, then dropped -- neither the conditioned nor the corrected fp32 movie is held.
     `want_plain`: the plain sum too, from the same warp launches (the first chunk stores it, the others add to it:
     ((s_0 + s_1) + s_2) + ... in chunk order).  Returns (dose-weighted sum, plain sum or None).  Raises
     McorrUnsupported for shapes outside the row-major kernels, with POLYPHASE_FOURIER_SHIFT, and for whatever the
@@ -1268,16 +1237,14 @@ def warp_dose_weighted_sum_raw(rm: RawMovie, lattices, pixel_spacing, rigid, dos
     if not rigid:
         _local_raw_check(rm)  # before anything is launched
     plain = torch.empty((h, w), dtype=torch.float32, device=rm.raw.device) if want_plain else None
+    warp_raw = warp_rigid_raw if rigid else warp_field_raw
 
-    def frames_of(a, n):
-        win = rm.window(a, n)
+    def forward_rows(a, n, S):  # the chunk's warped frames are released on return, before the next chunk's warp
         kw = dict(want_frames=True, out_sum=plain, accumulate=want_plain and a > 0)
-        if rigid:
-            return warp_rigid_raw(win, lattices[a:a + n], pixel_spacing, **kw)[0]
-        return warp_field_raw(win, lattices[a:a + n], pixel_spacing, **kw)[0]
+        _rows_forward(warp_raw(rm.window(a, n), lattices[a:a + n], pixel_spacing, **kw)[0], 0, n, S)
 
-    dw = _dose_weighted_sum_row_major(rm.raw, pixel_spacing, dose_per_frame, pre_exposure, voltage,
-                                      frames_of=frames_of, shape=(t, h, w))
+    dw, _ = _row_major_sums(rm.shape, rm.raw.device, forward_rows, pixel_spacing=pixel_spacing,
+                            dose_per_frame=dose_per_frame, pre_exposure=pre_exposure, voltage=voltage)
     return dw, plain
 
 
@@ -1291,9 +1258,8 @@ def fast_shifts(grid_px):
 def fast_shift_sums(src, shifts, pixel_spacing=1.0, dose_per_frame=None, pre_exposure=0.0, voltage=300.0,
                     want_plain=False):
     """fourier_shift(frames, shifts) followed by its plain sum and / or dose_weighted_sum, without the shifted
-    frames: both are linear, so each chunk of frames (the WORKSPACE_BYTES rule and column-major copy of
-    _dose_weighted_sum_row_major) is transformed forward once and the column pass multiplies each frame's
-    spectrum by its phase ramp and accumulates the plain and / or exposure-weighted sums (mc_full_cols_shift_sum);
+    frames: both are linear, so each chunk of frames is transformed forward once and the column pass multiplies each
+    frame's spectrum by its phase ramp and accumulates the plain and / or exposure-weighted sums (_row_major_sums);
     one inverse transform per sum at the end.  `src`: an fp32 (t, h, w) tensor, or a RawMovie, whose chunks are
     transformed from the raw bytes of their frame window (mc_full_rows_forward_raw, then the window's hot pixels,
     mc_full_rows_hot_correct) -- the same launches on the same samples otherwise.  Returns (dose-weighted sum or
@@ -1303,51 +1269,22 @@ def fast_shift_sums(src, shifts, pixel_spacing=1.0, dose_per_frame=None, pre_exp
     t, h, w = src.shape
     if POLYPHASE_FOURIER_SHIFT or not _full_row_major_ok(h, w):
         raise _lib.McorrUnsupported(f"no fused Fourier-shift sums for frames of {h} x {w}")
-    lib = _lib.load()
     dev = src.raw.device if raw else src.device
-    with_dose = dose_per_frame is not None
-    want_plain = want_plain or not with_dose
-    pitch = lib.mc_full_spectrum_pitch(w)
-    tw_row, tw_col = planmod.get_twiddles(w, dev), planmod.get_twiddles(h, dev)
-    per_frame = h * pitch * 8
-    colmajor = DOSE_COLUMN_MAJOR and h in (4096, 4092)  # as _dose_weighted_sum_row_major
-    chunk = max(1, min(t, WORKSPACE_BYTES // ((2 if colmajor else 1) * per_frame)))
-    S = torch.empty((chunk, h, pitch, 2), dtype=torch.float32, device=dev)
-    ST = torch.empty((chunk, w // 2 + 1, h, 2), dtype=torch.float32, device=dev) if colmajor else None
-    sums = torch.empty((int(with_dose) + int(want_plain), h, pitch, 2), dtype=torch.float32, device=dev)
-    A = sums[0] if with_dose else None
-    P = sums[-1] if want_plain else None
-    shifts = shifts.to(dev, torch.float32).contiguous()
-    st = stream_ptr(dev)
-    for a in range(0, t, chunk):
-        n = min(chunk, t - a)
-        if raw:
-            win = src.window(a, n)
-            off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
-            check(lib.mc_full_rows_forward_raw(ptr(win.raw), win.kind, ptr(win.gain), ptr(win.mu), ptr(off), ptr(S),
-                                               ptr(tw_row), n, h, w, pitch, st), "mc_full_rows_forward_raw")
-            if win.n_hot:
-                check(lib.mc_full_rows_hot_correct(ptr(win.hot_keys), ptr(win.hot_rv), win.n_hot, 0, n, h, w, ptr(S),
-                                                   pitch, st), "mc_full_rows_hot_correct")
-        else:
-            off = torch.arange(a, a + n, device=dev, dtype=torch.int64) * (h * w)
-            check(lib.mc_full_rows_forward(ptr(src), ptr(off), w, ptr(S), ptr(tw_row), n, h, w, pitch, st),
-                  "mc_full_rows_forward")
-        sum_args = (ptr(shifts[a:a + n]), n, a, t, ptr(A), ptr(P), ptr(tw_col), h, w, pitch, float(pixel_spacing),
-                    float(pre_exposure), float(dose_per_frame) if with_dose else 0.0, float(voltage),
-                    1 if a == 0 else 0, 1 if a + n >= t else 0, 1.0 / (h * w), st)
-        if colmajor:
-            check(lib.mc_full_transpose(ptr(S), ptr(ST), n, h, w, pitch, st), "mc_full_transpose")
-            check(lib.mc_full_cols_shift_sum_cm(ptr(ST), *sum_args), "mc_full_cols_shift_sum_cm")
-        else:
-            check(lib.mc_full_cols_shift_sum(ptr(S), *sum_args), "mc_full_cols_shift_sum")
-    del S, ST
-    n = sums.shape[0]
-    out = torch.empty((n, h, w), dtype=torch.float32, device=dev)
-    off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
-    check(lib.mc_full_rows_inverse(ptr(sums), ptr(out), ptr(off), w, ptr(tw_row), n, h, w, pitch, st),
-          "mc_full_rows_inverse")
-    return (out[0] if with_dose else None), (out[-1] if want_plain else None)
+
+    def raw_rows(a, n, S):
+        lib = _lib.load()
+        win, pitch, st = src.window(a, n), S.shape[2], stream_ptr(dev)
+        off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
+        check(lib.mc_full_rows_forward_raw(ptr(win.raw), win.kind, ptr(win.gain), ptr(win.mu), ptr(off), ptr(S),
+                                           ptr(planmod.get_twiddles(w, dev)), n, h, w, pitch, st),
+              "mc_full_rows_forward_raw")
+        if win.n_hot:
+            check(lib.mc_full_rows_hot_correct(ptr(win.hot_keys), ptr(win.hot_rv), win.n_hot, 0, n, h, w, ptr(S),
+                                               pitch, st), "mc_full_rows_hot_correct")
+
+    forward_rows = raw_rows if raw else (lambda a, n, S: _rows_forward(src, a, n, S))
+    return _row_major_sums(src.shape, dev, forward_rows, shifts.to(dev, torch.float32).contiguous(), pixel_spacing,
+                           dose_per_frame, pre_exposure, voltage, want_plain=want_plain or dose_per_frame is None)
 
 
 _HOT_NONE = (1 << 63) - 1
