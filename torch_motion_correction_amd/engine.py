@@ -517,6 +517,17 @@ def frame_lattices(field, t, grid_type):
 RIGID_KERNEL_HOOK = None  # callable(fn) -> calls fn(); set by bench.py to time warp_rigid_dma alone
 
 
+def rigid_shifts_px(lattices, pixel_spacing):
+    """(t, 2) fp32 pixel shifts of the rigid warp from the (t, 2, GH, GW) Angstrom lattices of a (2, t, 1, 1)
+    field: the lattice value over the pixel spacing, the correctly rounded fp32 quotient -- the rule of rigid_tail,
+    of the general-field kernel and of the reference (a CPU tensor over a Python float).  The divisor is a device
+    tensor: ATen divides a CUDA tensor by a Python scalar as a multiply by fp32(1 / ps), which is one ulp off for
+    some shifts (ps = 0.83: -3 px becomes -3 - 2.4e-7, and pixel row 3 falls outside the frame).  No host
+    synchronisation."""
+    ps = torch.full((), float(pixel_spacing), dtype=torch.float32, device=lattices.device)
+    return torch.div(lattices[:, :, 0, 0], ps).contiguous()
+
+
 def rigid_tables(img, lattices, pixel_spacing):
     """The per-frame weight tables of the rigid warp (rigid_base + rigid_weights: phase 1 of
     mc_warp_rigid_phase_t) enqueued on the CURRENT stream -> an opaque handle for
@@ -525,7 +536,7 @@ def rigid_tables(img, lattices, pixel_spacing):
     lib = _lib.load()
     t, h, w = img.shape
     dev = img.device
-    shifts_px = (lattices[:, :, 0, 0] / pixel_spacing).contiguous()  # shifts_angstroms / ps
+    shifts_px = rigid_shifts_px(lattices, pixel_spacing)
     nbytes = C.c_int64(0)
     check(lib.mc_warp_rigid_scratch_bytes(t, h, w, C.byref(nbytes)), "mc_warp_rigid_scratch_bytes")
     scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
@@ -579,7 +590,7 @@ def warp(img, lattices, pixel_spacing, want_frames=True, want_sum=False, rigid=F
         if tables is None and RIGID_KERNEL_HOOK is not None:
             tables = rigid_tables(img, lattices, pixel_spacing)
         if tables is None:
-            shifts_px = (lattices[:, :, 0, 0] / pixel_spacing).contiguous()  # shifts_angstroms / ps
+            shifts_px = rigid_shifts_px(lattices, pixel_spacing)
             check(lib.mc_warp_rigid_scratch_bytes(t, h, w, C.byref(nbytes)), "mc_warp_rigid_scratch_bytes")
             scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
             args = (ptr(img), storage_of(img), t, h, w, ptr(shifts_px), ptr(scratch), ptr(frames), ptr(total))
@@ -1125,7 +1136,7 @@ def warp_rigid_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want
                                                  if want_sum else None)
     entry = lib.mc_warp_rigid_raw_accumulate if accumulate else lib.mc_warp_rigid_raw
     if tables is None:
-        shifts_px = (lattices[:, :, 0, 0] / pixel_spacing).contiguous()
+        shifts_px = rigid_shifts_px(lattices, pixel_spacing)
         nbytes = C.c_int64(0)
         check(lib.mc_warp_rigid_scratch_bytes(t, h, w, C.byref(nbytes)), "mc_warp_rigid_scratch_bytes")
         scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
