@@ -10,7 +10,8 @@ import pytest
 import torch
 
 from rigid_reference import (FRAME_SPACINGS, LARGE_SHIFTS, PIPELINE_SPACINGS, RAW_SPACINGS, SMALL_SHIFTS,
-                             TABLE_SPACINGS, canonical_shift, coordinate_ulp, neighbour_gradient, rigid_resample_stack)
+                             TABLE_SPACINGS, assert_frames as _assert_frames, canonical_shift, coordinate_ulp,
+                             neighbour_gradient, rigid_resample_stack)
 
 pytestmark = pytest.mark.gpu
 
@@ -75,23 +76,6 @@ def _frame_bound(ref, mag, h, w):
     upsample of the constant lattice, one coordinate ulp per axis moves the sample by at most ulp x the largest
     neighbour difference of its footprint (x 1.5: bicubic overshoot) -- assert_frames_close_large's rule."""
     return 32 * 2.0 ** -24 * mag + 2 * 1.5 * coordinate_ulp(h, w) * neighbour_gradient(ref)
-
-
-def _assert_frames(got, ref, bound, what, on_border=None):
-    got = got.detach().cpu().double().numpy()
-    zr, zg = ref == 0, got == 0
-    if on_border is not None:  # pixels where the zero rule is left to the kernel (see the caller)
-        bound = np.where(on_border & (zr != zg), np.inf, bound)
-        zg = np.where(on_border, zr, zg)
-    if not np.array_equal(zr, zg):
-        bad = np.argwhere(zr != zg)
-        frames = sorted({int(f) for f in bad[:, 0]})
-        rows = sorted({(int(f), int(y)) for f, y, _ in bad})[:12]
-        cols = sorted({(int(f), int(x)) for f, _, x in bad})[:12]
-        raise AssertionError(f"{what}: zero pattern differs in frames {frames}, (frame, row) {rows}, "
-                             f"(frame, col) {cols}: {int((zr != zg).sum())} pixels")
-    d = np.abs(got - ref)
-    assert bool((d <= bound).all()), (what, float((d - bound).max()))
 
 
 @pytest.mark.parametrize("ps", FRAME_SPACINGS)
