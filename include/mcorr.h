@@ -495,6 +495,17 @@ int mc_full_cols_shift_sum_cm(const void* ST, const float* shifts, int nframes, 
                               void* P, const void* tw_col, int H, int W, int pitch, float pixel_size,
                               float pre_exposure, float dose_per_frame, float voltage, int first, int last, float scale,
                               void* stream);
+/* Fourier cropping by 2 per axis (the "-FtBin 2" of production motion correction): with F = rfft2(x) of an
+ * H x W frame, y = irfft2(G, (H/2, W/2)) of G = the rows -H/4 <= ky < H/4 (signed; the new Nyquist row from
+ * the negative side) and columns 0 <= kx <= W/4 of F, scaled by 1 / ((H/2) (W/2)): the frame's sum is kept.
+ *   mc_full_cols_crop  per job: columns kx <= W/4 of S (H x pitch; the others are never read): fft along y,
+ *                      the kept rows * 1 / ((H/2)(W/2)), ifft along y at H/2 points -> S2 (H/2 x pitch2,
+ *                      pitch2 = mc_full_spectrum_pitch(W/2); its padding columns hold nothing defined).
+ *                      Between mc_full_rows_forward(_raw) at (H, W) and mc_full_rows_inverse at (H/2, W/2).
+ *                      tw_col: the H-point table.  H and H/2 must both be column sizes above and W and W/2
+ *                      row sizes (H = 512 .. 4096 or 8184; W = 128 .. 8192 or 11520), else MC_ERR_UNSUPPORTED. */
+int mc_full_cols_crop(const void* S, void* S2, const void* tw_col, int njobs, int H, int W, int pitch, int pitch2,
+                      void* stream);
 
 /* correct_motion_fast (correct_motion.py:430-498): K3 variant multiplying spectrum
  * idx[p] by exp(-2*pi*i*(fy*sy+fx*sx)), shifts[p]=(sy,sx) px, then inverse columns. */

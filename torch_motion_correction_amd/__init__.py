@@ -16,9 +16,12 @@ from .api import (  # noqa: F401
     estimate_motion_cross_correlation_patches,
     evaluate_deformation_field,
     evaluate_deformation_field_at_t,
+    fourier_crop,
+    fourier_crop_raw,
     get_pixel_shifts,
     image_shifts_to_deformation_field,
     motion_correct_raw,
+    motion_correct_raw_binned,
     motion_correct_raw_fast,
     motion_correct_raw_patches,
     motion_correct_sum,
@@ -53,6 +56,9 @@ __all__ = [
     "motion_correct_sum_fast",
     "motion_correct_sum_fast_raw",
     "motion_correct_raw_fast",
+    "fourier_crop",
+    "fourier_crop_raw",
+    "motion_correct_raw_binned",
     "dose_weighted_sum",
     "condition_movie",
     "evaluate_deformation_field_at_t",

@@ -21,7 +21,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libmcorr.so")
 SOURCES = [("xcg_fft.hip", "xcg_fft_p3", ["-DXCG_PART=3"]), ("xcg_fft.hip", "xcg_fft_p2", ["-DXCG_PART=2"]),
            ("xcg_fft.hip", "xcg_fft_p0", ["-DXCG_PART=0"]), ("xcg_fft.hip", "xcg_fft_p1", ["-DXCG_PART=1"]),
            ("xc_fft.hip", "xc_fft", []), ("full_fft.hip", "full_fft", ["-DFULL_FFT_PART=0"]),
-           ("full_fft.hip", "full_fft_sums", ["-DFULL_FFT_PART=1"]),
+           ("full_fft.hip", "full_fft_sums", ["-DFULL_FFT_PART=1"]), ("fourier_crop.hip", "fourier_crop", []),
            # warp.hip: the SLP vectoriser turns the per-pixel coordinate chain into v_pk_* instructions fed by
            # ~1300 v_mov_b32 per kernel and 90 more VGPRs (warp_field 215 -> 160); packed fp32 issues at half
            # the scalar rate on gfx950, so nothing is gained for it

@@ -872,6 +872,148 @@ def _motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame, b_fact
     return tuple(out)
 
 
+# ------------------------------------------------------------------ Fourier cropping (2x binning)
+
+
+def _check_crop_args(shape, binning):
+    """binning 2 and even frames (ValueError), frame sizes the cropping column pass takes (NotImplementedError naming
+    them) -- all before any device is touched."""
+    if isinstance(binning, bool) or binning != 2:
+        raise ValueError(f"binning must be 2 (Fourier cropping by 2 per axis is the one factor built), got {binning!r}")
+    h, w = int(shape[-2]), int(shape[-1])
+    if h % 2 or w % 2 or h < 2 or w < 2:
+        raise ValueError(f"Fourier cropping by 2 needs frames with an even number of rows and columns, got {h} x {w}")
+    if not engine.fourier_crop_supported(h, w):
+        raise NotImplementedError(f"frames of {h} x {w}: the Fourier crop needs {engine.FOURIER_CROP_SIZES}")
+
+
+def fourier_crop(image, binning=2, device=None):
+    """Fourier cropping ("Fourier binning", MotionCor's ``-FtBin 2``) of a frame (h, w) or a stack (t, h, w), fp32 or
+    fp16, to (h/2, w/2): per frame ``irfft2(cat(F[:h/4, :w/4+1], F[h-h/4:, :w/4+1]), s=(h/2, w/2))`` of
+    ``F = rfft2(frame)`` -- the signed row frequencies -h/4 <= ky < h/4 and columns kx <= w/4, the inverse's 1 /
+    ((h/2)(w/2)) the only scale: an output pixel holds the counts of the 4 input pixels it stands for (a frame's sum
+    is kept, a mean of zero stays zero).  A super-resolution movie, or a full-size sum of any function here, comes
+    down to the detector's physical grid in one call.  Returns fp32 on ``image``'s device rule.  ``binning`` other
+    than 2 and odd sizes raise ValueError; even sizes outside heights 512 .. 4096 (powers of two) / 8184 and widths
+    128 .. 8192 (powers of two) / 11520 raise NotImplementedError (no chirp-z route, no CPU fallback)."""
+    if not isinstance(image, torch.Tensor) or image.dim() not in (2, 3):
+        raise ValueError(f"image must be (h, w) or (t, h, w), got {tuple(getattr(image, 'shape', ()))}")
+    _check_crop_args(image.shape, binning)
+    return _fourier_crop(image, device)
+
+
+@_on_gpu
+def _fourier_crop(image, device):
+    out_dev = _out_device(image, device)
+    dev = require_gpu(out_dev)
+    img = _stage(image, dev)
+    out = engine.fourier_crop(img if img.dim() == 3 else img[None])
+    return (out if img.dim() == 3 else out[0]).to(out_dev)
+
+
+def _crop_raw(raw, gd, mean_zero, thr):
+    """(binned fp32 movie, hot counts or None) of a movie on the device: u8 / i16 through one RawMovie, anything else
+    -- and a hot-pixel list overflow -- exactly condition_movie then fourier_crop."""
+    if raw.dtype in (torch.uint8, torch.int16):
+        try:
+            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
+            return engine.fourier_crop(rm), rm.hot_counts
+        except McorrUnsupported:
+            pass
+    counts = None
+    img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr, return_hot_counts=thr is not None)
+    if thr is not None:
+        img, counts = img
+    return engine.fourier_crop(img), counts
+
+
+def fourier_crop_raw(movie, gain, binning=2, mean_zero=True, hot_pixel_threshold=None, return_hot_counts=False,
+                     device=None):
+    """``fourier_crop(condition_movie(movie, gain, mean_zero, hot_pixel_threshold))`` for a RAW uint8 / int16 movie
+    without the full-size fp32 movie: the row transform reads the raw bytes and forms ``raw * gain - frame mean`` as
+    condition_movie rounds it, and the hot pixels enter the spectra as sparse corrections (engine.RawMovie).  Without
+    hot pixels the result is bit for bit that of the composition.  Returns the (t, h/2, w/2) fp32 movie, with
+    ``return_hot_counts`` also the (t,) int32 hot pixels per frame (zeros without a threshold).  fp16 / fp32 movies
+    and a hot-pixel list overflow take exactly condition_movie followed by fourier_crop.  Argument rules as
+    ``fourier_crop``."""
+    thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # every argument rule before any device
+    _check_raw_args(movie, gain)
+    _check_crop_args(movie.shape, binning)
+    return _fourier_crop_raw(movie, gain, mean_zero, thr, bool(return_hot_counts), device)
+
+
+@_on_gpu
+def _fourier_crop_raw(movie, gain, mean_zero, thr, want_counts, device):
+    out_dev = _out_device(movie, device)
+    dev = require_gpu(out_dev)
+    binned, counts = _crop_raw(movie.detach().to(dev), None if gain is None else gain.to(dev), mean_zero, thr)
+    if not want_counts:
+        return binned.to(out_dev)
+    t = movie.shape[0]
+    return binned.to(out_dev), (torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None
+                                else counts.to(out_dev))
+
+
+def motion_correct_raw_binned(movie, gain, pixel_spacing, binning=2, patch_sidelength=None, reference_frame=None,
+                              b_factor=500, frequency_range=(300, 10), grid_type="catmull_rom", mean_zero=True,
+                              hot_pixel_threshold=None, dose_per_frame=None, pre_exposure=0.0, voltage=300.0,
+                              return_plain_sum=False, return_hot_counts=False, device=None):
+    """A super-resolution session's first step as one call: ``fourier_crop_raw`` to the detector's physical grid,
+    then the estimate and the aligned sum THERE.  ``pixel_spacing`` is that of the input movie; everything after the
+    crop runs at ``binning * pixel_spacing`` and the returned field (Angstrom) and sums (h/2, w/2) belong to the
+    binned movie.  With ``binned = fourier_crop_raw(movie, gain, binning, mean_zero, hot_pixel_threshold)`` and
+    ``ps = binning * pixel_spacing`` the result is, bit for bit,
+
+    * ``patch_sidelength=None``: ``field = estimate_global_motion(binned, ps, reference_frame, b_factor,
+      frequency_range)`` and ``motion_correct_sum_fast(binned, field, ps, dose_per_frame, pre_exposure, voltage,
+      return_plain_sum)`` -> ``(field, sum[, plain sum])``, as ``motion_correct_raw_fast`` returns them;
+    * with a ``patch_sidelength`` (pixels of the binned movie): ``field, centres =
+      estimate_motion_cross_correlation_patches(binned, ps, reference_frame, b_factor=b_factor,
+      frequency_range=frequency_range, patch_sidelength=patch_sidelength)`` and ``motion_correct_sum(binned, field,
+      ps, grid_type, dose_per_frame=..., pre_exposure=..., voltage=...)`` -> ``(field, centres, sum)``;
+      ``return_plain_sum`` belongs to the whole-image route only.
+
+    ``return_hot_counts`` appends the (t,) int32 hot pixels per frame.  Argument rules as ``fourier_crop_raw``."""
+    dose = _check_fast_sum_args(dose_per_frame, return_plain_sum)  # every argument rule before any device
+    thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)
+    _check_raw_args(movie, gain)
+    _check_crop_args(movie.shape, binning)
+    if patch_sidelength is not None:
+        if not int(patch_sidelength) > 0:
+            raise ValueError(f"patch_sidelength must be > 0, got {patch_sidelength!r}")
+        if return_plain_sum:
+            raise ValueError("return_plain_sum belongs to the whole-image route (patch_sidelength=None)")
+    return _motion_correct_raw_binned(movie, gain, pixel_spacing, binning, patch_sidelength, reference_frame, b_factor,
+                                      frequency_range, grid_type, mean_zero, thr, dose, pre_exposure, voltage,
+                                      bool(return_plain_sum), bool(return_hot_counts), device)
+
+
+@_on_gpu
+def _motion_correct_raw_binned(movie, gain, pixel_spacing, binning, patch_sidelength, reference_frame, b_factor,
+                               frequency_range, grid_type, mean_zero, thr, dose, pre_exposure, voltage, want_plain,
+                               want_counts, device):
+    out_dev = _out_device(movie, device)
+    dev = require_gpu(out_dev)
+    binned, counts = _crop_raw(movie.detach().to(dev), None if gain is None else gain.to(dev), mean_zero, thr)
+    ps = binning * float(pixel_spacing)
+    # the public functions themselves on the device-resident binned movie: the composition by construction
+    if patch_sidelength is None:
+        field = estimate_global_motion(binned, ps, reference_frame=reference_frame, b_factor=b_factor,
+                                       frequency_range=frequency_range)
+        sums = motion_correct_sum_fast(binned, field, ps, dose_per_frame=dose, pre_exposure=pre_exposure,
+                                       voltage=voltage, return_plain_sum=want_plain)
+        out = [field, *(sums if want_plain else (sums,))]
+    else:
+        field, centers = estimate_motion_cross_correlation_patches(
+            binned, ps, reference_frame=reference_frame, b_factor=b_factor, frequency_range=frequency_range,
+            patch_sidelength=int(patch_sidelength))
+        out = [field, centers, motion_correct_sum(binned, field, ps, grid_type=grid_type, dose_per_frame=dose,
+                                                  pre_exposure=pre_exposure, voltage=voltage)]
+    if want_counts:
+        out.append(torch.zeros(movie.shape[0], dtype=torch.int32, device=dev) if counts is None else counts)
+    return tuple(x.to(out_dev) for x in out)
+
+
 @_on_gpu
 def get_pixel_shifts(frame, pixel_spacing, frame_deformation_grid, pixel_grid=None):
     """(h,w,2) per-pixel shifts in px from a (2,G_h,G_w) Angstrom lattice

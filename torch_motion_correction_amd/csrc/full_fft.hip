@@ -26,6 +26,7 @@
 // columns of H = 256 .. 4096 (powers of two), 4092 and 8184 rows (2^a 3 11 31: radix-31 and radix-11
 // passes, mc_fft.h) -- the K3 detector's two frame formats (BASELINE configs 3 and 5) run here
 // without chirp-z.  Columns of more than 4096 rows go one column per workgroup (NC = 1).
+#include "full_cols.h"
 #include "mc_fft.h"
 #include "mcorr.h"
 
@@ -43,30 +44,6 @@
 #else
 #define FULL_FFT_SUMS 0
 #endif
-
-// blockIdx.x -> column pair: the 8 pairs of one 128-byte line group on one XCD, consecutively
-// (single columns, NC = 1: the same with 16 columns per group -- npairs is then the column count / 2
-// and the caller maps block b to column 2 * full_pair_of_block(b >> 1, ..) + (b & 1))
-__device__ __forceinline__ int full_pair_of_block(int b, int npairs) {
-  const int ngroups = (npairs + 7) / 8;
-  if (ngroups < 8) return b;  // tiny widths: no mapping
-  const int xcd = b & 7, i = b >> 3;
-  const int grp = i >> 3, within = i & 7;
-  const int G = grp * 8 + xcd;
-  // groups beyond the last multiple of 8 keep the plain order
-  const int full = (ngroups / 8) * 8;
-  if (b >= full * 8) return b;
-  return G * 8 + within;
-}
-
-// The lane index, made opaque: every transform of a kernel derives its addresses and twiddle indices
-// from its own copy, so the compiler cannot keep one transform's twiddles and addresses alive for the
-// next (common-subexpression elimination across the unrolled column / direction loops cost 380
-// registers for a 4092-point column pair).
-__device__ __forceinline__ int full_opaque(int t) {
-  asm volatile("" : "+v"(t));
-  return t;
-}
 
 template <int N>
 __global__ __launch_bounds__(MC_WG) void full_rows_fwd(const float* __restrict__ src,
@@ -145,60 +122,6 @@ __global__ __launch_bounds__(MC_WG) void full_rows_inv(const cfloat* __restrict_
 __device__ __forceinline__ float full_fy(int ky, int H) {
   const int kk = (ky < (H + 1) / 2) ? ky : ky - H;
   return (float)kk * (float)(1.0 / (double)H);
-}
-
-// first column of workgroup b (NC columns per workgroup), ncols = pitch
-template <int NC>
-__device__ __forceinline__ int full_col_of_block(int b, int pitch) {
-  if constexpr (NC == 2) return 2 * full_pair_of_block(b, pitch / 2);
-  else return 2 * full_pair_of_block(b >> 1, pitch / 2) + (b & 1);
-}
-
-// stage NC adjacent columns of S (rows `pitch` apart) into NC LDS lines / write them back.  All of a
-// thread's loads are issued before the first LDS write (a rolled loop waits for every load in turn:
-// H / WG memory round trips per column instead of one).
-template <int H, int NC, int WG>
-__device__ __forceinline__ void full_cols_load(cfloat* const* lines, const cfloat* base, int64_t pitch, int tid) {
-  constexpr int IT = (H + WG - 1) / WG;
-  if constexpr (NC == 2) {
-    float4 v[IT];
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int i = tid + it * WG;
-      if (i < H) v[it] = *reinterpret_cast<const float4*>(base + (int64_t)i * pitch);
-    }
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int i = tid + it * WG;
-      if (i < H) {
-        lines[0][lpad(i)] = cmake(v[it].x, v[it].y);
-        lines[1][lpad(i)] = cmake(v[it].z, v[it].w);
-      }
-    }
-  } else {
-    cfloat v[IT];
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int i = tid + it * WG;
-      if (i < H) v[it] = base[(int64_t)i * pitch];
-    }
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int i = tid + it * WG;
-      if (i < H) lines[0][lpad(i)] = v[it];
-    }
-  }
-}
-template <int H, int NC, int WG>
-__device__ __forceinline__ void full_cols_store(cfloat* const* lines, cfloat* base, int pitch, int tid) {
-  for (int i = tid; i < H; i += WG) {
-    if constexpr (NC == 2) {
-      const cfloat a = lines[0][lpad(i)], b = lines[1][lpad(i)];
-      *reinterpret_cast<float4*>(base + (int64_t)i * pitch) = make_float4(a.x, a.y, b.x, b.y);
-    } else {
-      base[(int64_t)i * pitch] = lines[0][lpad(i)];
-    }
-  }
 }
 
 template <int H, int NC, int WG>
@@ -347,16 +270,9 @@ __global__ __launch_bounds__(256) void full_transpose(const cfloat* __restrict__
 
 #endif  // FULL_FFT_BASE
 
-static bool full_rows_ok(int W) {
-  return (mc_is_pow2(W) && W >= 64 && W <= 8192) || W == 5760 || W == 11520;
-}
-static bool full_cols_ok(int H) { return (mc_is_pow2(H) && H >= 256 && H <= 4096) || H == 4092 || H == 8184; }
 static bool full_sizes_ok(int H, int W, int pitch) {
   return full_rows_ok(W) && full_cols_ok(H) && pitch >= W / 2 + 1 && (pitch % 16) == 0;
 }
-
-#define MC_FULL_SET_LDS(k, bytes) \
-  (void)hipFuncSetAttribute((const void*)(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
 
 #define MC_FULL_CASE(V, ...) \
   case V: {                  \
@@ -379,12 +295,6 @@ static bool full_sizes_ok(int H, int W, int pitch) {
     MC_FULL_CASE(2048, __VA_ARGS__) MC_FULL_CASE(4092, __VA_ARGS__) MC_FULL_CASE(8184, __VA_ARGS__) \
     default: return MC_ERR_UNSUPPORTED;                                                            \
   }
-// columns per workgroup: pairs while two lines fit twice into a CU's LDS, single columns above;
-// threads per workgroup: 512 for 8184 rows (264 radix-31 butterflies per column)
-template <int H>
-constexpr int full_nc() { return H > 4096 ? 1 : 2; }
-template <int H>
-constexpr int full_wg() { return H > 4096 ? 512 : MC_WG; }
 
 #if FULL_FFT_BASE
 extern "C" {

@@ -1259,6 +1259,23 @@ def warp_dose_weighted_sum_raw(rm: RawMovie, lattices, pixel_spacing, rigid, dos
     return dw, plain
 
 
+def _raw_rows_forward(rm, first, n, S):
+    """_rows_forward for a RawMovie: the row transforms of frames first .. first+n-1 from the raw bytes of their
+    frame window (mc_full_rows_forward_raw), then the window's hot pixels as sparse corrections of the spectra
+    (mc_full_rows_hot_correct).  One sequence for every consumer of a raw movie's row-major spectra."""
+    lib = _lib.load()
+    _, h, w = rm.shape
+    dev = rm.raw.device
+    win, pitch, st = rm.window(first, n), S.shape[2], stream_ptr(dev)
+    off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
+    check(lib.mc_full_rows_forward_raw(ptr(win.raw), win.kind, ptr(win.gain), ptr(win.mu), ptr(off), ptr(S),
+                                       ptr(planmod.get_twiddles(w, dev)), n, h, w, pitch, st),
+          "mc_full_rows_forward_raw")
+    if win.n_hot:
+        check(lib.mc_full_rows_hot_correct(ptr(win.hot_keys), ptr(win.hot_rv), win.n_hot, 0, n, h, w, ptr(S),
+                                           pitch, st), "mc_full_rows_hot_correct")
+
+
 def fast_shifts(grid_px):
     """The (t, 2) fp32 shifts (sy, sx) the Fourier-shift routes apply for a rigid (2, t, 1, 1) field in pixels: the
     field negated, as correct_motion_fast forms them (correct_motion.py:473-476).  One helper for the fused sums of
@@ -1282,20 +1299,54 @@ def fast_shift_sums(src, shifts, pixel_spacing=1.0, dose_per_frame=None, pre_exp
         raise _lib.McorrUnsupported(f"no fused Fourier-shift sums for frames of {h} x {w}")
     dev = src.raw.device if raw else src.device
 
-    def raw_rows(a, n, S):
-        lib = _lib.load()
-        win, pitch, st = src.window(a, n), S.shape[2], stream_ptr(dev)
-        off = torch.arange(n, device=dev, dtype=torch.int64) * (h * w)
-        check(lib.mc_full_rows_forward_raw(ptr(win.raw), win.kind, ptr(win.gain), ptr(win.mu), ptr(off), ptr(S),
-                                           ptr(planmod.get_twiddles(w, dev)), n, h, w, pitch, st),
-              "mc_full_rows_forward_raw")
-        if win.n_hot:
-            check(lib.mc_full_rows_hot_correct(ptr(win.hot_keys), ptr(win.hot_rv), win.n_hot, 0, n, h, w, ptr(S),
-                                               pitch, st), "mc_full_rows_hot_correct")
-
-    forward_rows = raw_rows if raw else (lambda a, n, S: _rows_forward(src, a, n, S))
+    forward_rows = (lambda a, n, S: _raw_rows_forward(src, a, n, S)) if raw else (
+        lambda a, n, S: _rows_forward(src, a, n, S))
     return _row_major_sums(src.shape, dev, forward_rows, shifts.to(dev, torch.float32).contiguous(), pixel_spacing,
                            dose_per_frame, pre_exposure, voltage, want_plain=want_plain or dose_per_frame is None)
+
+
+FOURIER_CROP_SIZES = ("heights 512, 1024, 2048, 4096 and 8184 and widths 128, 256, ..., 8192 and 11520 "
+                      "(any combination)")
+
+
+def fourier_crop_supported(h, w):
+    """Frames mc_full_cols_crop bins by 2: (h, w) and (h/2, w/2) both sizes of the row-major transforms."""
+    pow2 = lambda n: n > 0 and (n & (n - 1)) == 0
+    return ((pow2(h) and 512 <= h <= 4096) or h == 8184) and ((pow2(w) and 128 <= w <= 8192) or w == 11520)
+
+
+def fourier_crop(src):
+    """Fourier cropping by 2 per axis: per frame irfft2 of the rows -h/4 <= ky < h/4 and columns kx <= w/4 of
+    rfft2(frame), at (h/2, w/2), the frame's sum kept (scale 1 / ((h/2)(w/2))).  `src`: an fp32 (t, h, w) tensor, or
+    a RawMovie, whose chunks are transformed from the raw bytes (_raw_rows_forward: no fp32 movie).  Per chunk of
+    frames (the WORKSPACE_BYTES rule over the spectrum and its cropped copy): rows forward at (h, w) ->
+    mc_full_cols_crop -> rows inverse at (h/2, w/2) straight into the (t, h/2, w/2) fp32 result.  Raises
+    McorrUnsupported for other shapes, before any launch."""
+    raw = isinstance(src, RawMovie)
+    t, h, w = src.shape
+    if not fourier_crop_supported(h, w):
+        raise _lib.McorrUnsupported(f"no Fourier crop for frames of {h} x {w}: it takes {FOURIER_CROP_SIZES}")
+    lib = _lib.load()
+    dev = src.raw.device if raw else src.device
+    h2, w2 = h // 2, w // 2
+    pitch, pitch2 = lib.mc_full_spectrum_pitch(w), lib.mc_full_spectrum_pitch(w2)
+    tw_col, tw_row2 = planmod.get_twiddles(h, dev), planmod.get_twiddles(w2, dev)
+    out = torch.empty((t, h2, w2), dtype=torch.float32, device=dev)
+    chunk = max(1, min(t, WORKSPACE_BYTES // ((h * pitch + h2 * pitch2) * 8)))
+    S = torch.empty((chunk, h, pitch, 2), dtype=torch.float32, device=dev)
+    S2 = torch.empty((chunk, h2, pitch2, 2), dtype=torch.float32, device=dev)
+    st = stream_ptr(dev)
+    for a in range(0, t, chunk):
+        n = min(chunk, t - a)
+        if raw:
+            _raw_rows_forward(src, a, n, S)
+        else:
+            _rows_forward(src, a, n, S)
+        check(lib.mc_full_cols_crop(ptr(S), ptr(S2), ptr(tw_col), n, h, w, pitch, pitch2, st), "mc_full_cols_crop")
+        off = torch.arange(a, a + n, device=dev, dtype=torch.int64) * (h2 * w2)
+        check(lib.mc_full_rows_inverse(ptr(S2), ptr(out), ptr(off), w2, ptr(tw_row2), n, h2, w2, pitch2, st),
+              "mc_full_rows_inverse")
+    return out
 
 
 _HOT_NONE = (1 << 63) - 1
