@@ -1652,23 +1652,59 @@ def test_fp16_statistics_and_patch_rows_read_natively(mc, dev):
     assert torch.equal(a, b)
 
 
+# mc_warp_frames_t reads fp16 frames in warp_field3 only, i.e. for w % 8 == 0 and 64 (GH - 1) <= 3 (h - 1) with
+# GH = 10 gh lattice rows: the last two (shape, field grid) below; everything else is widened by engine.warp
+_FP16_NATIVE = {((3, 416, 520), (2, 2)), ((3, 200, 264), (1, 2))}
+
+
 @pytest.mark.parametrize("shape,grid,ps", [((4, 300, 520), (3, 4), 1.0), ((3, 200, 264), (2, 2), 0.83),
-                                           ((3, 130, 96), (2, 3), 1.0), ((2, 100, 101), (2, 2), 1.0)])
-def test_fp16_frames_through_the_field_warp(mc, dev, shape, grid, ps):
-    """The deformation-field warp on fp16 frames (window DMA'd as fp16, widened in LDS; borders,
-    edge tiles, non-unit spacing; a row length that is not a multiple of 8 falls back to a widened
-    copy) == the warp of the fp32 up-cast, frames and sum, bit for bit."""
+                                           ((3, 130, 96), (2, 3), 1.0), ((2, 100, 101), (2, 2), 1.0),
+                                           ((3, 416, 520), (2, 2), 1.0), ((3, 200, 264), (1, 2), 0.83)])
+def test_fp16_frames_through_the_field_warp(mc, dev, shape, grid, ps, monkeypatch):
+    """The deformation-field warp on fp16 frames == the warp of the fp32 up-cast, frames and sum, bit for bit.
+    native: the shape is one warp_field3<HALF> reads (window DMA'd as fp16, widened in LDS; borders, edge tiles,
+    non-unit spacing) -- the widening fallback entry mc_warp_frames is never called; the other shapes (a dense
+    lattice for the frame height, a row length that is not a multiple of 8) pin that fallback: every fp16 warp goes
+    through it.  (The fp16 kernel against an independent float64 reference: tests/test_field_kernels_float64.py.)"""
+    from field_reference import route_of, tile_plan
+    from torch_motion_correction_amd import _lib, engine
+
     t, h, w = shape
+    native = (shape, grid) in _FP16_NATIVE
+    assert (route_of(h, w, 10 * grid[0], "f16") == "warp_field3") == native
+    lib = _lib.load()
+    fallback = lib.mc_warp_frames
+    calls = []
+
+    def counted(*a):
+        calls.append(a)
+        return fallback(*a)
+
+    monkeypatch.setattr(lib, "mc_warp_frames", counted)
     g = torch.Generator().manual_seed(h + w)
     st16 = (torch.randn(t, h, w, generator=g) * 2 + 1).half().to(dev)
     field = (torch.randn(2, t, *grid, generator=g) * 1.5).to(dev)
     for gt in ("bspline", "catmull_rom"):
+        n = len(calls)
         sa, fa = mc.motion_correct_sum(st16, field, ps, grid_type=gt, return_frames=True)
+        assert len(calls) - n == (0 if native else 1)
         sb, fb = mc.motion_correct_sum(st16.float(), field, ps, grid_type=gt, return_frames=True)
+        assert len(calls) - n == (0 if native else 1)  # fp32 stacks never take the fallback entry
         assert fa.dtype == torch.float32 and torch.equal(fa, fb) and torch.equal(sa, sb)
-    # rough field: some tile-frames fail the regularity test and take the generic kernel
-    rough = (torch.randn(2, t, 6, 6, generator=g) * 6).to(dev)
+    # rough field: some tile-frames fail the regularity test and take the generic kernel (native shapes: a field on
+    # the shape's own grid, so that the lattice stays sparse and warp_field_slow<HALF> runs -- asserted from the
+    # plan rule; the other shapes: any rough field, through the fallback)
+    if native:  # a calm first frame, then rougher ones: regular and irregular tile-frames on the same tiles
+        rough = (torch.randn(2, t, *grid, generator=g) * torch.tensor([0.5, 8.0, 30.0]).view(1, 3, 1, 1)).to(dev)
+    else:
+        rough = (torch.randn(2, t, 6, 6, generator=g) * 6).to(dev)
+    if native:
+        lat = engine.frame_lattices(rough.contiguous(), t, "bspline").cpu().numpy()
+        irregular = tile_plan(lat, h, w, ps)[0] == 0
+        assert irregular.any() and not irregular.all()
+    n = len(calls)
     fa = mc.correct_motion(st16, rough, ps, grid_type="bspline")
+    assert len(calls) - n == (0 if native else 1)
     fb = mc.correct_motion(st16.float(), rough, ps, grid_type="bspline")
     assert torch.equal(fa, fb)
     # and against the oracle on the up-cast (SURVEY Q11)
