@@ -306,6 +306,26 @@ int mc_xc_ref_mean_except_current(const void* U, const void* V, const int* sched
                                   const int* sched_idx, const uint8_t* sched_rebuild, void* REF,
                                   int t, int npatch, int64_t len, float inv_count, void* stream);
 
+/* Iterative sub-pixel whole-frame alignment (refine_global_motion; no counterpart in the reference tree, whose
+ * example calls a refine_alignment it never shipped, examples/ttMotion.py:264-285).  One iteration on the filtered
+ * spectra S ([t][nkx][nky] complex, as K2 writes them) with the current shifts_px ([t][2] px, (y, x)):
+ *   G_f = S_f exp(+2 pi i (fy[ky] sy_f + fx[kx] sx_f))   (fy, fx: the kept bins' signed frequencies in cycles/px, the
+ *   convention of mc_local_loss_sums; the ramp correct_motion_fast applies for the field s),
+ *   A = sum_f G_f,   REF[f] = (A - G_f) / (t - 1)   (zero for t == 1),
+ *   G[f] = G_f exp(-2 pi i under_px (fy + fx)): the aligned frame UNDER-corrected by under_px pixels on both axes, so
+ *   that the correlation map of (cur = G, ref = REF) is the true one translated circularly by (under_px, under_px)
+ *   and a converged peak lies inside the map, where mc_xc_peak_neighbourhood has values (0: G = G_f).
+ * 1 <= t <= 512.  Follow with K3/K4/K6 on (G, REF) and mc_xc_refine_update. */
+int mc_xc_aligned_refs(const void* S, const float* shifts_px, const float* fy, const float* fx, void* G, void* REF,
+                       int t, int nkx, int nky, int under_px, void* stream);
+/* The rest of the iteration, one small workgroup: for every frame f the residual r_f = (peak - under_px) mod (H, W)
+ * after the wrap-around rule `p if p <= n//2 else p-n`, plus the parabola offsets of estimate_motion_xc.py:465-481
+ * from nb ([t][3][3], its `!=` guards; an axis whose outer samples are NaN -- a peak on the border of the translated
+ * map -- keeps its integer residual); shifts_px[f] += (t-1)/t r_f, then shifts_px -= shifts_px[ref] with row `ref`
+ * exactly 0; *max_r = max_f max(|r_y|, |r_x|).  2 <= t <= 512. */
+int mc_xc_refine_update(const int* peaks, const float* nb, float* shifts_px, int ref, int t, int H, int W,
+                        int under_px, float* max_r, void* stream);
+
 /* ---- a11/a12/a13: per-frame shift post-processing ------------------------------- */
 /* Sub-pixel parabola (rules Q4/Q5), wrap-around, outlier rejection
  * (estimate_motion_xc.py:538-627) and accumulation into field (2,t,gh,gw) [Angstrom]

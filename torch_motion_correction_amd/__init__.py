@@ -28,6 +28,8 @@ from .api import (  # noqa: F401
     motion_correct_sum_fast,
     motion_correct_sum_fast_raw,
     motion_correct_sum_raw,
+    refine_global_motion,
+    refine_global_motion_raw,
     resample_deformation_field,
 )
 from ._lib import McorrError  # noqa: F401
@@ -44,6 +46,8 @@ __all__ = [
     "get_pixel_shifts",
     "evaluate_deformation_field",
     "estimate_global_motion",
+    "refine_global_motion",
+    "refine_global_motion_raw",
     "estimate_motion_cross_correlation_patches",
     "estimate_local_motion",
     "OptimizationState",

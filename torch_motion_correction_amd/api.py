@@ -141,6 +141,111 @@ def estimate_global_motion(image, pixel_spacing, reference_frame=None, b_factor=
     return image_shifts_to_deformation_field(shifts, pixel_spacing).to(out_dev)
 
 
+def _check_refine_call(t, reference_frame, max_iterations, convergence_threshold):
+    """The refinement's own argument rules, before any device is touched -> (reference frame, iterations, threshold)."""
+    n_iter, thr = engine.check_refine_args(max_iterations, convergence_threshold)
+    ref = t // 2 if reference_frame is None else reference_frame
+    normalize_frame_index(ref, t)  # IndexError outside [-t, t)
+    if t > engine.REFINE_MAX_FRAMES:
+        raise NotImplementedError(f"{t} frames: the refinement takes at most {engine.REFINE_MAX_FRAMES}")
+    return ref, n_iter, thr
+
+
+def refine_global_motion(image, pixel_spacing, deformation_field=None, reference_frame=None, b_factor=500,
+                         frequency_range=(300, 10), max_iterations=10, convergence_threshold=0.01,
+                         return_history=False, device=None):
+    """Iterative sub-pixel whole-frame alignment (the unblur / MotionCor2 scheme; the reference's example calls such a
+    ``refine_alignment`` that the package never shipped, examples/ttMotion.py:264-285): every frame is aligned, to
+    sub-pixel precision, against the sum of the OTHER aligned frames, until the shifts stop moving.  `image`: an fp32
+    or fp16 (t, h, w) stack.  Returns the (2,t,1,1) float32 field in Angstrom, as ``estimate_global_motion`` does;
+    the reference frame's entry is exactly 0.
+
+    Start: ``estimate_global_motion``'s integer shifts, or a caller's rigid (2,t,1,1) `deformation_field` (Angstrom).
+    Per iteration, on the masked, filtered spectra of ``estimate_global_motion`` (transformed once, no frame is read
+    again): each frame's spectrum gets the phase ramp ``correct_motion_fast`` applies for the current shifts, is
+    correlated with the mean of the others, and the residual -- the first maximum with the wrap-around rule plus the
+    parabola offsets of the patch estimator's sub-pixel step, the three samples per axis taken circularly -- is added
+    with the factor (t-1)/t (the frame's error against the mean of the others overstates it by t/(t-1)); then the
+    reference frame's shift is subtracted from all.  The loop stops after the iteration whose largest residual is
+    below `convergence_threshold` pixels (0: never), at the latest after `max_iterations`.  ``return_history=True``
+    also returns the per-iteration largest residual as a CPU float tensor.  One frame returns zeros.
+
+    `reference_frame` follows Python indexing (None: t // 2; outside [-t, t): IndexError).  Argument errors are
+    raised before any device is touched.  At most 512 frames."""
+    if not isinstance(image, torch.Tensor) or image.dim() != 3:
+        raise ValueError(f"image must be (t, h, w), got {tuple(getattr(image, 'shape', ()))}")
+    t = image.shape[0]
+    ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations, convergence_threshold)
+    if deformation_field is not None:
+        _check_fast_field(deformation_field, t)
+    return _refine_global_motion(image, pixel_spacing, deformation_field, ref, b_factor, frequency_range, n_iter, thr,
+                                 bool(return_history), device)
+
+
+def _start_shifts(deformation_field, ps, dev):
+    """(t, 2) px start shifts of the refinement from a rigid (2,t,1,1) Angstrom field, or None."""
+    if deformation_field is None:
+        return None
+    return (deformation_field.detach().to(device=dev, dtype=torch.float32)[:, :, 0, 0].transpose(0, 1) / ps).contiguous()
+
+
+@_on_gpu
+def _refine_global_motion(image, pixel_spacing, deformation_field, ref, b_factor, frequency_range, n_iter, thr,
+                          want_history, device):
+    out_dev = _out_device(image, device)
+    dev = require_gpu(out_dev)
+    img = _stage(image, dev, keep_half=True)
+    ps = float(pixel_spacing)
+    shifts, hist = engine.global_shifts_refined(img, ref, ps, float(b_factor), tuple(frequency_range),
+                                                _start_shifts(deformation_field, ps, dev), n_iter, thr)
+    field = image_shifts_to_deformation_field(shifts, pixel_spacing).to(out_dev)
+    return (field, hist) if want_history else field
+
+
+def refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field=None, reference_frame=None, b_factor=500,
+                             frequency_range=(300, 10), mean_zero=True, hot_pixel_threshold=None, max_iterations=10,
+                             convergence_threshold=0.01, return_history=False, device=None):
+    """``refine_global_motion(condition_movie(movie, gain, mean_zero, hot_pixel_threshold), ...)`` for a RAW uint8 /
+    int16 movie without the conditioned fp32 movie: the spectra are those ``motion_correct_raw`` and
+    ``motion_correct_raw_fast`` estimate on (the row transform reads the raw bytes, hot pixels enter as sparse
+    corrections, engine.RawMovie), and the iterations only touch those spectra.  Returns the (2,t,1,1) Angstrom
+    field (and the history); feed it to ``motion_correct_sum_fast_raw`` or ``motion_correct_sum_raw`` for the sums,
+    again without an fp32 movie.  fp16 / fp32 movies, shapes without the fused kernels and a hot-pixel list overflow
+    take exactly condition_movie followed by refine_global_motion."""
+    thr_hot = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # every argument rule before any device
+    _check_raw_args(movie, gain)
+    t = movie.shape[0]
+    ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations, convergence_threshold)
+    if deformation_field is not None:
+        _check_fast_field(deformation_field, t)
+    return _refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field, ref, b_factor, frequency_range,
+                                     mean_zero, thr_hot, n_iter, thr, bool(return_history), device)
+
+
+@_on_gpu
+def _refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field, ref, b_factor, frequency_range, mean_zero,
+                              thr_hot, n_iter, thr, want_history, device):
+    out_dev = _out_device(movie, device)
+    dev = require_gpu(out_dev)
+    raw = movie.detach().to(dev)
+    ps = float(pixel_spacing)
+    gd = None if gain is None else gain.to(dev)
+    start = _start_shifts(deformation_field, ps, dev)
+    res = None
+    if raw.dtype in (torch.uint8, torch.int16):
+        try:
+            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr_hot)
+            res = engine.global_shifts_raw_refined(rm, ref, ps, float(b_factor), tuple(frequency_range), start, n_iter,
+                                                   thr)
+        except McorrUnsupported:
+            res = None
+    if res is None:  # exactly condition_movie, then refine_global_motion
+        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr_hot)
+        res = engine.global_shifts_refined(img, ref, ps, float(b_factor), tuple(frequency_range), start, n_iter, thr)
+    field = image_shifts_to_deformation_field(res[0], pixel_spacing).to(out_dev)
+    return (field, res[1]) if want_history else field
+
+
 @_on_gpu
 def estimate_motion_cross_correlation_patches(
     image, pixel_spacing, reference_frame=None, reference_strategy="mean_except_current",

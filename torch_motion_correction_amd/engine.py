@@ -340,6 +340,106 @@ def _shifts_from_spectra(S, t, reference_frame, pl):
     return shifts
 
 
+# ------------------------------------------------------------------ iterative sub-pixel refinement
+
+
+REFINE_MAX_FRAMES = 512  # mc_xc_aligned_refs / mc_xc_refine_update
+
+
+def check_refine_args(max_iterations, threshold, what=("max_iterations", "convergence_threshold"), min_iterations=1):
+    """(iterations, threshold) of the refinement as (int, float); ValueError otherwise (before any device is
+    touched): a whole number of iterations >= `min_iterations`, a finite threshold >= 0 (0 = never stop early)."""
+    import operator
+
+    try:
+        if isinstance(max_iterations, bool):
+            raise TypeError
+        n = operator.index(max_iterations)
+    except TypeError:
+        raise ValueError(f"{what[0]} must be an integer >= {min_iterations}, got {max_iterations!r}") from None
+    if n < min_iterations:
+        raise ValueError(f"{what[0]} must be an integer >= {min_iterations}, got {max_iterations!r}")
+    try:
+        thr = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what[1]} must be a finite number >= 0, got {threshold!r}") from None
+    if not (math.isfinite(thr) and thr >= 0.0):
+        raise ValueError(f"{what[1]} must be a finite number >= 0, got {threshold!r}")
+    return n, thr
+
+
+def refine_under_px(h, w):
+    """The whole-pixel under-correction of the refinement's `cur` spectra (mc_xc_aligned_refs): the correlation map is
+    translated by (c, c), so a converged peak lies at (c, c) instead of (0, 0) and its 3 x 3 neighbourhood inside the
+    map.  16 lies inside the 64 rows per end the near-window search of 1024-row and taller maps visits; small frames
+    take a quarter of their shorter side."""
+    return max(1, min(16, h // 4, w // 4))
+
+
+def _kept_frequencies(pl, dev):
+    """(fy (nky,), fx (nkx,)): signed frequencies of the plan's kept bins in cycles/pixel, as LocalMotionProblem
+    forms them for mc_local_loss_sums."""
+    g = pl.geom
+
+    def build():
+        rows = np.concatenate([np.arange(g.kyp), np.arange(g.H - g.kyn, g.H)])
+        kk = np.where(rows < (g.H + 1) // 2, rows, rows - g.H).astype(np.float32)
+        fy = torch.from_numpy(kk * np.float32(1.0 / g.H)).to(dev)
+        fx = torch.from_numpy(np.arange(g.nkx).astype(np.float32) * np.float32(1.0 / g.W)).to(dev)
+        return fy, fx
+
+    return _cached(("kept_freqs", str(dev), g.H, g.W, g.nkx, g.kyp, g.kyn), build)
+
+
+def refine_shifts_from_spectra(S, t, reference_frame, pl, start=None, max_iterations=10, threshold=0.01):
+    """Iterative sub-pixel alignment on the filtered spectra S (t, nkx, nky, 2) of the global estimate: every frame
+    against the mean of the OTHER aligned frames, until the shifts stop moving (csrc/xc_refine.hip has the
+    definition).  `start`: (t, 2) px shifts, default the integer estimate against `reference_frame`
+    (_shifts_from_spectra).  Per iteration: mc_xc_aligned_refs, K3/K4/K6 (_peaks with cur = G, ref = REF) and
+    mc_xc_refine_update; no frame is read again.  Stops after the iteration whose max |r| is below `threshold` px
+    (one host read of max |r| per iteration; none with threshold 0), at the latest after `max_iterations`.
+    Returns ((t, 2) fp32 px shifts, the reference frame's row exactly 0; per-iteration max |r| as a CPU float
+    tensor)."""
+    lib = _lib.load()
+    dev = S.device
+    ref = _lib.normalize_frame_index(reference_frame, t)
+    if t > REFINE_MAX_FRAMES:
+        raise NotImplementedError(f"{t} frames: the refinement kernels take at most {REFINE_MAX_FRAMES}")
+    if t == 1:
+        return torch.zeros((1, 2), dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.float32)
+    shifts = (_shifts_from_spectra(S, t, reference_frame, pl) if start is None
+              else start.detach().to(device=dev, dtype=torch.float32)).contiguous().clone()
+    g = pl.geom
+    fy, fx = _kept_frequencies(pl, dev)
+    under = refine_under_px(g.H, g.W)
+    G, REF = torch.empty_like(S), torch.empty_like(S)
+    idx = _cached(("refine_pairs", str(dev), t), lambda: torch.arange(t, device=dev, dtype=torch.int32))
+    hist = torch.zeros(max_iterations, dtype=torch.float32, device=dev)
+    st = stream_ptr(dev)
+    done = 0
+    for k in range(max_iterations):
+        check(lib.mc_xc_aligned_refs(ptr(S), ptr(shifts), ptr(fy), ptr(fx), ptr(G), ptr(REF), t, g.nkx, g.nky, under,
+                                     st), "mc_xc_aligned_refs")
+        peaks, _, nb = _peaks(G, idx, REF, idx, pl, want_nbhd=True)
+        check(lib.mc_xc_refine_update(ptr(peaks), ptr(nb), ptr(shifts), ref, t, g.H, g.W, under, ptr(hist[k:k + 1]),
+                                      st), "mc_xc_refine_update")
+        done = k + 1
+        if threshold > 0.0 and float(hist[k]) < threshold:
+            break
+    return shifts, hist[:done].cpu()
+
+
+def global_shifts_refined(img, reference_frame, pixel_spacing, b_factor, frequency_range, start=None,
+                          max_iterations=10, threshold=0.01):
+    """global_shifts followed by refine_shifts_from_spectra on the same spectra (computed exactly as global_shifts
+    computes them) -> ((t, 2) px, history)."""
+    t, h, w = img.shape
+    _lib.normalize_frame_index(reference_frame, t)  # IndexError before any launch
+    pl = planmod.get_xc_plan(h, w, pixel_spacing, b_factor, frequency_range, img.device)
+    S = _global_spectra(img, pl)
+    return refine_shifts_from_spectra(S, t, reference_frame, pl, start, max_iterations, threshold)
+
+
 # ------------------------------------------------------------------ a8: patch field
 
 
@@ -1082,6 +1182,12 @@ def global_shifts_raw(rm: RawMovie, reference_frame, pixel_spacing, b_factor, fr
     statistics are known beforehand, so the plain column pass follows.  Raises McorrUnsupported for shapes
     without a fused kernel.  `after_k1()`, if given, is called once the last chunk's K1 (and hot-pixel fix-up)
     has been enqueued."""
+    S, pl = _global_spectra_raw(rm, reference_frame, pixel_spacing, b_factor, frequency_range, after_k1)
+    return _shifts_from_spectra(S, rm.shape[0], reference_frame, pl)
+
+
+def _global_spectra_raw(rm, reference_frame, pixel_spacing, b_factor, frequency_range, after_k1=None):
+    """The filtered pruned spectra of global_shifts_raw and their plan -> (S (t, nkx, nky, 2), plan)."""
     lib = _lib.load()
     t, h, w = rm.shape
     dev = rm.raw.device
@@ -1118,7 +1224,15 @@ def global_shifts_raw(rm: RawMovie, reference_frame, pixel_spacing, b_factor, fr
             after_k1()
         check(_k2(lib, g, dev, T1, pl.filt, S[a:a + n], pl.tw_col, n, st), "xc cols forward")
     del T1
-    return _shifts_from_spectra(S, t, reference_frame, pl)
+    return S, pl
+
+
+def global_shifts_raw_refined(rm: RawMovie, reference_frame, pixel_spacing, b_factor, frequency_range, start=None,
+                              max_iterations=10, threshold=0.01):
+    """global_shifts_raw followed by refine_shifts_from_spectra on the same spectra -> ((t, 2) px, history).  Raises
+    McorrUnsupported for shapes without a fused raw kernel, as global_shifts_raw."""
+    S, pl = _global_spectra_raw(rm, reference_frame, pixel_spacing, b_factor, frequency_range)
+    return refine_shifts_from_spectra(S, rm.shape[0], reference_frame, pl, start, max_iterations, threshold)
 
 
 def warp_rigid_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want_sum=False, tables=None,
