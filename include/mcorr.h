@@ -326,6 +326,22 @@ int mc_xc_aligned_refs(const void* S, const float* shifts_px, const float* fy, c
 int mc_xc_refine_update(const int* peaks, const float* nb, float* shifts_px, int ref, int t, int H, int W,
                         int under_px, float* max_r, void* stream);
 
+/* Iterative sub-pixel PATCH alignment (refine_local_motion): the same iteration with one shift per (frame, patch).
+ * S: the patch estimator's filtered spectra, [t][npatch][nkx][nky] complex (job = f * npatch + q); shifts_px and
+ * offsets_px: [t][npatch][2] px (y, x), offsets_px the whole-pixel displacement each job's window was cut at (the
+ * ramp carries shifts_px - offsets_px).  For the patches q0 <= q < q0 + nq (independent of each other):
+ *   G_fq = S_fq exp(+2 pi i (fy[ky] (sy - oy) + fx[kx] (sx - ox))),   REF = (sum_g G_gq - G_fq) / (t - 1),
+ * G (under-corrected by under_px on both axes, as mc_xc_aligned_refs) and REF hold that range only, [t][nq][nkx][nky]:
+ * pair f * nq + (q - q0) for K3/K4/K6.  1 <= t <= 512, nq <= 65535. */
+int mc_xc_aligned_refs_patches(const void* S, const float* shifts_px, const float* offsets_px, const float* fy,
+                               const float* fx, void* G, void* REF, int t, int npatch, int q0, int nq, int nkx,
+                               int nky, int under_px, void* stream);
+/* mc_xc_refine_update for the patches q0 <= q < q0 + nq, one workgroup each: peaks / nb in the pair order above;
+ * shifts_px[f][q] += (t-1)/t r, then shifts_px[:][q] -= shifts_px[ref][q] (row `ref` exactly 0 in every patch);
+ * max_r[q] ([npatch]) = max_f max(|r_y|, |r_x|) of patch q.  2 <= t <= 512. */
+int mc_xc_refine_update_patches(const int* peaks, const float* nb, float* shifts_px, int ref, int t, int npatch,
+                                int q0, int nq, int H, int W, int under_px, float* max_r, void* stream);
+
 /* ---- a11/a12/a13: per-frame shift post-processing ------------------------------- */
 /* Sub-pixel parabola (rules Q4/Q5), wrap-around, outlier rejection
  * (estimate_motion_xc.py:538-627) and accumulation into field (2,t,gh,gw) [Angstrom]

@@ -30,6 +30,8 @@ from .api import (  # noqa: F401
     motion_correct_sum_raw,
     refine_global_motion,
     refine_global_motion_raw,
+    refine_local_motion,
+    refine_local_motion_raw,
     resample_deformation_field,
 )
 from ._lib import McorrError  # noqa: F401
@@ -48,6 +50,8 @@ __all__ = [
     "estimate_global_motion",
     "refine_global_motion",
     "refine_global_motion_raw",
+    "refine_local_motion",
+    "refine_local_motion_raw",
     "estimate_motion_cross_correlation_patches",
     "estimate_local_motion",
     "OptimizationState",

@@ -27,7 +27,8 @@ SOURCES = [("xcg_fft.hip", "xcg_fft_p3", ["-DXCG_PART=3"]), ("xcg_fft.hip", "xcg
            # the scalar rate on gfx950, so nothing is gained for it
            ("warp.hip", "warp", ["-fno-slp-vectorize"]), ("plan_stats.hip", "plan_stats", []),
            ("field_post.hip", "field_post", []), ("local_motion.hip", "local_motion", []),
-           ("polyphase.hip", "polyphase", []), ("xc_refine.hip", "xc_refine", [])]
+           ("polyphase.hip", "polyphase", []), ("xc_refine.hip", "xc_refine", []),
+           ("xc_refine_patches.hip", "xc_refine_patches", [])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 

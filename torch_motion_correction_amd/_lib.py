@@ -65,6 +65,8 @@ SIGNATURES = {
     "mc_xc_ref_mean_except_current": [vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, vp],
     "mc_xc_aligned_refs": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "mc_xc_refine_update": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
+    "mc_xc_aligned_refs_patches": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "mc_xc_refine_update_patches": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "mc_field_accumulate": [vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, vp, vp],
     "mc_field_smooth_center": [vp, vp, i32, i32, i32, i32, vp],
     "mc_spline_lattice": [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp],

@@ -246,6 +246,126 @@ def _refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field, ref
     return (field, res[1]) if want_history else field
 
 
+def _check_local_refine_call(movie, patch_sidelength, deformation_field, reference_frame, max_iterations,
+                             convergence_threshold, what):
+    """Argument rules of the patch refinement, before any device is touched -> (patch side, reference frame,
+    iterations, threshold)."""
+    if not isinstance(movie, torch.Tensor) or movie.dim() != 3:
+        raise ValueError(f"{what} must be (t, h, w), got {tuple(getattr(movie, 'shape', ()))}")
+    t, h, w = movie.shape
+    ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations, convergence_threshold)
+    try:
+        p = int(patch_sidelength)
+    except (TypeError, ValueError):
+        raise ValueError(f"patch_sidelength must be an integer > 0, got {patch_sidelength!r}") from None
+    if not p > 0:
+        raise ValueError(f"patch_sidelength must be > 0, got {patch_sidelength!r}")
+    if p > h or p > w:
+        raise ValueError(f"patch_sidelength {p} exceeds the frame size {h}x{w}")
+    field = deformation_field
+    if field is not None and (not isinstance(field, torch.Tensor) or field.dim() != 4 or field.shape[0] != 2
+                              or min(field.shape) < 1):
+        raise ValueError(f"deformation_field must be a (2, nt, gh, gw) tensor, got {tuple(getattr(field, 'shape', ()))}")
+    return p, ref, n_iter, thr
+
+
+def _local_refine_result(res, ps, want_history, out_dev):
+    shifts, hist, centres = res
+    field = (shifts.permute(3, 0, 1, 2) * ps).contiguous().to(out_dev)
+    return (field, centres.to(out_dev), hist) if want_history else (field, centres.to(out_dev))
+
+
+def refine_local_motion(image, pixel_spacing, patch_sidelength=1024, deformation_field=None, reference_frame=None,
+                        b_factor=500, frequency_range=(300, 10), max_iterations=10, convergence_threshold=0.01,
+                        return_history=False, device=None):
+    """Iterative sub-pixel patch alignment (local motion; MotionCor2's scheme, and what the reference's example does
+    with five passes of the patch estimator, examples/ttMotion.py:287-329): every patch of every frame is aligned, to
+    sub-pixel precision, against the mean of the same patch of the OTHER aligned frames, until the shifts stop
+    moving.  `image`: an fp32 or fp16 (t, h, w) stack (fp16 is read as it is by the 1024-px patch kernel and widened
+    once otherwise).  Returns ``(field (2, t, gh, gw) float32 in Angstrom, centres (t, gh, gw, 3) int64[, history])``
+    on the lattice ``estimate_motion_cross_correlation_patches`` uses.  The field's global mean is NOT subtracted:
+    frame `reference_frame` is the coordinate system and its field is exactly 0 in every patch, as in
+    ``refine_global_motion``.  No outlier rejection, no temporal smoothing.
+
+    Start: `deformation_field` (Angstrom; (2, t, 1, 1) from ``refine_global_motion`` or any (2, nt, gh', gw')), divided
+    by the pixel spacing and resampled to (t, gh, gw) as ``resample_deformation_field`` does; None: the result of
+    ``refine_global_motion`` on the same stack with the same `b_factor`, `frequency_range` and `reference_frame` at
+    its default iteration settings.  Every job's window is cut ONCE, at the patch origin + o with o = the start
+    rounded to whole pixels (halves to even) and clamped per axis so that the window stays inside the frame; the
+    offset needs no coarser unit for any storage type.  The windows are normalised with the central-box statistics
+    of the stack as it is, masked once and transformed once.  Per iteration, on those spectra only (no frame is read
+    again and no warped movie is written): the phase ramp for s - o, the leave-one-out mean per patch, the residual
+    -- first maximum with the wrap-around rule plus the parabola offsets of the patch estimator's sub-pixel step, the
+    three samples per axis taken circularly -- added with the factor (t-1)/t, then the reference frame's shift is
+    subtracted per patch.  The loop stops after the iteration whose largest residual over all frames and patches is
+    below `convergence_threshold` pixels (0: never, and nothing is read back inside the loop), at the latest after
+    `max_iterations`.  ``return_history=True`` appends the per-iteration largest residual as a CPU float tensor.
+    One frame returns zeros.
+
+    `reference_frame` follows Python indexing (None: t // 2; outside [-t, t): IndexError).  Argument errors are raised
+    before any device is touched.  At most 512 frames."""
+    p, ref, n_iter, thr = _check_local_refine_call(image, patch_sidelength, deformation_field, reference_frame,
+                                                   max_iterations, convergence_threshold, "image")
+    return _refine_local_motion(image, pixel_spacing, p, deformation_field, ref, b_factor, frequency_range, n_iter,
+                                thr, bool(return_history), device)
+
+
+@_on_gpu
+def _refine_local_motion(image, pixel_spacing, p, deformation_field, ref, b_factor, frequency_range, n_iter, thr,
+                         want_history, device):
+    out_dev = _out_device(image, device)
+    dev = require_gpu(out_dev)
+    img = _stage(image, dev, keep_half=True)
+    ps = float(pixel_spacing)
+    field = None if deformation_field is None else _stage(deformation_field, dev)
+    res = engine.local_shifts_refined(img, ps, p, field, ref, float(b_factor), tuple(frequency_range), n_iter, thr)
+    return _local_refine_result(res, ps, want_history, out_dev)
+
+
+def refine_local_motion_raw(movie, gain, pixel_spacing, patch_sidelength=1024, deformation_field=None,
+                            reference_frame=None, b_factor=500, frequency_range=(300, 10), max_iterations=10,
+                            convergence_threshold=0.01, return_history=False, device=None, mean_zero=True,
+                            hot_pixel_threshold=None):
+    """``refine_local_motion(condition_movie(movie, gain, mean_zero, hot_pixel_threshold), ...)`` for a RAW uint8 /
+    int16 movie without the conditioned fp32 movie: the default start comes from ``refine_global_motion_raw``'s
+    route, the patch row pass reads the raw bytes and forms ``raw * gain - frame mean`` on the fly
+    (engine.RawMovie), and the iterations only touch the patch spectra.  Returns ``(field, centres[, history])``.
+    The sums of the example's pipeline follow, still without an fp32 movie, from
+    ``motion_correct_sum_raw(movie, gain, field, pixel_spacing, dose_per_frame=..., return_plain_sum=True)``.
+
+    Fused route: u8 / i16 movies, 1024-px patches, no `hot_pixel_threshold`, frame shapes the raw kernels take.
+    Every other case runs exactly condition_movie followed by refine_local_motion."""
+    thr_hot = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # every argument rule before any device
+    _check_raw_args(movie, gain)
+    p, ref, n_iter, thr = _check_local_refine_call(movie, patch_sidelength, deformation_field, reference_frame,
+                                                   max_iterations, convergence_threshold, "movie")
+    return _refine_local_motion_raw(movie, gain, pixel_spacing, p, deformation_field, ref, b_factor, frequency_range,
+                                    n_iter, thr, bool(return_history), device, mean_zero, thr_hot)
+
+
+@_on_gpu
+def _refine_local_motion_raw(movie, gain, pixel_spacing, p, deformation_field, ref, b_factor, frequency_range, n_iter,
+                             thr, want_history, device, mean_zero, thr_hot):
+    out_dev = _out_device(movie, device)
+    dev = require_gpu(out_dev)
+    raw = movie.detach().to(dev)
+    ps = float(pixel_spacing)
+    gd = None if gain is None else gain.to(dev)
+    field = None if deformation_field is None else _stage(deformation_field, dev)
+    args = (ps, p, field, ref, float(b_factor), tuple(frequency_range), n_iter, thr)
+    res = None
+    if raw.dtype in (torch.uint8, torch.int16) and thr_hot is None:  # (the engine refuses a hot-pixel threshold)
+        try:
+            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero))
+            res = engine.local_shifts_raw_refined(rm, *args)
+        except McorrUnsupported:
+            res = None
+    if res is None:  # exactly condition_movie, then refine_local_motion
+        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr_hot)
+        res = engine.local_shifts_refined(img, *args)
+    return _local_refine_result(res, ps, want_history, out_dev)
+
+
 @_on_gpu
 def estimate_motion_cross_correlation_patches(
     image, pixel_spacing, reference_frame=None, reference_strategy="mean_except_current",

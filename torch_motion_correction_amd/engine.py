@@ -455,12 +455,22 @@ def patch_field(img, stats, pixel_spacing, reference_frame, reference_strategy, 
     p = int(patch_sidelength)
     _check_patch_args(reference_strategy, p, h, w)
     pl = planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev)
+    spectra = _patch_spectra(img, pl, stats)
+    return _patch_field_core((t, h, w), dev, pl, p, pixel_spacing, reference_frame, reference_strategy,
+                             sub_pixel_refinement, temporal_smoothing, smoothing_window_size, field0,
+                             outlier_rejection, outlier_threshold, spectra)
+
+
+def _patch_spectra(img, pl, stats):
+    """The K1 / K2 source of the patch estimators for an fp32 / fp16 (t, h, w) stack ->
+    ``spectra(job_off, job_expo, frames, expo_b=None, min_expo=None)``, the filtered spectra of the jobs (a pair
+    with `expo_b`).  `stats`: central-box statistics to normalise with inside K1, or None."""
+    w = img.shape[2]
     g = pl.geom
     if img.dtype != torch.float32 and not (g.W == 1024 and g.nkx <= 128 and g.ny % 8 == 0):
         # fp16 frames are read natively by the 1024-px patch kernel only (BASELINE C5); any other
-        # patch size goes through the workgroup / chirp-z kernels on a widened copy
-        if stats is not None:
-            pass  # the statistics were taken from the fp16 bytes: identical values
+        # patch size goes through the workgroup / chirp-z kernels on a widened copy (the statistics
+        # were taken from the fp16 bytes: identical values)
         img = img.float()
     src = [img]
 
@@ -473,9 +483,7 @@ def patch_field(img, stats, pixel_spacing, reference_frame, reference_strategy, 
             src[0] = src[0].float()  # the C side has no fp16 kernel for this case after all: widen once
             return _forward_spectra(src[0], off, w, ex, pl, stats, job_expo_b=expo_b, min_expo=min_expo)
 
-    return _patch_field_core((t, h, w), dev, pl, p, pixel_spacing, reference_frame, reference_strategy,
-                             sub_pixel_refinement, temporal_smoothing, smoothing_window_size, field0,
-                             outlier_rejection, outlier_threshold, spectra)
+    return spectra
 
 
 def _check_patch_args(reference_strategy, p, h, w):
@@ -554,6 +562,153 @@ def _patch_field_core(shape, dev, pl, p, pixel_spacing, reference_frame, referen
     check(lib.mc_field_smooth_center(ptr(field), ptr(out), t, npatch, window, 1, st),
           "mc_field_smooth_center")
     return out, lattice.centers_tensor(t, cy, cx)
+
+
+# ------------------------------------------------------------------ iterative sub-pixel patch alignment
+
+
+def patch_origins(shape, p):
+    """(cy, cx, origin): the patch estimator's centres and the (npatch, 2) int64 (y, x) corner of every patch's
+    window, centre - p // 2, patches in row-major (gy, gx) order."""
+    t, h, w = shape
+    cy, cx = lattice.patch_grid_centers(t, h, w, p)
+    origin = np.stack([np.repeat(cy - p // 2, len(cx)), np.tile(cx - p // 2, len(cy))], axis=1).astype(np.int64)
+    return cy, cx, origin
+
+
+def refine_window_offsets(start_px, shape, p):
+    """The whole-pixel displacement o of every job's window for the (t, npatch, 2) start shifts `start_px` (px,
+    (y, x); any device): per axis o = clamp(rint(s0), -origin, (h - p, w - p) - origin) with rint rounding halves
+    to even, so that the window read at origin + o stays inside the frame.  No K1 needs the offset in coarser
+    units than one sample (the raw and fp16 row passes load their sample pairs unaligned).  -> int64, same shape."""
+    t, h, w = shape
+    _, _, origin = patch_origins(shape, p)
+    org = torch.as_tensor(origin, device=start_px.device)
+    lo = (-org).to(torch.float32)
+    hi = (torch.tensor([h - p, w - p], device=start_px.device) - org).to(torch.float32)
+    s0 = start_px.detach().to(torch.float32).reshape(t, -1, 2)
+    return torch.maximum(torch.minimum(torch.round(s0), hi), lo).to(torch.int64)
+
+
+def start_field_px(field, pixel_spacing, t, gh, gw):
+    """(t, gh * gw, 2) px start shifts from a (2, nt, nh, nw) Angstrom field on the device: resampled to
+    (t, gh, gw) as resample_deformation_field does (Catmull-Rom) and divided by the pixel spacing (a device
+    divisor: the correctly rounded quotient, see rigid_shifts_px)."""
+    lin = lambda n: torch.linspace(0, 1, steps=n)  # noqa: E731
+    lat = spline_lattice(field.to(torch.float32).contiguous(), lin(t), lin(gh), lin(gw), "catmull_rom")
+    ps = torch.full((), float(pixel_spacing), dtype=torch.float32, device=lat.device)
+    return torch.div(lat, ps).permute(1, 2, 3, 0).reshape(t, gh * gw, 2).contiguous()
+
+
+def refine_patch_shifts(spectra, shape, pl, p, start_px, reference_frame, max_iterations=10, threshold=0.01):
+    """Iterative sub-pixel alignment with one shift per (frame, patch): every patch of every frame against the mean
+    of the same patch of the OTHER aligned frames (csrc/xc_refine_patches.hip has the definition), built like
+    refine_shifts_from_spectra.  `spectra`: the K1 / K2 source of the patch estimator (_patch_spectra /
+    _patch_spectra_raw); `start_px`: (t, npatch, 2) px on the device.  The windows are cut once, at the patch origin
+    + refine_window_offsets(start_px), and transformed once (mask exponent 1); an iteration -- per chunk of
+    patches mc_xc_aligned_refs_patches, K3/K4/K6 and mc_xc_refine_update_patches -- only touches those spectra.
+    G' and REF hold one chunk of patches, at most WORKSPACE_BYTES each.  Stops after the iteration whose max |r|
+    over all (frame, patch) is below `threshold` px (one host read per iteration; none with threshold 0), at the
+    latest after `max_iterations`.  Returns ((t, npatch, 2) fp32 px shifts, row `reference_frame` exactly 0 in
+    every patch; per-iteration max |r| as a CPU float tensor)."""
+    lib = _lib.load()
+    t, h, w = shape
+    dev = start_px.device
+    ref = _lib.normalize_frame_index(reference_frame, t)
+    if t > REFINE_MAX_FRAMES:
+        raise NotImplementedError(f"{t} frames: the refinement kernels take at most {REFINE_MAX_FRAMES}")
+    _, _, origin = patch_origins(shape, p)
+    npatch = origin.shape[0]
+    if t == 1:
+        return torch.zeros((1, npatch, 2), dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.float32)
+    shifts = start_px.detach().to(torch.float32).reshape(t, npatch, 2).contiguous().clone()
+    offs = refine_window_offsets(shifts, shape, p)
+    corner = torch.as_tensor(origin[:, 0] * w + origin[:, 1], device=dev)
+    frame0 = torch.arange(t, device=dev, dtype=torch.int64) * (h * w)
+    job_off = (frame0[:, None] + corner[None, :] + offs[..., 0] * w + offs[..., 1]).reshape(-1).contiguous()
+    ones = torch.ones(t * npatch, dtype=torch.int32, device=dev)
+    S = spectra(job_off, ones, np.repeat(np.arange(t, dtype=np.int64), npatch), min_expo=1)
+    offs = offs.to(torch.float32).contiguous()
+    g = pl.geom
+    fy, fx = _kept_frequencies(pl, dev)
+    under = refine_under_px(g.H, g.W)
+    nq = max(1, min(npatch, 65535, WORKSPACE_BYTES // (t * g.nkx * g.nky * 8)))
+    G = torch.empty((t * nq, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
+    REF = torch.empty_like(G)
+    idx = torch.arange(t * nq, device=dev, dtype=torch.int32)
+    patch_max = torch.zeros(npatch, dtype=torch.float32, device=dev)
+    hist = torch.zeros(max_iterations, dtype=torch.float32, device=dev)
+    st = stream_ptr(dev)
+    done = 0
+    for k in range(max_iterations):
+        for q0 in range(0, npatch, nq):
+            n = min(nq, npatch - q0)
+            check(lib.mc_xc_aligned_refs_patches(ptr(S), ptr(shifts), ptr(offs), ptr(fy), ptr(fx), ptr(G), ptr(REF), t,
+                                                 npatch, q0, n, g.nkx, g.nky, under, st), "mc_xc_aligned_refs_patches")
+            peaks, _, nb = _peaks(G, idx[:t * n], REF, idx[:t * n], pl, want_nbhd=True)
+            check(lib.mc_xc_refine_update_patches(ptr(peaks), ptr(nb), ptr(shifts), ref, t, npatch, q0, n, g.H, g.W,
+                                                  under, ptr(patch_max), st), "mc_xc_refine_update_patches")
+        hist[k] = patch_max.max()
+        done = k + 1
+        if threshold > 0.0 and float(hist[k]) < threshold:
+            break
+    return shifts, hist[:done].cpu()
+
+
+def _local_refine_plan(shape, dev, patch_sidelength, pixel_spacing, b_factor, frequency_range):
+    t, h, w = shape
+    p = int(patch_sidelength)
+    _check_patch_args("mean_except_current", p, h, w)
+    cy, cx, _ = patch_origins(shape, p)
+    return p, planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev), cy, cx
+
+
+def local_shifts_refined(img, pixel_spacing, patch_sidelength, field, reference_frame, b_factor, frequency_range,
+                         max_iterations=10, threshold=0.01):
+    """refine_patch_shifts on an fp32 / fp16 stack, normalised inside K1 with the central-box statistics of the stack
+    as it is.  `field`: the (2, nt, nh, nw) Angstrom start field on the device, or None for the result of
+    global_shifts_refined on the same stack at its default iteration settings.
+    -> ((t, gh, gw, 2) px shifts, history, (t, gh, gw, 3) centres)."""
+    t = img.shape[0]
+    dev = img.device
+    _lib.normalize_frame_index(reference_frame, t)  # IndexError before any launch
+    p, pl, cy, cx = _local_refine_plan(img.shape, dev, patch_sidelength, pixel_spacing, b_factor, frequency_range)
+    gh, gw = len(cy), len(cx)
+    centres = lattice.centers_tensor(t, cy, cx)
+    if t == 1:
+        return torch.zeros((1, gh, gw, 2), dtype=torch.float32, device=dev), torch.zeros(0), centres
+    if field is None:
+        rigid, _ = global_shifts_refined(img, reference_frame, pixel_spacing, b_factor, frequency_range)
+        field = (rigid * pixel_spacing).transpose(0, 1)[:, :, None, None]
+    start = start_field_px(field, pixel_spacing, t, gh, gw)
+    shifts, hist = refine_patch_shifts(_patch_spectra(img, pl, central_box_stats(img)), tuple(img.shape), pl, p, start,
+                                       reference_frame, max_iterations, threshold)
+    return shifts.reshape(t, gh, gw, 2), hist, centres
+
+
+def local_shifts_raw_refined(rm: "RawMovie", pixel_spacing, patch_sidelength, field, reference_frame, b_factor,
+                             frequency_range, max_iterations=10, threshold=0.01):
+    """local_shifts_refined of the conditioned movie straight from a RawMovie: 1024-px patches and no hot-pixel
+    threshold; anything else raises McorrUnsupported before anything is launched (there is no silent fall-back).
+    The default start is global_shifts_raw_refined on the same RawMovie."""
+    _local_raw_check(rm)
+    t = rm.shape[0]
+    dev = rm.raw.device
+    _lib.normalize_frame_index(reference_frame, t)
+    p, pl, cy, cx = _local_refine_plan(rm.shape, dev, patch_sidelength, pixel_spacing, b_factor, frequency_range)
+    if not _wave512_ok(pl.geom, True, True, 1):
+        raise _lib.McorrUnsupported(f"no raw patch kernel for {p}-px patches (1024 only)")
+    gh, gw = len(cy), len(cx)
+    centres = lattice.centers_tensor(t, cy, cx)
+    if t == 1:
+        return torch.zeros((1, gh, gw, 2), dtype=torch.float32, device=dev), torch.zeros(0), centres
+    if field is None:
+        rigid, _ = global_shifts_raw_refined(rm, reference_frame, pixel_spacing, b_factor, frequency_range)
+        field = (rigid * pixel_spacing).transpose(0, 1)[:, :, None, None]
+    start = start_field_px(field, pixel_spacing, t, gh, gw)
+    shifts, hist = refine_patch_shifts(_patch_spectra_raw(rm, pl), rm.shape, pl, p, start, reference_frame,
+                                       max_iterations, threshold)
+    return shifts.reshape(t, gh, gw, 2), hist, centres
 
 
 # ------------------------------------------------------------------ a14/a16: spline lattice
@@ -1274,23 +1429,13 @@ def _local_raw_check(rm: RawMovie):
         raise _lib.McorrUnsupported("the fused local-motion route has no hot-pixel corrections: condition the movie")
 
 
-def patch_field_raw(rm: RawMovie, pixel_spacing, reference_frame, reference_strategy, b_factor, frequency_range,
-                    patch_sidelength, sub_pixel_refinement, temporal_smoothing, smoothing_window_size,
-                    outlier_rejection, outlier_threshold):
-    """patch_field of the conditioned movie (condition_movie, then the central-box statistics) straight from a
-    RawMovie: the 1024-px patch row pass reads the raw bytes and the gain (mc_xc_rows_forward_dual_raw) and
-    subtracts each job's frame mean + box mean.  Raises McorrUnsupported for any shape that needs another kernel
-    (patch sizes other than 1024, a hot-pixel threshold); there is no silent fall-back."""
-    _local_raw_check(rm)
+def _patch_spectra_raw(rm: "RawMovie", pl):
+    """_patch_spectra for a RawMovie: the 1024-px patch row pass reads the raw bytes and the gain
+    (mc_xc_rows_forward_dual_raw) and subtracts each job's frame mean + box mean."""
     lib = _lib.load()
     t, h, w = rm.shape
     dev = rm.raw.device
-    p = int(patch_sidelength)
-    _check_patch_args(reference_strategy, p, h, w)
-    pl = planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev)
     g = pl.geom
-    if not _wave512_ok(g, True, True, 1):
-        raise _lib.McorrUnsupported(f"no raw patch kernel for {p}-px patches (1024 only)")
     st = stream_ptr(dev)
 
     def spectra(off, ex, frames, expo_b=None, min_expo=None):
@@ -1318,6 +1463,25 @@ def patch_field_raw(rm: RawMovie, pixel_spacing, reference_frame, reference_stra
                 check(_k2(lib, g, dev, T1b, pl.filt, Sb[a:a + n], pl.tw_col, n, st), "xc cols forward")
         return (S, Sb) if dual else S
 
+    return spectra
+
+
+def patch_field_raw(rm: RawMovie, pixel_spacing, reference_frame, reference_strategy, b_factor, frequency_range,
+                    patch_sidelength, sub_pixel_refinement, temporal_smoothing, smoothing_window_size,
+                    outlier_rejection, outlier_threshold):
+    """patch_field of the conditioned movie (condition_movie, then the central-box statistics) straight from a
+    RawMovie: the 1024-px patch row pass reads the raw bytes and the gain (mc_xc_rows_forward_dual_raw) and
+    subtracts each job's frame mean + box mean.  Raises McorrUnsupported for any shape that needs another kernel
+    (patch sizes other than 1024, a hot-pixel threshold); there is no silent fall-back."""
+    _local_raw_check(rm)
+    t, h, w = rm.shape
+    dev = rm.raw.device
+    p = int(patch_sidelength)
+    _check_patch_args(reference_strategy, p, h, w)
+    pl = planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev)
+    if not _wave512_ok(pl.geom, True, True, 1):
+        raise _lib.McorrUnsupported(f"no raw patch kernel for {p}-px patches (1024 only)")
+    spectra = _patch_spectra_raw(rm, pl)
     return _patch_field_core((t, h, w), dev, pl, p, pixel_spacing, reference_frame, reference_strategy,
                              sub_pixel_refinement, temporal_smoothing, smoothing_window_size, None,
                              outlier_rejection, outlier_threshold, spectra)
