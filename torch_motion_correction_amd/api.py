@@ -71,6 +71,66 @@ def _on_gpu(fn):
     return scoped
 
 
+# ------------------------------------------------------------------ raw movies: one route
+RAW_DTYPES = (torch.uint8, torch.int16)  # storage the fused kernels (engine.RawMovie) read
+
+
+def _stage_raw(movie, gain, device):
+    """Staging of every raw entry point -> (result device, GPU, the movie on the GPU in its own storage type, the
+    gain on the GPU or None)."""
+    out_dev = _out_device(movie, device)
+    dev = require_gpu(out_dev)
+    return out_dev, dev, movie.detach().to(dev), None if gain is None else gain.to(dev)
+
+
+def _raw_or_conditioned(raw, gd, mean_zero, thr, fused, conditioned, allow_fused=True):
+    """THE fused-or-conditioned rule of the raw entry points -> (result, (t,) int32 hot counts or None).
+    A u8 / i16 movie (and `allow_fused`, the caller's own preconditions) goes through ONE engine.RawMovie:
+    ``fused(rm)``, with the RawMovie's counts.  Where its constructor or `fused` raises McorrUnsupported (a shape
+    without a fused kernel, a hot-pixel list overflow) -- nothing else is caught -- and for every other movie, the
+    route is exactly ``conditioned(engine.condition_movie(raw, gd, mean_zero, thr))``.  The counts are asked of
+    condition_movie whenever a threshold is set: it enqueues the same kernel into the same buffers either way
+    (mc_condition_movie_hot always writes them), so callers that drop them launch what they did before."""
+    if allow_fused and raw.dtype in RAW_DTYPES:
+        try:
+            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
+            return fused(rm), rm.hot_counts
+        except McorrUnsupported:
+            pass
+    img, counts = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr,
+                                         return_hot_counts=thr is not None), None
+    if thr is not None:
+        img, counts = img
+    return conditioned(img), counts
+
+
+def _hot_counts_out(counts, t, out_dev):
+    """The ``return_hot_counts`` result: zeros where no threshold was set."""
+    return torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None else counts.to(out_dev)
+
+
+def _check_patch_sidelength(patch_sidelength, frame=None):
+    """The patch side as an int > 0 (ValueError).  With `frame` (h, w) -- the refinements' rules -- a value int()
+    refuses is a ValueError of ours too, and the patch has to fit the frame."""
+    try:
+        p = int(patch_sidelength)
+    except (TypeError, ValueError):
+        if frame is None:
+            raise
+        raise ValueError(f"patch_sidelength must be an integer > 0, got {patch_sidelength!r}") from None
+    if not p > 0:
+        raise ValueError(f"patch_sidelength must be > 0, got {patch_sidelength!r}")
+    if frame is not None and (p > frame[0] or p > frame[1]):
+        raise ValueError(f"patch_sidelength {p} exceeds the frame size {frame[0]}x{frame[1]}")
+    return p
+
+
+def _check_field_4d(field, what):
+    """A (2, nt, gh, gw) tensor without an empty axis; ValueError opening with `what` otherwise."""
+    if not isinstance(field, torch.Tensor) or field.dim() != 4 or field.shape[0] != 2 or min(field.shape) < 1:
+        raise ValueError(f"{what}, got {tuple(getattr(field, 'shape', ()))}")
+
+
 # ------------------------------------------------------------------ field utilities
 
 
@@ -225,23 +285,11 @@ def refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field=None,
 @_on_gpu
 def _refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field, ref, b_factor, frequency_range, mean_zero,
                               thr_hot, n_iter, thr, want_history, device):
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    raw = movie.detach().to(dev)
+    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
     ps = float(pixel_spacing)
-    gd = None if gain is None else gain.to(dev)
-    start = _start_shifts(deformation_field, ps, dev)
-    res = None
-    if raw.dtype in (torch.uint8, torch.int16):
-        try:
-            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr_hot)
-            res = engine.global_shifts_raw_refined(rm, ref, ps, float(b_factor), tuple(frequency_range), start, n_iter,
-                                                   thr)
-        except McorrUnsupported:
-            res = None
-    if res is None:  # exactly condition_movie, then refine_global_motion
-        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr_hot)
-        res = engine.global_shifts_refined(img, ref, ps, float(b_factor), tuple(frequency_range), start, n_iter, thr)
+    args = (ref, ps, float(b_factor), tuple(frequency_range), _start_shifts(deformation_field, ps, dev), n_iter, thr)
+    res, _ = _raw_or_conditioned(raw, gd, mean_zero, thr_hot, lambda rm: engine.global_shifts_raw_refined(rm, *args),
+                                 lambda img: engine.global_shifts_refined(img, *args))
     field = image_shifts_to_deformation_field(res[0], pixel_spacing).to(out_dev)
     return (field, res[1]) if want_history else field
 
@@ -254,18 +302,9 @@ def _check_local_refine_call(movie, patch_sidelength, deformation_field, referen
         raise ValueError(f"{what} must be (t, h, w), got {tuple(getattr(movie, 'shape', ()))}")
     t, h, w = movie.shape
     ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations, convergence_threshold)
-    try:
-        p = int(patch_sidelength)
-    except (TypeError, ValueError):
-        raise ValueError(f"patch_sidelength must be an integer > 0, got {patch_sidelength!r}") from None
-    if not p > 0:
-        raise ValueError(f"patch_sidelength must be > 0, got {patch_sidelength!r}")
-    if p > h or p > w:
-        raise ValueError(f"patch_sidelength {p} exceeds the frame size {h}x{w}")
-    field = deformation_field
-    if field is not None and (not isinstance(field, torch.Tensor) or field.dim() != 4 or field.shape[0] != 2
-                              or min(field.shape) < 1):
-        raise ValueError(f"deformation_field must be a (2, nt, gh, gw) tensor, got {tuple(getattr(field, 'shape', ()))}")
+    p = _check_patch_sidelength(patch_sidelength, (h, w))
+    if deformation_field is not None:
+        _check_field_4d(deformation_field, "deformation_field must be a (2, nt, gh, gw) tensor")
     return p, ref, n_iter, thr
 
 
@@ -346,24 +385,29 @@ def refine_local_motion_raw(movie, gain, pixel_spacing, patch_sidelength=1024, d
 @_on_gpu
 def _refine_local_motion_raw(movie, gain, pixel_spacing, p, deformation_field, ref, b_factor, frequency_range, n_iter,
                              thr, want_history, device, mean_zero, thr_hot):
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    raw = movie.detach().to(dev)
+    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
     ps = float(pixel_spacing)
-    gd = None if gain is None else gain.to(dev)
     field = None if deformation_field is None else _stage(deformation_field, dev)
     args = (ps, p, field, ref, float(b_factor), tuple(frequency_range), n_iter, thr)
-    res = None
-    if raw.dtype in (torch.uint8, torch.int16) and thr_hot is None:  # (the engine refuses a hot-pixel threshold)
-        try:
-            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero))
-            res = engine.local_shifts_raw_refined(rm, *args)
-        except McorrUnsupported:
-            res = None
-    if res is None:  # exactly condition_movie, then refine_local_motion
-        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr_hot)
-        res = engine.local_shifts_refined(img, *args)
+    # (the engine refuses a hot-pixel threshold)
+    res, _ = _raw_or_conditioned(raw, gd, mean_zero, thr_hot, lambda rm: engine.local_shifts_raw_refined(rm, *args),
+                                 lambda img: engine.local_shifts_refined(img, *args), allow_fused=thr_hot is None)
     return _local_refine_result(res, ps, want_history, out_dev)
+
+
+def _check_patch_estimate_args(t, reference_frame, reference_strategy, sub_pixel_refinement, outlier_rejection):
+    """The patch estimator's own argument rules -> the reference frame it uses."""
+    if reference_strategy not in ("middle_frame", "mean_except_current"):
+        raise ValueError(f"Unknown reference_strategy: {reference_strategy}")
+    ref = t // 2 if reference_frame is None else reference_frame
+    if reference_strategy == "middle_frame":
+        normalize_frame_index(ref, t)  # lazy_patch_grid[ref] (xc.py:306): IndexError outside [-t, t)
+    else:
+        ref = t // 2  # mean_except_current never reads reference_frame (xc.py:310-328)
+    if BUG_COMPATIBLE and outlier_rejection and not sub_pixel_refinement:
+        # Q12: integer peak coordinates reach torch.std at estimate_motion_xc.py:577
+        raise RuntimeError("std and var only support floating point and complex dtypes")
+    return ref
 
 
 @_on_gpu
@@ -382,16 +426,7 @@ def estimate_motion_cross_correlation_patches(
     # and resamples in fp32)
     img = _stage(image, dev, keep_half=deformation_field is None)
     t, h, w = img.shape
-    ref = t // 2 if reference_frame is None else reference_frame
-    if reference_strategy not in ("middle_frame", "mean_except_current"):
-        raise ValueError(f"Unknown reference_strategy: {reference_strategy}")
-    if reference_strategy == "middle_frame":
-        normalize_frame_index(ref, t)  # lazy_patch_grid[ref] (xc.py:306): IndexError outside [-t, t)
-    else:
-        ref = t // 2  # mean_except_current never reads reference_frame (xc.py:310-328)
-    if BUG_COMPATIBLE and outlier_rejection and not sub_pixel_refinement:
-        # Q12: integer peak coordinates reach torch.std at estimate_motion_xc.py:577
-        raise RuntimeError("std and var only support floating point and complex dtypes")
+    ref = _check_patch_estimate_args(t, reference_frame, reference_strategy, sub_pixel_refinement, outlier_rejection)
     stats = engine.central_box_stats(img)  # statistics of the *uncorrected* stack (Q9)
     field0 = None
     if deformation_field is not None:
@@ -548,17 +583,8 @@ def motion_correct_sum(image, deformation_grid, pixel_spacing, grid_type="catmul
     img = _stage(image, dev, keep_half=True)
     lat = engine.frame_lattices(_stage(deformation_grid, dev), img.shape[0], grid_type)
     rigid = RIGID_FAST_PATH and _is_rigid(deformation_grid)
-    if dose_per_frame is None:
-        frames, total = engine.warp(img, lat, float(pixel_spacing), want_frames=return_frames, want_sum=True,
-                                    rigid=rigid)
-    elif return_frames:
-        frames, _ = engine.warp(img, lat, float(pixel_spacing), want_frames=True, want_sum=False, rigid=rigid)
-        total = engine.dose_weighted_sum(frames, float(pixel_spacing), float(dose_per_frame),
-                                         float(pre_exposure), float(voltage))
-    else:  # the corrected movie is only an intermediate: warped and transformed a chunk at a time
-        frames = None
-        total = engine.warp_dose_weighted_sum(img, lat, float(pixel_spacing), rigid, float(dose_per_frame),
-                                              float(pre_exposure), float(voltage))
+    total, _, frames = engine.corrected_sums(img, lat, pixel_spacing, rigid, dose_per_frame, pre_exposure, voltage,
+                                             False, return_frames)
     return (total.to(out_dev), frames.to(out_dev)) if return_frames else total.to(out_dev)
 
 
@@ -597,21 +623,6 @@ def _check_dose(dose_per_frame):
     return v
 
 
-def _fused_sums(rm, lat, ps, rigid, dose, pre_exposure, voltage, want_plain, want_frames):
-    """(sum, plain sum or None, frames or None) of a RawMovie through `lat`: motion_correct_sum's three cases, the
-    warps reading the raw bytes.  Raises McorrUnsupported where a fused kernel is missing."""
-    warp = engine.warp_rigid_raw if rigid else engine.warp_field_raw
-    if dose is None:
-        frames, total = warp(rm, lat, ps, want_frames=want_frames, want_sum=True)
-        return total, None, frames
-    if want_frames:  # the frames are an output anyway: weight them as motion_correct_sum does
-        frames, plain = warp(rm, lat, ps, want_frames=True, want_sum=want_plain)
-        return engine.dose_weighted_sum(frames, ps, dose, float(pre_exposure), float(voltage)), plain, frames
-    total, plain = engine.warp_dose_weighted_sum_raw(rm, lat, ps, rigid, dose, float(pre_exposure), float(voltage),
-                                                     want_plain)
-    return total, plain, None
-
-
 def motion_correct_raw(movie, gain, pixel_spacing, reference_frame=None, b_factor=500, frequency_range=(300, 10),
                        grid_type="catmull_rom", mean_zero=True, return_frames=False, device=None,
                        hot_pixel_threshold=None, return_hot_counts=False, dose_per_frame=None, pre_exposure=0.0,
@@ -645,45 +656,28 @@ def motion_correct_raw(movie, gain, pixel_spacing, reference_frame=None, b_facto
 @_on_gpu
 def _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, grid_type, mean_zero,
                         return_frames, device, thr, return_hot_counts, dose, pre_exposure, voltage):
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    raw = movie.detach().to(dev)
+    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
     t = raw.shape[0]
     ref = t // 2 if reference_frame is None else int(reference_frame)
     ps = float(pixel_spacing)
-    gd = None if gain is None else gain.to(dev)
-    fused = raw.dtype in (torch.uint8, torch.int16)
-    counts = None
-    if fused:
-        try:
-            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
-            shifts = engine.global_shifts_raw(rm, ref, ps, float(b_factor), tuple(frequency_range))
+
+    def route(estimate):  # the same steps on a RawMovie and on the conditioned movie
+        def run(src):
+            shifts = estimate(src, ref, ps, float(b_factor), tuple(frequency_range))
             field = image_shifts_to_deformation_field(shifts, ps)
             lat = engine.frame_lattices(field.contiguous(), t, grid_type)
-            total, _, frames = _fused_sums(rm, lat, ps, True, dose, pre_exposure, voltage, False, bool(return_frames))
-            counts = rm.hot_counts
-        except McorrUnsupported:
-            fused = False
-    if not fused:
-        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr, return_hot_counts=thr is not None)
-        if thr is not None:
-            img, counts = img
-        shifts = engine.global_shifts(img, ref, ps, float(b_factor), tuple(frequency_range))
-        field = image_shifts_to_deformation_field(shifts, ps)
-        lat = engine.frame_lattices(field.contiguous(), t, grid_type)
-        if dose is None:
-            frames, total = engine.warp(img, lat, ps, want_frames=bool(return_frames), want_sum=True, rigid=True)
-        elif return_frames:  # motion_correct_sum's two dose-weighted forms
-            frames, _ = engine.warp(img, lat, ps, want_frames=True, want_sum=False, rigid=True)
-            total = engine.dose_weighted_sum(frames, ps, dose, float(pre_exposure), float(voltage))
-        else:
-            frames = None
-            total = engine.warp_dose_weighted_sum(img, lat, ps, True, dose, float(pre_exposure), float(voltage))
+            total, _, frames = engine.corrected_sums(src, lat, ps, True, dose, pre_exposure, voltage, False,
+                                                     bool(return_frames))
+            return field, total, frames
+        return run
+
+    (field, total, frames), counts = _raw_or_conditioned(raw, gd, mean_zero, thr, route(engine.global_shifts_raw),
+                                                         route(engine.global_shifts))
     out = [field.to(out_dev), total.to(out_dev)]
     if return_frames:
         out.append(frames.to(out_dev))
     if return_hot_counts:
-        out.append(torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None else counts.to(out_dev))
+        out.append(_hot_counts_out(counts, t, out_dev))
     return tuple(out)
 
 
@@ -708,9 +702,8 @@ def motion_correct_raw_patches(movie, gain, pixel_spacing, patch_sidelength=1024
     if reference_strategy not in ("middle_frame", "mean_except_current"):
         raise ValueError(f"Unknown reference_strategy: {reference_strategy}")
     thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # ValueError before any device is touched
-    if not int(patch_sidelength) > 0:
-        raise ValueError(f"patch_sidelength must be > 0, got {patch_sidelength!r}")
-    return _motion_correct_raw_patches(movie, gain, pixel_spacing, int(patch_sidelength), reference_frame,
+    p = _check_patch_sidelength(patch_sidelength)
+    return _motion_correct_raw_patches(movie, gain, pixel_spacing, p, reference_frame,
                                        reference_strategy, b_factor, frequency_range, sub_pixel_refinement,
                                        temporal_smoothing, smoothing_window_size, deformation_field, outlier_rejection,
                                        outlier_threshold, grid_type, mean_zero, return_frames, device, thr,
@@ -722,53 +715,43 @@ def _motion_correct_raw_patches(movie, gain, pixel_spacing, patch_sidelength, re
                                 b_factor, frequency_range, sub_pixel_refinement, temporal_smoothing,
                                 smoothing_window_size, deformation_field, outlier_rejection, outlier_threshold,
                                 grid_type, mean_zero, return_frames, device, thr, return_hot_counts):
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    raw = movie.detach().to(dev)
+    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
     t = raw.shape[0]
     ps = float(pixel_spacing)
-    gd = None if gain is None else gain.to(dev)
-    est = dict(reference_strategy=reference_strategy, b_factor=b_factor, frequency_range=frequency_range,
-               patch_sidelength=patch_sidelength, sub_pixel_refinement=sub_pixel_refinement,
-               temporal_smoothing=temporal_smoothing, smoothing_window_size=smoothing_window_size,
-               outlier_rejection=outlier_rejection, outlier_threshold=outlier_threshold)
-    fused = raw.dtype in (torch.uint8, torch.int16) and deformation_field is None and thr is None
-    if fused:
-        # the estimator's own argument rules (estimate_motion_cross_correlation_patches), before any launch
-        ref = t // 2 if reference_frame is None else reference_frame
-        if reference_strategy == "middle_frame":
-            normalize_frame_index(ref, t)
-        else:
-            ref = t // 2
-        if BUG_COMPATIBLE and outlier_rejection and not sub_pixel_refinement:
-            raise RuntimeError("std and var only support floating point and complex dtypes")
-        try:
-            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero))
-            field, centers = engine.patch_field_raw(
-                rm, ps, ref, reference_strategy, float(b_factor), frequency_range, patch_sidelength,
-                bool(sub_pixel_refinement), bool(temporal_smoothing), int(smoothing_window_size),
-                bool(outlier_rejection), float(outlier_threshold))
-            lat = engine.frame_lattices(field, t, grid_type)
-            if RIGID_FAST_PATH and _is_rigid(field):  # a single patch: motion_correct_sum's rigid warp
-                frames, total = engine.warp_rigid_raw(rm, lat, ps, want_frames=bool(return_frames), want_sum=True)
-            else:
-                frames, total = engine.warp_field_raw(rm, lat, ps, want_frames=bool(return_frames), want_sum=True)
-        except McorrUnsupported:
-            fused = False
-    counts = None
-    if not fused:
-        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr, return_hot_counts=thr is not None)
-        if thr is not None:
-            img, counts = img
-        field, centers = estimate_motion_cross_correlation_patches(img, ps, reference_frame=reference_frame,
-                                                                   deformation_field=deformation_field, **est)
+    allow_fused = deformation_field is None and thr is None
+    ref = None
+    if allow_fused and raw.dtype in RAW_DTYPES:  # the estimator's own argument rules, before any launch
+        ref = _check_patch_estimate_args(t, reference_frame, reference_strategy, sub_pixel_refinement,
+                                         outlier_rejection)
+
+    def fused(rm):
+        field, centers = engine.patch_field_raw(
+            rm, ps, ref, reference_strategy, float(b_factor), frequency_range, patch_sidelength,
+            bool(sub_pixel_refinement), bool(temporal_smoothing), int(smoothing_window_size),
+            bool(outlier_rejection), float(outlier_threshold))
+        lat = engine.frame_lattices(field, t, grid_type)
+        # (a single patch: motion_correct_sum's rigid warp)
+        total, _, frames = engine.corrected_sums(rm, lat, ps, RIGID_FAST_PATH and _is_rigid(field),
+                                                 want_frames=bool(return_frames))
+        return field, centers, total, frames
+
+    def conditioned(img):
+        field, centers = estimate_motion_cross_correlation_patches(
+            img, ps, reference_frame=reference_frame, reference_strategy=reference_strategy, b_factor=b_factor,
+            frequency_range=frequency_range, patch_sidelength=patch_sidelength,
+            sub_pixel_refinement=sub_pixel_refinement, temporal_smoothing=temporal_smoothing,
+            smoothing_window_size=smoothing_window_size, deformation_field=deformation_field,
+            outlier_rejection=outlier_rejection, outlier_threshold=outlier_threshold)
         res = motion_correct_sum(img, field, ps, grid_type=grid_type, return_frames=bool(return_frames))
-        total, frames = res if return_frames else (res, None)
+        return (field, centers, *(res if return_frames else (res, None)))
+
+    (field, centers, total, frames), counts = _raw_or_conditioned(raw, gd, mean_zero, thr, fused, conditioned,
+                                                                  allow_fused)
     out = [field.to(out_dev), centers.to(out_dev), total.to(out_dev)]
     if return_frames:
         out.append(frames.to(out_dev))
     if return_hot_counts:
-        out.append(torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None else counts.to(out_dev))
+        out.append(_hot_counts_out(counts, t, out_dev))
     return tuple(out)
 
 
@@ -789,46 +772,34 @@ def motion_correct_sum_raw(movie, gain, deformation_grid, pixel_spacing, grid_ty
     Returns ``sum (h,w)``, or the tuple ``(sum[, plain sum][, frames (t,h,w)])``.  A (2,t,1,1) field takes the rigid
     warp.  fp16 / fp32 movies, shapes without fused kernels, a local field with ``hot_pixel_threshold`` (the local
     raw warp has no hot-pixel corrections) and a hot-pixel list overflow take exactly the conditioned route."""
-    dose = _check_dose(dose_per_frame)  # every argument rule before any device is touched
-    if return_plain_sum and dose is None:
-        raise ValueError("return_plain_sum needs dose_per_frame: without a dose the result is the plain sum")
+    dose = _check_fast_sum_args(dose_per_frame, return_plain_sum)  # every argument rule before any device is touched
     thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)
-    field = deformation_grid
-    if not isinstance(field, torch.Tensor) or field.dim() != 4 or field.shape[0] != 2 or min(field.shape) < 1:
-        raise ValueError(f"deformation_grid must be a (2, nt, gh, gw) tensor, got {tuple(getattr(field, 'shape', ()))}")
-    if movie.dim() != 3:
-        raise ValueError(f"movie must be (t, h, w), got {tuple(movie.shape)}")
-    if gain is not None and tuple(gain.shape) != tuple(movie.shape[-2:]):
-        raise ValueError(f"gain reference has shape {tuple(gain.shape)}, frames are {tuple(movie.shape[-2:])}")
-    return _motion_correct_sum_raw(movie, gain, field, pixel_spacing, grid_type, mean_zero, thr, dose, pre_exposure,
-                                   voltage, bool(return_plain_sum), bool(return_frames), device)
+    _check_field_4d(deformation_grid, "deformation_grid must be a (2, nt, gh, gw) tensor")
+    _check_raw_args(movie, gain)
+    return _motion_correct_sum_raw(movie, gain, deformation_grid, pixel_spacing, grid_type, mean_zero, thr, dose,
+                                   pre_exposure, voltage, bool(return_plain_sum), bool(return_frames), device)
 
 
 @_on_gpu
 def _motion_correct_sum_raw(movie, gain, field, pixel_spacing, grid_type, mean_zero, thr, dose, pre_exposure, voltage,
                             want_plain, want_frames, device):
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    raw = movie.detach().to(dev)
+    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
     t = raw.shape[0]
     ps = float(pixel_spacing)
-    gd = None if gain is None else gain.to(dev)
     field = _stage(field, dev)
     rigid = RIGID_FAST_PATH and _is_rigid(field)
-    fused = raw.dtype in (torch.uint8, torch.int16)
-    if fused:
-        try:
-            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
-            lat = engine.frame_lattices(field, t, grid_type)
-            total, plain, frames = _fused_sums(rm, lat, ps, rigid, dose, pre_exposure, voltage, want_plain, want_frames)
-        except McorrUnsupported:
-            fused = False
-    if not fused:  # exactly condition_movie, then motion_correct_sum (once more without the dose for the plain sum)
-        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr)
+
+    def fused(rm):
+        lat = engine.frame_lattices(field, t, grid_type)
+        return engine.corrected_sums(rm, lat, ps, rigid, dose, pre_exposure, voltage, want_plain, want_frames)
+
+    def conditioned(img):  # motion_correct_sum, once more without the dose for the plain sum
         res = motion_correct_sum(img, field, ps, grid_type=grid_type, return_frames=want_frames, dose_per_frame=dose,
                                  pre_exposure=pre_exposure, voltage=voltage)
         total, frames = res if want_frames else (res, None)
-        plain = motion_correct_sum(img, field, ps, grid_type=grid_type) if want_plain else None
+        return total, (motion_correct_sum(img, field, ps, grid_type=grid_type) if want_plain else None), frames
+
+    (total, plain, frames), _ = _raw_or_conditioned(raw, gd, mean_zero, thr, fused, conditioned)
     out = [total.to(out_dev)]
     if want_plain:
         out.append(plain.to(out_dev))
@@ -917,8 +888,7 @@ def _check_fast_field(deformation_grid, t):
     """A rigid (2, t, 1, 1) field for the Fourier-shift sums; ValueError otherwise (before any device is touched).  A
     field with more than one patch gets correct_motion_fast's own message."""
     field = deformation_grid
-    if not isinstance(field, torch.Tensor) or field.dim() != 4 or field.shape[0] != 2 or min(field.shape) < 1:
-        raise ValueError(f"deformation_grid must be a (2, t, 1, 1) tensor, got {tuple(getattr(field, 'shape', ()))}")
+    _check_field_4d(field, "deformation_grid must be a (2, t, 1, 1) tensor")
     if tuple(field.shape[-2:]) != (1, 1):
         raise ValueError(
             f"Expected single patch deformation field with shape (2, t, 1, 1), "
@@ -1020,23 +990,13 @@ def motion_correct_sum_fast_raw(movie, gain, deformation_grid, pixel_spacing, me
 @_on_gpu
 def _motion_correct_sum_fast_raw(movie, gain, deformation_grid, pixel_spacing, mean_zero, thr, dose, pre_exposure,
                                  voltage, want_plain, device):
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    raw = movie.detach().to(dev)
+    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
     ps = float(pixel_spacing)
-    gd = None if gain is None else gain.to(dev)
     field = deformation_grid.detach().to(dev)
-    res = None
-    if raw.dtype in (torch.uint8, torch.int16):
-        try:
-            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
-            res = engine.fast_shift_sums(rm, engine.fast_shifts(field / ps), ps, dose, pre_exposure, voltage,
-                                         want_plain)
-        except McorrUnsupported:
-            res = None
-    if res is None:  # exactly condition_movie, then motion_correct_sum_fast
-        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr)
-        res = _fast_sums(img, field, ps, dose, pre_exposure, voltage, want_plain)
+    sums = (ps, dose, pre_exposure, voltage, want_plain)
+    res, _ = _raw_or_conditioned(raw, gd, mean_zero, thr,
+                                 lambda rm: engine.fast_shift_sums(rm, engine.fast_shifts(field / ps), *sums),
+                                 lambda img: _fast_sums(img, field, *sums))
     return _fast_result(*res, want_plain, out_dev)
 
 
@@ -1062,38 +1022,28 @@ def motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame=None, b_
 @_on_gpu
 def _motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, mean_zero, thr,
                              dose, pre_exposure, voltage, want_plain, want_counts, device):
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    raw = movie.detach().to(dev)
+    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
     t = raw.shape[0]
     ref = t // 2 if reference_frame is None else int(reference_frame)
     ps = float(pixel_spacing)
-    gd = None if gain is None else gain.to(dev)
-    res = counts = None
-    if raw.dtype in (torch.uint8, torch.int16):
-        try:
-            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
-            shifts = engine.global_shifts_raw(rm, ref, ps, float(b_factor), tuple(frequency_range))
+    sums = (ps, dose, pre_exposure, voltage, want_plain)
+
+    def route(estimate, fast_sums):  # the same steps on a RawMovie and on the conditioned movie
+        def run(src):
+            shifts = estimate(src, ref, ps, float(b_factor), tuple(frequency_range))
             field = image_shifts_to_deformation_field(shifts, ps)  # as motion_correct_raw
-            res = engine.fast_shift_sums(rm, engine.fast_shifts(field / ps), ps, dose, pre_exposure, voltage,
-                                         want_plain)
-            counts = rm.hot_counts
-        except McorrUnsupported:
-            res = counts = None
-    if res is None:  # exactly condition_movie, estimate_global_motion, motion_correct_sum_fast
-        img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr,
-                                     return_hot_counts=thr is not None)
-        if thr is not None:
-            img, counts = img
-        shifts = engine.global_shifts(img, ref, ps, float(b_factor), tuple(frequency_range))
-        field = image_shifts_to_deformation_field(shifts, ps)
-        res = _fast_sums(img, field, ps, dose, pre_exposure, voltage, want_plain)
-    dw, plain = res
+            return field, fast_sums(src, field)
+        return run
+
+    (field, (dw, plain)), counts = _raw_or_conditioned(
+        raw, gd, mean_zero, thr,
+        route(engine.global_shifts_raw, lambda rm, f: engine.fast_shift_sums(rm, engine.fast_shifts(f / ps), *sums)),
+        route(engine.global_shifts, lambda img, f: _fast_sums(img, f, *sums)))
     out = [field.to(out_dev), (plain if dw is None else dw).to(out_dev)]
     if want_plain:
         out.append(plain.to(out_dev))
     if want_counts:
-        out.append(torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None else counts.to(out_dev))
+        out.append(_hot_counts_out(counts, t, out_dev))
     return tuple(out)
 
 
@@ -1137,19 +1087,9 @@ def _fourier_crop(image, device):
 
 
 def _crop_raw(raw, gd, mean_zero, thr):
-    """(binned fp32 movie, hot counts or None) of a movie on the device: u8 / i16 through one RawMovie, anything else
-    -- and a hot-pixel list overflow -- exactly condition_movie then fourier_crop."""
-    if raw.dtype in (torch.uint8, torch.int16):
-        try:
-            rm = engine.RawMovie(raw, gd, mean_zero=bool(mean_zero), hot_pixel_threshold=thr)
-            return engine.fourier_crop(rm), rm.hot_counts
-        except McorrUnsupported:
-            pass
-    counts = None
-    img = engine.condition_movie(raw, gd, bool(mean_zero), hot_pixel_threshold=thr, return_hot_counts=thr is not None)
-    if thr is not None:
-        img, counts = img
-    return engine.fourier_crop(img), counts
+    """(binned fp32 movie, hot counts or None) of a movie on the device: engine.fourier_crop of the RawMovie, or of
+    the conditioned movie."""
+    return _raw_or_conditioned(raw, gd, mean_zero, thr, engine.fourier_crop, engine.fourier_crop)
 
 
 def fourier_crop_raw(movie, gain, binning=2, mean_zero=True, hot_pixel_threshold=None, return_hot_counts=False,
@@ -1169,14 +1109,11 @@ def fourier_crop_raw(movie, gain, binning=2, mean_zero=True, hot_pixel_threshold
 
 @_on_gpu
 def _fourier_crop_raw(movie, gain, mean_zero, thr, want_counts, device):
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    binned, counts = _crop_raw(movie.detach().to(dev), None if gain is None else gain.to(dev), mean_zero, thr)
+    out_dev, _, raw, gd = _stage_raw(movie, gain, device)
+    binned, counts = _crop_raw(raw, gd, mean_zero, thr)
     if not want_counts:
         return binned.to(out_dev)
-    t = movie.shape[0]
-    return binned.to(out_dev), (torch.zeros(t, dtype=torch.int32, device=out_dev) if counts is None
-                                else counts.to(out_dev))
+    return binned.to(out_dev), _hot_counts_out(counts, movie.shape[0], out_dev)
 
 
 def motion_correct_raw_binned(movie, gain, pixel_spacing, binning=2, patch_sidelength=None, reference_frame=None,
@@ -1204,8 +1141,7 @@ def motion_correct_raw_binned(movie, gain, pixel_spacing, binning=2, patch_sidel
     _check_raw_args(movie, gain)
     _check_crop_args(movie.shape, binning)
     if patch_sidelength is not None:
-        if not int(patch_sidelength) > 0:
-            raise ValueError(f"patch_sidelength must be > 0, got {patch_sidelength!r}")
+        _check_patch_sidelength(patch_sidelength)
         if return_plain_sum:
             raise ValueError("return_plain_sum belongs to the whole-image route (patch_sidelength=None)")
     return _motion_correct_raw_binned(movie, gain, pixel_spacing, binning, patch_sidelength, reference_frame, b_factor,
@@ -1217,9 +1153,8 @@ def motion_correct_raw_binned(movie, gain, pixel_spacing, binning=2, patch_sidel
 def _motion_correct_raw_binned(movie, gain, pixel_spacing, binning, patch_sidelength, reference_frame, b_factor,
                                frequency_range, grid_type, mean_zero, thr, dose, pre_exposure, voltage, want_plain,
                                want_counts, device):
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    binned, counts = _crop_raw(movie.detach().to(dev), None if gain is None else gain.to(dev), mean_zero, thr)
+    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
+    binned, counts = _crop_raw(raw, gd, mean_zero, thr)
     ps = binning * float(pixel_spacing)
     # the public functions themselves on the device-resident binned movie: the composition by construction
     if patch_sidelength is None:
@@ -1235,7 +1170,7 @@ def _motion_correct_raw_binned(movie, gain, pixel_spacing, binning, patch_sidele
         out = [field, centers, motion_correct_sum(binned, field, ps, grid_type=grid_type, dose_per_frame=dose,
                                                   pre_exposure=pre_exposure, voltage=voltage)]
     if want_counts:
-        out.append(torch.zeros(movie.shape[0], dtype=torch.int32, device=dev) if counts is None else counts)
+        out.append(_hot_counts_out(counts, movie.shape[0], dev))  # (moved to out_dev with the rest)
     return tuple(x.to(out_dev) for x in out)
 
 

@@ -41,6 +41,19 @@ def _i64(a, device):
     return torch.as_tensor(np.asarray(a, dtype=np.int64), device=device)
 
 
+def _pow2(n):
+    return n > 0 and (n & (n - 1)) == 0
+
+
+def _chunks(n, item_bytes, most=None):
+    """THE workspace rule: `n` items whose intermediates take `item_bytes` each are processed `chunk` at a time,
+    as many as fit WORKSPACE_BYTES (read at call time; `most`: a further cap on the chunk), at least one
+    -> (chunk, [(first, count), ...]).  The chunk size is result-bearing: it sets the summation order of the dose
+    accumulators and the path _peaks takes."""
+    chunk = max(1, min(n if most is None else min(n, most), WORKSPACE_BYTES // item_bytes))
+    return chunk, [(a, min(chunk, n - a)) for a in range(0, n, chunk)]
+
+
 # ------------------------------------------------------------------ statistics
 
 
@@ -97,11 +110,37 @@ def _k2(lib, g, dev, T1, filt, S, tw_col, n, st):
     return lib.mc_xcg_cols_forward(ptr(T1), ptr(filt), ptr(S), line, n, g, st)
 
 
+def _wave_rows_geometry(g):
+    """The geometry of the wave-per-row patch kernels (mc_xc_rows_forward_dual*): rows of 1024 samples."""
+    return g.W == 1024 and g.nkx <= 128 and g.ny % 8 == 0
+
+
 def _wave512_ok(g, job_expo, use_mask, min_expo):
     """Patch rows of 1024 samples can take the wave-per-row K1 (mc_xc_rows_forward_dual):
     needs the mask and per-job exponents that are all >= 1 (`min_expo`, known on the host)."""
-    return (g.W == 1024 and g.nkx <= 128 and g.ny % 8 == 0 and use_mask and job_expo is not None
+    return (_wave_rows_geometry(g) and use_mask and job_expo is not None
             and min_expo is not None and min_expo >= 1)
+
+
+def _filtered_spectra(pl, dev, njobs, rows_pass, dual=False, use_filter=True):
+    """THE K1 + K2 loop of the estimators -> S (njobs, nkx, nky, 2), or (S, Sb) with `dual`.  Per chunk of jobs
+    (_chunks over the transposed intermediate T1, and T1b with `dual`) `rows_pass(a, n, T1, T1b)` enqueues the row
+    pass of jobs a .. a+n-1 into T1 (chunk, nkx, ny, 2) (and T1b); the column pass (_k2) follows into S[a:a+n]."""
+    lib = _lib.load()
+    g = pl.geom
+    S = torch.empty((njobs, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
+    Sb = torch.empty_like(S) if dual else None
+    chunk, spans = _chunks(njobs, g.nkx * g.ny * 8 * (2 if dual else 1))
+    T1 = torch.empty((chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
+    T1b = torch.empty_like(T1) if dual else None
+    filt = pl.filt if use_filter else None
+    st = stream_ptr(dev)
+    for a, n in spans:
+        rows_pass(a, n, T1, T1b)
+        check(_k2(lib, g, dev, T1, filt, S[a : a + n], pl.tw_col, n, st), "xc cols forward")
+        if dual:
+            check(_k2(lib, g, dev, T1b, filt, Sb[a : a + n], pl.tw_col, n, st), "xc cols forward")
+    return (S, Sb) if dual else S
 
 
 def _forward_spectra(src, job_off, row_stride, job_expo, pl, stats, use_mask=True, use_filter=True,
@@ -110,7 +149,6 @@ def _forward_spectra(src, job_off, row_stride, job_expo, pl, stats, use_mask=Tru
     once and transformed twice (mask^job_expo and mask^job_expo_b): returns (S_a, S_b)."""
     lib = _lib.load()
     g, dev = pl.geom, src.device
-    njobs = int(job_off.numel())
     dual = job_expo_b is not None
     wave = _wave512_ok(g, job_expo, use_mask, min_expo)
     if src.dtype != torch.float32 and not wave:
@@ -118,15 +156,9 @@ def _forward_spectra(src, job_off, row_stride, job_expo, pl, stats, use_mask=Tru
     if dual and not wave:  # no fused kernel for this shape: two ordinary passes
         return (_forward_spectra(src, job_off, row_stride, job_expo, pl, stats, use_mask, use_filter),
                 _forward_spectra(src, job_off, row_stride, job_expo_b, pl, stats, use_mask, use_filter))
-    S = torch.empty((njobs, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
-    Sb = torch.empty_like(S) if dual else None
-    per_job = g.nkx * g.ny * 8 * (2 if dual else 1)
-    chunk = max(1, min(njobs, WORKSPACE_BYTES // per_job))
-    T1 = torch.empty((chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
-    T1b = torch.empty_like(T1) if dual else None
     st = stream_ptr(dev)
-    for a in range(0, njobs, chunk):
-        n = min(chunk, njobs - a)
+
+    def rows_pass(a, n, T1, T1b):
         off = job_off[a : a + n]
         expo = None if job_expo is None else job_expo[a : a + n]
         if wave:
@@ -139,12 +171,8 @@ def _forward_spectra(src, job_off, row_stride, job_expo, pl, stats, use_mask=Tru
         else:
             check(_k1(lib, g, dev, src, off, row_stride, expo, pl.mask if use_mask else None, stats, T1,
                       pl.tw_row, n, st), "xc rows forward")
-        check(_k2(lib, g, dev, T1, pl.filt if use_filter else None, S[a : a + n], pl.tw_col, n, st),
-              "xc cols forward")
-        if dual:
-            check(_k2(lib, g, dev, T1b, pl.filt if use_filter else None, Sb[a : a + n], pl.tw_col, n, st),
-                  "xc cols forward")
-    return (S, Sb) if dual else S
+
+    return _filtered_spectra(pl, dev, int(job_off.numel()), rows_pass, dual, use_filter)
 
 
 def _peaks(S_cur, cur_idx, S_ref, ref_idx, pl, want_nbhd, shift_rows=None, n_shift_rows=0):
@@ -158,8 +186,7 @@ def _peaks(S_cur, cur_idx, S_ref, ref_idx, pl, want_nbhd, shift_rows=None, n_shi
     shifts = torch.empty((n_shift_rows if shift_rows is not None else npairs, 2), dtype=torch.float32,
                          device=dev)
     nb = torch.empty((npairs, 3, 3), dtype=torch.float32, device=dev) if want_nbhd else None
-    per_pair = g.nkx * g.H * 8
-    chunk = max(1, min(npairs, WORKSPACE_BYTES // per_pair))
+    chunk, spans = _chunks(npairs, g.nkx * g.H * 8)
     T2 = torch.empty((chunk, g.nkx, g.H, 2), dtype=torch.float32, device=dev)
     ngrp = g.H // g.RG
     pv = torch.empty(chunk * ngrp + chunk * g.H, dtype=torch.float32, device=dev)
@@ -174,8 +201,7 @@ def _peaks(S_cur, cur_idx, S_ref, ref_idx, pl, want_nbhd, shift_rows=None, n_shi
         table, shifts = shifts, torch.empty((npairs, 2), dtype=torch.float32, device=dev)
     if fused:
         T2n = torch.empty((chunk, g.nkx, 2 * lib.mc_xc_near_rows(g), 2), dtype=torch.float32, device=dev)
-    for a in range(0, npairs, chunk):
-        n = min(chunk, npairs - a)
+    for a, n in spans:
         if fused:
             check(lib.mc_xc_correlate_argmax(ptr(S_cur), ptr(cur_idx[a : a + n]), ptr(S_ref),
                                              ptr(ref_idx[a : a + n]), ptr(T2), ptr(T2n), ptr(pv), ptr(pi),
@@ -466,8 +492,7 @@ def _patch_spectra(img, pl, stats):
     ``spectra(job_off, job_expo, frames, expo_b=None, min_expo=None)``, the filtered spectra of the jobs (a pair
     with `expo_b`).  `stats`: central-box statistics to normalise with inside K1, or None."""
     w = img.shape[2]
-    g = pl.geom
-    if img.dtype != torch.float32 and not (g.W == 1024 and g.nkx <= 128 and g.ny % 8 == 0):
+    if img.dtype != torch.float32 and not _wave_rows_geometry(pl.geom):
         # fp16 frames are read natively by the 1024-px patch kernel only (BASELINE C5); any other
         # patch size goes through the workgroup / chirp-z kernels on a widened copy (the statistics
         # were taken from the fp16 bytes: identical values)
@@ -632,7 +657,7 @@ def refine_patch_shifts(spectra, shape, pl, p, start_px, reference_frame, max_it
     g = pl.geom
     fy, fx = _kept_frequencies(pl, dev)
     under = refine_under_px(g.H, g.W)
-    nq = max(1, min(npatch, 65535, WORKSPACE_BYTES // (t * g.nkx * g.nky * 8)))
+    nq, spans = _chunks(npatch, t * g.nkx * g.nky * 8, most=65535)
     G = torch.empty((t * nq, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
     REF = torch.empty_like(G)
     idx = torch.arange(t * nq, device=dev, dtype=torch.int32)
@@ -641,8 +666,7 @@ def refine_patch_shifts(spectra, shape, pl, p, start_px, reference_frame, max_it
     st = stream_ptr(dev)
     done = 0
     for k in range(max_iterations):
-        for q0 in range(0, npatch, nq):
-            n = min(nq, npatch - q0)
+        for q0, n in spans:
             check(lib.mc_xc_aligned_refs_patches(ptr(S), ptr(shifts), ptr(offs), ptr(fy), ptr(fx), ptr(G), ptr(REF), t,
                                                  npatch, q0, n, g.nkx, g.nky, under, st), "mc_xc_aligned_refs_patches")
             peaks, _, nb = _peaks(G, idx[:t * n], REF, idx[:t * n], pl, want_nbhd=True)
@@ -655,12 +679,28 @@ def refine_patch_shifts(spectra, shape, pl, p, start_px, reference_frame, max_it
     return shifts, hist[:done].cpu()
 
 
-def _local_refine_plan(shape, dev, patch_sidelength, pixel_spacing, b_factor, frequency_range):
+def _local_shifts_refined(shape, dev, pixel_spacing, patch_sidelength, field, reference_frame, b_factor,
+                          frequency_range, max_iterations, threshold, spectra, default_start):
+    """The body of local_shifts_refined / local_shifts_raw_refined.  `spectra(pl)`: the K1 / K2 source of the movie
+    for the patch plan, made once the start is known; `default_start()`: ((t, 2) px, history) of the whole-frame
+    refinement of the same movie, the start without a `field`."""
     t, h, w = shape
+    _lib.normalize_frame_index(reference_frame, t)  # IndexError before any launch
     p = int(patch_sidelength)
     _check_patch_args("mean_except_current", p, h, w)
     cy, cx, _ = patch_origins(shape, p)
-    return p, planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev), cy, cx
+    pl = planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev)
+    gh, gw = len(cy), len(cx)
+    centres = lattice.centers_tensor(t, cy, cx)
+    if t == 1:
+        return torch.zeros((1, gh, gw, 2), dtype=torch.float32, device=dev), torch.zeros(0), centres
+    if field is None:
+        rigid, _ = default_start()
+        field = (rigid * pixel_spacing).transpose(0, 1)[:, :, None, None]
+    start = start_field_px(field, pixel_spacing, t, gh, gw)
+    shifts, hist = refine_patch_shifts(spectra(pl), tuple(shape), pl, p, start, reference_frame, max_iterations,
+                                       threshold)
+    return shifts.reshape(t, gh, gw, 2), hist, centres
 
 
 def local_shifts_refined(img, pixel_spacing, patch_sidelength, field, reference_frame, b_factor, frequency_range,
@@ -669,21 +709,10 @@ def local_shifts_refined(img, pixel_spacing, patch_sidelength, field, reference_
     as it is.  `field`: the (2, nt, nh, nw) Angstrom start field on the device, or None for the result of
     global_shifts_refined on the same stack at its default iteration settings.
     -> ((t, gh, gw, 2) px shifts, history, (t, gh, gw, 3) centres)."""
-    t = img.shape[0]
-    dev = img.device
-    _lib.normalize_frame_index(reference_frame, t)  # IndexError before any launch
-    p, pl, cy, cx = _local_refine_plan(img.shape, dev, patch_sidelength, pixel_spacing, b_factor, frequency_range)
-    gh, gw = len(cy), len(cx)
-    centres = lattice.centers_tensor(t, cy, cx)
-    if t == 1:
-        return torch.zeros((1, gh, gw, 2), dtype=torch.float32, device=dev), torch.zeros(0), centres
-    if field is None:
-        rigid, _ = global_shifts_refined(img, reference_frame, pixel_spacing, b_factor, frequency_range)
-        field = (rigid * pixel_spacing).transpose(0, 1)[:, :, None, None]
-    start = start_field_px(field, pixel_spacing, t, gh, gw)
-    shifts, hist = refine_patch_shifts(_patch_spectra(img, pl, central_box_stats(img)), tuple(img.shape), pl, p, start,
-                                       reference_frame, max_iterations, threshold)
-    return shifts.reshape(t, gh, gw, 2), hist, centres
+    return _local_shifts_refined(
+        img.shape, img.device, pixel_spacing, patch_sidelength, field, reference_frame, b_factor, frequency_range,
+        max_iterations, threshold, lambda pl: _patch_spectra(img, pl, central_box_stats(img)),
+        lambda: global_shifts_refined(img, reference_frame, pixel_spacing, b_factor, frequency_range))
 
 
 def local_shifts_raw_refined(rm: "RawMovie", pixel_spacing, patch_sidelength, field, reference_frame, b_factor,
@@ -692,23 +721,13 @@ def local_shifts_raw_refined(rm: "RawMovie", pixel_spacing, patch_sidelength, fi
     threshold; anything else raises McorrUnsupported before anything is launched (there is no silent fall-back).
     The default start is global_shifts_raw_refined on the same RawMovie."""
     _local_raw_check(rm)
-    t = rm.shape[0]
     dev = rm.raw.device
-    _lib.normalize_frame_index(reference_frame, t)
-    p, pl, cy, cx = _local_refine_plan(rm.shape, dev, patch_sidelength, pixel_spacing, b_factor, frequency_range)
-    if not _wave512_ok(pl.geom, True, True, 1):
-        raise _lib.McorrUnsupported(f"no raw patch kernel for {p}-px patches (1024 only)")
-    gh, gw = len(cy), len(cx)
-    centres = lattice.centers_tensor(t, cy, cx)
-    if t == 1:
-        return torch.zeros((1, gh, gw, 2), dtype=torch.float32, device=dev), torch.zeros(0), centres
-    if field is None:
-        rigid, _ = global_shifts_raw_refined(rm, reference_frame, pixel_spacing, b_factor, frequency_range)
-        field = (rigid * pixel_spacing).transpose(0, 1)[:, :, None, None]
-    start = start_field_px(field, pixel_spacing, t, gh, gw)
-    shifts, hist = refine_patch_shifts(_patch_spectra_raw(rm, pl), rm.shape, pl, p, start, reference_frame,
-                                       max_iterations, threshold)
-    return shifts.reshape(t, gh, gw, 2), hist, centres
+    _lib.normalize_frame_index(reference_frame, rm.shape[0])
+    _raw_patch_plan(rm.shape, dev, "mean_except_current", patch_sidelength, pixel_spacing, b_factor, frequency_range)
+    return _local_shifts_refined(
+        rm.shape, dev, pixel_spacing, patch_sidelength, field, reference_frame, b_factor, frequency_range,
+        max_iterations, threshold, lambda pl: _patch_spectra_raw(rm, pl),
+        lambda: global_shifts_raw_refined(rm, reference_frame, pixel_spacing, b_factor, frequency_range))
 
 
 # ------------------------------------------------------------------ a14/a16: spline lattice
@@ -783,6 +802,30 @@ def rigid_shifts_px(lattices, pixel_spacing):
     return torch.div(lattices[:, :, 0, 0], ps).contiguous()
 
 
+def _rigid_scratch(lib, t, h, w, dev):
+    """The rigid warp's scratch buffer (weight tables of t frames of h x w)."""
+    nbytes = C.c_int64(0)
+    check(lib.mc_warp_rigid_scratch_bytes(t, h, w, C.byref(nbytes)), "mc_warp_rigid_scratch_bytes")
+    return torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+
+
+def _field_scratch(lib, t, h, w, GH, GW, dev):
+    """The deformation-field warp's scratch buffer for (GH, GW) lattices."""
+    nbytes = C.c_int64(0)
+    check(lib.mc_warp_scratch_bytes(t, h, w, GH, GW, C.byref(nbytes)), "mc_warp_scratch_bytes")
+    return torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+
+
+def _sum_target(out_sum, want_sum, accumulate, h, w, dev):
+    """Where a raw warp's frame sum goes: the caller's `out_sum` (with `accumulate` the kernel adds to what it
+    holds), a new (h, w) buffer with `want_sum`, else None."""
+    if accumulate and out_sum is None:
+        raise ValueError("accumulate needs out_sum")
+    if out_sum is not None:
+        return out_sum
+    return torch.empty((h, w), dtype=torch.float32, device=dev) if want_sum else None
+
+
 def rigid_tables(img, lattices, pixel_spacing):
     """The per-frame weight tables of the rigid warp (rigid_base + rigid_weights: phase 1 of
     mc_warp_rigid_phase_t) enqueued on the CURRENT stream -> an opaque handle for
@@ -792,9 +835,7 @@ def rigid_tables(img, lattices, pixel_spacing):
     t, h, w = img.shape
     dev = img.device
     shifts_px = rigid_shifts_px(lattices, pixel_spacing)
-    nbytes = C.c_int64(0)
-    check(lib.mc_warp_rigid_scratch_bytes(t, h, w, C.byref(nbytes)), "mc_warp_rigid_scratch_bytes")
-    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+    scratch = _rigid_scratch(lib, t, h, w, dev)
     # phase 1 never touches the frames (only their geometry matters): tagged fp32 so that fp16 stacks of
     # any row length get their tables here, whichever kernel resamples them later
     check(lib.mc_warp_rigid_phase_t(ptr(img), STORE_F32, t, h, w, ptr(shifts_px), ptr(scratch), None, None, 1,
@@ -819,9 +860,7 @@ def rigid_tables_from_shifts(shifts, img_shape, pixel_spacing, grid_type):
     idx_t, w_t, w1 = _cached(("rigid_tail_taps", str(dev), t, grid_type), build)
     field = torch.empty((2, t), dtype=torch.float32, device=dev)
     shifts_px = torch.empty((t, 2), dtype=torch.float32, device=dev)
-    nbytes = C.c_int64(0)
-    check(lib.mc_warp_rigid_scratch_bytes(t, h, w, C.byref(nbytes)), "mc_warp_rigid_scratch_bytes")
-    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+    scratch = _rigid_scratch(lib, t, h, w, dev)
     check(lib.mc_rigid_tables_from_shifts(ptr(shifts.contiguous()), float(pixel_spacing), ptr(idx_t), ptr(w_t), ptr(w1),
                                           ptr(w1), t, h, w, ptr(field), ptr(shifts_px), ptr(scratch), stream_ptr(dev)),
           "mc_rigid_tables_from_shifts")
@@ -840,14 +879,12 @@ def warp(img, lattices, pixel_spacing, want_frames=True, want_sum=False, rigid=F
         img = img.float()  # fp16 rows that are not whole 8-sample units: widened once
     frames = torch.empty((t, h, w), dtype=torch.float32, device=dev) if want_frames else None
     total = torch.empty((h, w), dtype=torch.float32, device=dev) if want_sum else None  # the kernels store it
-    nbytes = C.c_int64(0)
     if rigid:
         if tables is None and RIGID_KERNEL_HOOK is not None:
             tables = rigid_tables(img, lattices, pixel_spacing)
         if tables is None:
             shifts_px = rigid_shifts_px(lattices, pixel_spacing)
-            check(lib.mc_warp_rigid_scratch_bytes(t, h, w, C.byref(nbytes)), "mc_warp_rigid_scratch_bytes")
-            scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+            scratch = _rigid_scratch(lib, t, h, w, dev)
             args = (ptr(img), storage_of(img), t, h, w, ptr(shifts_px), ptr(scratch), ptr(frames), ptr(total))
             check(lib.mc_warp_rigid_phase_t(*args, 0, stream_ptr(dev)), "mc_warp_rigid")
             return frames, total
@@ -860,8 +897,7 @@ def warp(img, lattices, pixel_spacing, want_frames=True, want_sum=False, rigid=F
             RIGID_KERNEL_HOOK(run)
         return frames, total
     _, _, GH, GW = lattices.shape
-    check(lib.mc_warp_scratch_bytes(t, h, w, GH, GW, C.byref(nbytes)), "mc_warp_scratch_bytes")
-    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+    scratch = _field_scratch(lib, t, h, w, GH, GW, dev)
     rc = lib.mc_warp_frames_t(ptr(img), storage_of(img), t, h, w, ptr(lattices), GH, GW, float(pixel_spacing),
                               ptr(scratch), ptr(frames), ptr(total), stream_ptr(dev))
     if rc == -2 and img.dtype != torch.float32:
@@ -878,9 +914,7 @@ def pixel_shifts(lattice, h, w, pixel_spacing):
     lib = _lib.load()
     dev = lattice.device
     _, GH, GW = lattice.shape
-    nbytes = C.c_int64(0)
-    check(lib.mc_warp_scratch_bytes(1, h, w, GH, GW, C.byref(nbytes)), "mc_warp_scratch_bytes")
-    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+    scratch = _field_scratch(lib, 1, h, w, GH, GW, dev)
     out = torch.empty((h, w, 2), dtype=torch.float32, device=dev)
     check(lib.mc_pixel_shifts(ptr(lattice.contiguous()), GH, GW, h, w, float(pixel_spacing),
                               ptr(scratch), ptr(out), stream_ptr(dev)), "mc_pixel_shifts")
@@ -907,36 +941,62 @@ def pixel_shifts_at(lattice, h, w, pixel_spacing, coords):
 POLYPHASE_FOURIER_SHIFT = False  # tests: force the x-polyphase form on frames that do not need it
 
 
+def _full_spectra_chunks(img, g, consume, polyphase=False):
+    """THE unmasked full-spectrum loop of the pruned engine (K1 + K2: no mask, filter or statistics) behind the
+    Fourier-shift and dose routines.  Per chunk of frames (_chunks; T1 and S together make the factor 2) the frames
+    a .. a+n-1 of the fp32 stack `img` are transformed into S and ``consume(a, n, S, T1, off, src)`` follows; T1 is
+    dead by then and free as T2.  `polyphase` (csrc/polyphase.hip): every frame enters as two jobs of (h, w/2), its
+    even and its odd columns -- `src` is the chunk's de-interleaved (2n, h, w/2) stack, evens first, and S holds 2n
+    spectra; otherwise `src` is `img`.  `g`: the full geometry of one job, `off`: the jobs' element offsets in
+    `src`.  Returns T1."""
+    lib = _lib.load()
+    t, h, w = img.shape
+    dev = img.device
+    k = 2 if polyphase else 1  # jobs per frame
+    wj = w // k
+    tw_row, tw_col = planmod.get_twiddles(wj, dev), planmod.get_twiddles(h, dev)
+    chunk, spans = _chunks(t, 2 * k * g.nkx * g.H * 8)
+    T1 = torch.empty((k * chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
+    S = torch.empty((k * chunk, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
+    st = stream_ptr(dev)
+    for a, n in spans:
+        if polyphase:
+            src = torch.cat([img[a:a + n, :, 0::2], img[a:a + n, :, 1::2]], dim=0).contiguous()  # (2n, h, w/2)
+            off = torch.arange(2 * n, device=dev, dtype=torch.int64) * (h * wj)
+        else:
+            src, off = img, torch.arange(a, a + n, device=dev, dtype=torch.int64) * (h * w)
+        check(_k1(lib, g, dev, src, off, wj, None, None, None, T1, tw_row, k * n, st), "xc rows forward")
+        check(_k2(lib, g, dev, T1, None, S, tw_col, k * n, st), "xc cols forward")
+        consume(a, n, S, T1, off, src)
+    return T1
+
+
+def _polyphase_geometry(h, w, what):
+    if w % 4:
+        raise NotImplementedError(f"frames of {w} columns: the polyphase {what} needs a width divisible by 4")
+    return planmod.full_geometry(h, w // 2)
+
+
 def _fourier_shift_polyphase(img, shifts):
     """fourier_shift for frames whose full spectrum does not fit one row line (csrc/polyphase.hip):
     even and odd columns are transformed as two (h, w/2) frames, one pointwise pass applies the
     radix-2 butterfly + phase ramp + inverse butterfly, the halves go back and are interleaved."""
     lib = _lib.load()
     t, h, w = img.shape
-    if w % 4:
-        raise NotImplementedError(f"frames of {w} columns: the polyphase Fourier shift needs a width divisible by 4")
+    g = _polyphase_geometry(h, w, "Fourier shift")
     dev = img.device
-    w2 = w // 2
-    g = planmod.full_geometry(h, w2)
-    tw_row, tw_col = planmod.get_twiddles(w2, dev), planmod.get_twiddles(h, dev)
     out = torch.empty_like(img)
-    per_frame = 2 * g.nkx * g.H * 8
-    chunk = max(1, min(t, WORKSPACE_BYTES // (2 * per_frame)))
-    T1 = torch.empty((2 * chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
-    S = torch.empty((2 * chunk, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
     st = stream_ptr(dev)
     shifts = shifts.to(dev, torch.float32).contiguous()
-    for a in range(0, t, chunk):
-        n = min(chunk, t - a)
-        sub = torch.cat([img[a:a + n, :, 0::2], img[a:a + n, :, 1::2]], dim=0).contiguous()  # (2n, h, w2)
-        off = torch.arange(2 * n, device=dev, dtype=torch.int64) * (h * w2)
-        check(_k1(lib, g, dev, sub, off, w2, None, None, None, T1, tw_row, 2 * n, st), "xc rows forward")
-        check(_k2(lib, g, dev, T1, None, S, tw_col, 2 * n, st), "xc cols forward")
+
+    def consume(a, n, S, T1, off, sub):
         check(lib.mc_polyphase_fourier_shift(ptr(S), ptr(shifts[a:a + n]), n, g.nkx, h, w, st),
               "mc_polyphase_fourier_shift")
-        res = _inverse_frames(lib, g, S, 2 * n, h, w2, dev, st, out=torch.empty_like(sub), off=off, T2=T1)
+        res = _inverse_frames(lib, g, S, 2 * n, h, w // 2, dev, st, out=torch.empty_like(sub), off=off, T2=T1)
         out[a:a + n, :, 0::2] = res[:n]
         out[a:a + n, :, 1::2] = res[n:]
+
+    _full_spectra_chunks(img, g, consume, polyphase=True)
     return out
 
 
@@ -947,9 +1007,8 @@ DOSE_COLUMN_MAJOR = True  # tests / A-B: False feeds the exposure-weighted pass 
 def _full_row_major_ok(h, w):
     """Frames the row-major full-spectrum kernels (csrc/full_fft.hip) take: power-of-two rows and
     columns, and the K3 detector's 5760 / 11520 columns and 4092 / 8184 rows (mixed radix)."""
-    pow2 = lambda n: n > 0 and (n & (n - 1)) == 0
-    rows_ok = (pow2(w) and 64 <= w <= 8192) or w in (5760, 11520)
-    cols_ok = (pow2(h) and 256 <= h <= 4096) or h in (4092, 8184)
+    rows_ok = (_pow2(w) and 64 <= w <= 8192) or w in (5760, 11520)
+    cols_ok = (_pow2(h) and 256 <= h <= 4096) or h in (4092, 8184)
     return FULL_ROW_MAJOR and rows_ok and cols_ok
 
 
@@ -962,13 +1021,11 @@ def _fourier_shift_row_major(img, shifts):
     pitch = lib.mc_full_spectrum_pitch(w)
     tw_row, tw_col = planmod.get_twiddles(w, dev), planmod.get_twiddles(h, dev)
     out = torch.empty_like(img)
-    per_frame = h * pitch * 8
-    chunk = max(1, min(t, WORKSPACE_BYTES // per_frame))
+    chunk, spans = _chunks(t, h * pitch * 8)
     S = torch.empty((chunk, h, pitch, 2), dtype=torch.float32, device=dev)
     st = stream_ptr(dev)
     shifts = shifts.to(dev, torch.float32).contiguous()
-    for a in range(0, t, chunk):
-        n = min(chunk, t - a)
+    for a, n in spans:
         off = torch.arange(a, a + n, device=dev, dtype=torch.int64) * (h * w)
         check(lib.mc_full_rows_forward(ptr(img), ptr(off), w, ptr(S), ptr(tw_row), n, h, w, pitch, st),
               "mc_full_rows_forward")
@@ -1010,15 +1067,14 @@ def _row_major_sums(shape, dev, forward_rows, shifts=None, pixel_spacing=1.0, do
     # 15.2 ms per 12 frames: that column kernel is bound by its radix-31 pass on 512-thread workgroups, not by how it
     # is fed).
     colmajor = DOSE_COLUMN_MAJOR and h in (4096, 4092)
-    chunk = max(1, min(t, WORKSPACE_BYTES // ((2 if colmajor else 1) * per_frame)))
+    chunk, spans = _chunks(t, (2 if colmajor else 1) * per_frame)
     S = torch.empty((chunk, h, pitch, 2), dtype=torch.float32, device=dev)
     ST = torch.empty((chunk, w // 2 + 1, h, 2), dtype=torch.float32, device=dev) if colmajor else None
     sums = torch.empty((int(with_dose) + int(want_plain), h, pitch, 2), dtype=torch.float32, device=dev)
     A = sums[0] if with_dose else None
     P = sums[-1] if want_plain else None
     st = stream_ptr(dev)
-    for a in range(0, t, chunk):
-        n = min(chunk, t - a)
+    for a, n in spans:
         forward_rows(a, n, S)
         sum_args = (None if shifts is None else ptr(shifts[a:a + n]), n, a, t, ptr(A), ptr(P), ptr(tw_col), h, w,
                     pitch, float(pixel_spacing), float(pre_exposure), float(dose_per_frame) if with_dose else 0.0,
@@ -1071,21 +1127,12 @@ def fourier_shift(img, shifts):
         if w % 4 == 0 and w <= 16384 and h <= 8192:
             return _fourier_shift_polyphase(img, shifts)  # too wide for one row line: even / odd columns
         raise
-    tw_row, tw_col = planmod.get_twiddles(w, dev), planmod.get_twiddles(h, dev)
     out = torch.empty_like(img)
-    per_frame = g.nkx * g.H * 8
-    chunk = max(1, min(t, WORKSPACE_BYTES // (2 * per_frame)))
-    T1 = torch.empty((chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
-    S = torch.empty((chunk, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
     st = stream_ptr(dev)
     shifts = shifts.to(dev, torch.float32).contiguous()
-    for a in range(0, t, chunk):
-        n = min(chunk, t - a)
-        off = torch.arange(a, a + n, device=dev, dtype=torch.int64) * (h * w)
-        check(_k1(lib, g, dev, img, off, w, None, None, None, T1, tw_row, n, st), "xc rows forward")
-        check(_k2(lib, g, dev, T1, None, S, tw_col, n, st), "xc cols forward")
-        # T1 is dead now and has the same footprint as T2: reuse it
-        _inverse_frames(lib, g, S, n, h, w, dev, st, shifts=shifts[a:a + n], out=out, off=off, T2=T1)
+    # T1 is dead after K2 and has the same footprint as T2: reuse it
+    _full_spectra_chunks(img, g, lambda a, n, S, T1, off, _: _inverse_frames(
+        lib, g, S, n, h, w, dev, st, shifts=shifts[a:a + n], out=out, off=off, T2=T1))
     return out
 
 
@@ -1125,29 +1172,16 @@ def _dose_weighted_sum_polyphase(img, pixel_spacing, dose_per_frame, pre_exposur
     """dose_weighted_sum for frames too wide for one row line: even / odd columns (csrc/polyphase.hip)."""
     lib = _lib.load()
     t, h, w = img.shape
-    if w % 4:
-        raise NotImplementedError(f"frames of {w} columns: the polyphase form needs a width divisible by 4")
+    g = _polyphase_geometry(h, w, "form")
     dev = img.device
-    w2 = w // 2
-    g = planmod.full_geometry(h, w2)
-    tw_row, tw_col = planmod.get_twiddles(w2, dev), planmod.get_twiddles(h, dev)
-    per_frame = 2 * g.nkx * g.H * 8
-    chunk = max(1, min(t, WORKSPACE_BYTES // (2 * per_frame)))
-    T1 = torch.empty((2 * chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
-    S = torch.empty((2 * chunk, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
     A = torch.empty((2, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
     st = stream_ptr(dev)
-    for a in range(0, t, chunk):
-        n = min(chunk, t - a)
-        sub = torch.cat([img[a:a + n, :, 0::2], img[a:a + n, :, 1::2]], dim=0).contiguous()
-        off = torch.arange(2 * n, device=dev, dtype=torch.int64) * (h * w2)
-        check(_k1(lib, g, dev, sub, off, w2, None, None, None, T1, tw_row, 2 * n, st), "xc rows forward")
-        check(_k2(lib, g, dev, T1, None, S, tw_col, 2 * n, st), "xc cols forward")
-        check(lib.mc_polyphase_dose_accumulate(ptr(S), n, a, t, ptr(A), g.nkx, h, w, float(pixel_spacing),
-                                               float(pre_exposure), float(dose_per_frame), float(voltage),
-                                               1 if a == 0 else 0, 1 if a + n >= t else 0, st),
-              "mc_polyphase_dose_accumulate")
-    halves = _inverse_frames(lib, g, A, 2, h, w2, dev, st)
+    _full_spectra_chunks(img, g, lambda a, n, S, *_: check(
+        lib.mc_polyphase_dose_accumulate(ptr(S), n, a, t, ptr(A), g.nkx, h, w, float(pixel_spacing),
+                                         float(pre_exposure), float(dose_per_frame), float(voltage),
+                                         1 if a == 0 else 0, 1 if a + n >= t else 0, st),
+        "mc_polyphase_dose_accumulate"), polyphase=True)
+    halves = _inverse_frames(lib, g, A, 2, h, w // 2, dev, st)
     out = torch.empty((h, w), dtype=torch.float32, device=dev)
     out[:, 0::2] = halves[0]
     out[:, 1::2] = halves[1]
@@ -1174,21 +1208,12 @@ def dose_weighted_sum(img, pixel_spacing, dose_per_frame, pre_exposure=0.0, volt
         if w % 4 == 0 and w <= 16384 and h <= 8192:
             return _dose_weighted_sum_polyphase(img, pixel_spacing, dose_per_frame, pre_exposure, voltage)
         raise
-    tw_row, tw_col = planmod.get_twiddles(w, dev), planmod.get_twiddles(h, dev)
-    per_frame = g.nkx * g.H * 8
-    chunk = max(1, min(t, WORKSPACE_BYTES // (2 * per_frame)))
-    T1 = torch.empty((chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
-    S = torch.empty((chunk, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
     A = torch.empty((1, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
     st = stream_ptr(dev)
-    for a in range(0, t, chunk):
-        n = min(chunk, t - a)
-        off = torch.arange(a, a + n, device=dev, dtype=torch.int64) * (h * w)
-        check(_k1(lib, g, dev, img, off, w, None, None, None, T1, tw_row, n, st), "xc rows forward")
-        check(_k2(lib, g, dev, T1, None, S, tw_col, n, st), "xc cols forward")
-        check(lib.mc_dose_accumulate(ptr(S), n, a, t, ptr(A), w, h, float(pixel_spacing), float(pre_exposure),
-                                     float(dose_per_frame), float(voltage), 1 if a == 0 else 0,
-                                     1 if a + n >= t else 0, st), "mc_dose_accumulate")
+    T1 = _full_spectra_chunks(img, g, lambda a, n, S, *_: check(
+        lib.mc_dose_accumulate(ptr(S), n, a, t, ptr(A), w, h, float(pixel_spacing), float(pre_exposure),
+                               float(dose_per_frame), float(voltage), 1 if a == 0 else 0, 1 if a + n >= t else 0, st),
+        "mc_dose_accumulate"))
     # inverse of the single accumulated spectrum: Fourier-shift path with a zero shift
     T2 = T1[:1] if g.ny == g.H else None
     return _inverse_frames(lib, g, A, 1, h, w, dev, st, T2=T2)[0]
@@ -1354,14 +1379,10 @@ def _global_spectra_raw(rm, reference_frame, pixel_spacing, b_factor, frequency_
     st = stream_ptr(dev)
     job_off = _cached(("frame_off", str(dev), t, h, w),
                       lambda: torch.arange(t, device=dev, dtype=torch.int64) * (h * w))
-    S = torch.empty((t, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
-    # row pass in chunks of frames when the transposed intermediate would be large (K3 formats: 0.4 GB per 10 frames)
-    per_job = g.nkx * g.ny * 8
-    chunk = max(1, min(t, WORKSPACE_BYTES // per_job))
-    T1 = torch.empty((chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
     chord = ptr(pl.chord) if (pl.chord is not None and USE_ROW_CHORDS) else None
-    for a in range(0, t, chunk):
-        n = min(chunk, t - a)
+
+    # row pass in chunks of frames when the transposed intermediate would be large (K3 formats: 0.4 GB per 10 frames)
+    def rows_pass(a, n, T1, T1b):
         off, sub = job_off[a:a + n], rm.sub[a:a + n]
         if planmod.native_rows(g):
             check(lib.mc_xc_rows_forward_raw(ptr(rm.raw), rm.kind, ptr(rm.gain), ptr(off), w, ptr(pl.mask), ptr(sub),
@@ -1377,9 +1398,8 @@ def _global_spectra_raw(rm, reference_frame, pixel_spacing, b_factor, frequency_
                                              ptr(rm.mean_rstd), ptr(T1), g, st), "mc_xc_rows_hot_correct")
         if a + n >= t and after_k1 is not None:
             after_k1()
-        check(_k2(lib, g, dev, T1, pl.filt, S[a:a + n], pl.tw_col, n, st), "xc cols forward")
-    del T1
-    return S, pl
+
+    return _filtered_spectra(pl, dev, t, rows_pass), pl
 
 
 def global_shifts_raw_refined(rm: RawMovie, reference_frame, pixel_spacing, b_factor, frequency_range, start=None,
@@ -1395,20 +1415,15 @@ def warp_rigid_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want
     """``warp(..., rigid=True)`` of the conditioned movie without materialising it (mc_warp_rigid_raw).
     `out_sum`: the (h, w) buffer the sum goes to (implies want_sum); with `accumulate` the sum is added to what it
     holds (mc_warp_rigid_raw_accumulate) -- the hot-pixel corrections of these frames too."""
-    if accumulate and out_sum is None:
-        raise ValueError("accumulate needs out_sum")
-    lib = _lib.load()
     t, h, w = rm.shape
     dev = rm.raw.device
+    total = _sum_target(out_sum, want_sum, accumulate, h, w, dev)
+    lib = _lib.load()
     frames = torch.empty((t, h, w), dtype=torch.float32, device=dev) if want_frames else None
-    total = out_sum if out_sum is not None else (torch.empty((h, w), dtype=torch.float32, device=dev)
-                                                 if want_sum else None)
     entry = lib.mc_warp_rigid_raw_accumulate if accumulate else lib.mc_warp_rigid_raw
     if tables is None:
         shifts_px = rigid_shifts_px(lattices, pixel_spacing)
-        nbytes = C.c_int64(0)
-        check(lib.mc_warp_rigid_scratch_bytes(t, h, w, C.byref(nbytes)), "mc_warp_rigid_scratch_bytes")
-        scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+        scratch = _rigid_scratch(lib, t, h, w, dev)
         phase = 0
     else:
         shifts_px, scratch = tables
@@ -1429,6 +1444,18 @@ def _local_raw_check(rm: RawMovie):
         raise _lib.McorrUnsupported("the fused local-motion route has no hot-pixel corrections: condition the movie")
 
 
+def _raw_patch_plan(shape, dev, reference_strategy, patch_sidelength, pixel_spacing, b_factor, frequency_range):
+    """(patch side, plan) of a patch estimator on a RawMovie, after the estimator's own argument rules; raises
+    McorrUnsupported for every patch size but the wave-per-row kernel's -- before anything is launched."""
+    _, h, w = shape
+    p = int(patch_sidelength)
+    _check_patch_args(reference_strategy, p, h, w)
+    pl = planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev)
+    if not _wave_rows_geometry(pl.geom):
+        raise _lib.McorrUnsupported(f"no raw patch kernel for {p}-px patches (1024 only)")
+    return p, pl
+
+
 def _patch_spectra_raw(rm: "RawMovie", pl):
     """_patch_spectra for a RawMovie: the 1024-px patch row pass reads the raw bytes and the gain
     (mc_xc_rows_forward_dual_raw) and subtracts each job's frame mean + box mean."""
@@ -1441,27 +1468,18 @@ def _patch_spectra_raw(rm: "RawMovie", pl):
     def spectra(off, ex, frames, expo_b=None, min_expo=None):
         if min_expo is None or min_expo < 1:
             raise _lib.McorrUnsupported("the raw patch kernel needs mask exponents >= 1")
-        njobs = int(off.numel())
         sub = rm.sub[torch.as_tensor(frames, device=dev)].contiguous()  # each job's frame mean + box mean
         dual = expo_b is not None
-        S = torch.empty((njobs, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
-        Sb = torch.empty_like(S) if dual else None
-        per_job = g.nkx * g.ny * 8 * (2 if dual else 1)
-        chunk = max(1, min(njobs, WORKSPACE_BYTES // per_job))
-        T1 = torch.empty((chunk, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
-        T1b = torch.empty_like(T1) if dual else None
-        for a in range(0, njobs, chunk):
-            n = min(chunk, njobs - a)
+
+        def rows_pass(a, n, T1, T1b):
             check(lib.mc_xc_rows_forward_dual_raw(ptr(rm.raw), rm.kind, ptr(rm.gain), h * w, ptr(off[a:a + n]), w,
                                                   ptr(ex[a:a + n]), ptr(expo_b[a:a + n]) if dual else None,
                                                   ptr(pl.mask), ptr(sub[a:a + n]), ptr(rm.mean_rstd), ptr(T1),
                                                   ptr(T1b), ptr(pl.tw_row), n, g,
                                                   ptr(pl.chord) if USE_ROW_CHORDS else None, st),
                   "mc_xc_rows_forward_dual_raw")
-            check(_k2(lib, g, dev, T1, pl.filt, S[a:a + n], pl.tw_col, n, st), "xc cols forward")
-            if dual:
-                check(_k2(lib, g, dev, T1b, pl.filt, Sb[a:a + n], pl.tw_col, n, st), "xc cols forward")
-        return (S, Sb) if dual else S
+
+        return _filtered_spectra(pl, dev, int(off.numel()), rows_pass, dual)
 
     return spectra
 
@@ -1474,15 +1492,11 @@ def patch_field_raw(rm: RawMovie, pixel_spacing, reference_frame, reference_stra
     subtracts each job's frame mean + box mean.  Raises McorrUnsupported for any shape that needs another kernel
     (patch sizes other than 1024, a hot-pixel threshold); there is no silent fall-back."""
     _local_raw_check(rm)
-    t, h, w = rm.shape
     dev = rm.raw.device
-    p = int(patch_sidelength)
-    _check_patch_args(reference_strategy, p, h, w)
-    pl = planmod.get_xc_plan(p, p, pixel_spacing, b_factor, frequency_range, dev)
-    if not _wave512_ok(pl.geom, True, True, 1):
-        raise _lib.McorrUnsupported(f"no raw patch kernel for {p}-px patches (1024 only)")
+    p, pl = _raw_patch_plan(rm.shape, dev, reference_strategy, patch_sidelength, pixel_spacing, b_factor,
+                            frequency_range)
     spectra = _patch_spectra_raw(rm, pl)
-    return _patch_field_core((t, h, w), dev, pl, p, pixel_spacing, reference_frame, reference_strategy,
+    return _patch_field_core(rm.shape, dev, pl, p, pixel_spacing, reference_frame, reference_strategy,
                              sub_pixel_refinement, temporal_smoothing, smoothing_window_size, None,
                              outlier_rejection, outlier_threshold, spectra)
 
@@ -1493,18 +1507,13 @@ def warp_field_raw(rm: RawMovie, lattices, pixel_spacing, want_frames=True, want
     (mc_warp_frames_raw).  Raises McorrUnsupported outside the raw kernel's shapes.  `out_sum` / `accumulate` as in
     warp_rigid_raw (mc_warp_frames_raw_accumulate)."""
     _local_raw_check(rm)
-    if accumulate and out_sum is None:
-        raise ValueError("accumulate needs out_sum")
-    lib = _lib.load()
     t, h, w = rm.shape
     dev = rm.raw.device
+    total = _sum_target(out_sum, want_sum, accumulate, h, w, dev)
+    lib = _lib.load()
     _, _, GH, GW = lattices.shape
     frames = torch.empty((t, h, w), dtype=torch.float32, device=dev) if want_frames else None
-    total = out_sum if out_sum is not None else (torch.empty((h, w), dtype=torch.float32, device=dev)
-                                                 if want_sum else None)
-    nbytes = C.c_int64(0)
-    check(lib.mc_warp_scratch_bytes(t, h, w, GH, GW, C.byref(nbytes)), "mc_warp_scratch_bytes")
-    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+    scratch = _field_scratch(lib, t, h, w, GH, GW, dev)
     entry = lib.mc_warp_frames_raw_accumulate if accumulate else lib.mc_warp_frames_raw
     check(entry(ptr(rm.raw), rm.kind, ptr(rm.gain), ptr(rm.mu), t, h, w, ptr(lattices.contiguous()), GH, GW,
                 float(pixel_spacing), ptr(scratch), ptr(frames), ptr(total), stream_ptr(dev)), "mc_warp_frames_raw")
@@ -1535,6 +1544,37 @@ def warp_dose_weighted_sum_raw(rm: RawMovie, lattices, pixel_spacing, rigid, dos
     dw, _ = _row_major_sums(rm.shape, rm.raw.device, forward_rows, pixel_spacing=pixel_spacing,
                             dose_per_frame=dose_per_frame, pre_exposure=pre_exposure, voltage=voltage)
     return dw, plain
+
+
+def corrected_sums(src, lattices, pixel_spacing, rigid, dose_per_frame=None, pre_exposure=0.0, voltage=300.0,
+                   want_plain=False, want_frames=False):
+    """THE three ways to make the aligned sum of a movie through `lattices` -> (sum, plain sum or None, frames or
+    None).  `src`: an fp32 / fp16 (t, h, w) stack on the device, or a RawMovie, whose warps read the raw bytes (and
+    raise McorrUnsupported where a fused kernel is missing).  `rigid`: the separable rigid warp.
+    * no `dose_per_frame`: the plain sum, from the warp itself;
+    * a dose and `want_frames`: the frames are an output anyway, so they are warped and then weighted
+      (dose_weighted_sum); `want_plain`: the plain sum too, from the same warp launch;
+    * a dose alone: warped, transformed and weighted a chunk at a time (warp_dose_weighted_sum[_raw]); the plain sum
+      alongside is built for a RawMovie only."""
+    ps = float(pixel_spacing)
+    raw = isinstance(src, RawMovie)
+    if raw:
+        warp_src = warp_rigid_raw if rigid else warp_field_raw
+    else:
+        warp_src = lambda *a, **kw: warp(*a, rigid=rigid, **kw)  # noqa: E731
+    if dose_per_frame is None:
+        frames, total = warp_src(src, lattices, ps, want_frames=want_frames, want_sum=True)
+        return total, None, frames
+    dose = (float(dose_per_frame), float(pre_exposure), float(voltage))
+    if want_frames:
+        frames, plain = warp_src(src, lattices, ps, want_frames=True, want_sum=want_plain)
+        return dose_weighted_sum(frames, ps, *dose), plain, frames
+    if raw:
+        total, plain = warp_dose_weighted_sum_raw(src, lattices, ps, rigid, *dose, want_plain)
+        return total, plain, None
+    if want_plain:
+        raise ValueError("the plain sum next to a streamed dose-weighted sum is built for a RawMovie only")
+    return warp_dose_weighted_sum(src, lattices, ps, rigid, *dose), None, None
 
 
 def _raw_rows_forward(rm, first, n, S):
@@ -1589,8 +1629,7 @@ FOURIER_CROP_SIZES = ("heights 512, 1024, 2048, 4096 and 8184 and widths 128, 25
 
 def fourier_crop_supported(h, w):
     """Frames mc_full_cols_crop bins by 2: (h, w) and (h/2, w/2) both sizes of the row-major transforms."""
-    pow2 = lambda n: n > 0 and (n & (n - 1)) == 0
-    return ((pow2(h) and 512 <= h <= 4096) or h == 8184) and ((pow2(w) and 128 <= w <= 8192) or w == 11520)
+    return ((_pow2(h) and 512 <= h <= 4096) or h == 8184) and ((_pow2(w) and 128 <= w <= 8192) or w == 11520)
 
 
 def fourier_crop(src):
@@ -1610,12 +1649,11 @@ def fourier_crop(src):
     pitch, pitch2 = lib.mc_full_spectrum_pitch(w), lib.mc_full_spectrum_pitch(w2)
     tw_col, tw_row2 = planmod.get_twiddles(h, dev), planmod.get_twiddles(w2, dev)
     out = torch.empty((t, h2, w2), dtype=torch.float32, device=dev)
-    chunk = max(1, min(t, WORKSPACE_BYTES // ((h * pitch + h2 * pitch2) * 8)))
+    chunk, spans = _chunks(t, (h * pitch + h2 * pitch2) * 8)
     S = torch.empty((chunk, h, pitch, 2), dtype=torch.float32, device=dev)
     S2 = torch.empty((chunk, h2, pitch2, 2), dtype=torch.float32, device=dev)
     st = stream_ptr(dev)
-    for a in range(0, t, chunk):
-        n = min(chunk, t - a)
+    for a, n in spans:
         if raw:
             _raw_rows_forward(src, a, n, S)
         else:
