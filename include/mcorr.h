@@ -601,6 +601,17 @@ int mc_xcg_peak_neighbourhood(const void* T2, const int* peaks, float* nb, int n
 /* caller-side frame sum (examples/ttMotion.py:398): sum[h*w] = sum_t frames[t]. */
 int mc_sum_frames(const float* frames, int nframes, int64_t hw, float* sum, void* stream);
 
+/* Calibration from raw bytes: the per-pixel statistics a gain reference (gain = mean of the good pixels / pixel
+ * mean) and a session-wide defect map (dead / hot / stuck pixels) are estimated from, as relion_estimate_gain
+ * and MotionCor2's gain tools do where the reference's example loads a file (examples/ttMotion.py:40-121).
+ * raw: contiguous (t, h, w) movie, u8 (is_i16 == 0) or i16 (is_i16 == 1).  sum, sumsq: (h, w) 64-bit
+ * accumulators; the call ADDS sum_f v and sum_f v^2 to them, exactly, so repeated calls accumulate a session
+ * (zero them first; the caller keeps sumsq below 2^63: 255^2 n for u8, 2^30 n for i16 after n frames).  One read
+ * of the movie's bytes, nothing written per frame; any h, w, t >= 1 (rows of whole 16-byte pieces at 16-byte
+ * addresses take the vector path, everything else one load per pixel with the same results). */
+int mc_raw_pixel_sums(const void* raw, int is_i16, int t, int h, int w, long long* sum, unsigned long long* sumsq,
+                      void* stream);
+
 /* ---- estimate_local_motion (estimate_motion_optimizer.py:28-439): loss + gradient ------
  * The reference rebuilds, every iteration and for every patch, rfftn(patch * mask), the
  * Fourier shift by the spline-predicted shifts, the band-pass and B-factor filters, the

@@ -35,6 +35,7 @@ from .api import (  # noqa: F401
     resample_deformation_field,
 )
 from ._lib import McorrError  # noqa: F401
+from .calibration import RawStatistics, estimate_defect_map, estimate_gain_reference  # noqa: F401
 from .data_io import read_deformation_field_from_csv, write_deformation_field_to_csv  # noqa: F401
 from .optimization_state import OptimizationState, OptimizationTracker  # noqa: F401
 from .multi_gpu import motion_correct_movies_sharded  # noqa: F401
@@ -80,5 +81,8 @@ __all__ = [
     "MoviePipeline",
     "RawMoviePipeline",
     "MovieResult",
+    "RawStatistics",
+    "estimate_defect_map",
+    "estimate_gain_reference",
 ]
 __version__ = "0.1.0"

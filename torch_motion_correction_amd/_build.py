@@ -28,7 +28,7 @@ SOURCES = [("xcg_fft.hip", "xcg_fft_p3", ["-DXCG_PART=3"]), ("xcg_fft.hip", "xcg
            ("warp.hip", "warp", ["-fno-slp-vectorize"]), ("plan_stats.hip", "plan_stats", []),
            ("field_post.hip", "field_post", []), ("local_motion.hip", "local_motion", []),
            ("polyphase.hip", "polyphase", []), ("xc_refine.hip", "xc_refine", []),
-           ("xc_refine_patches.hip", "xc_refine_patches", [])]
+           ("xc_refine_patches.hip", "xc_refine_patches", []), ("raw_accumulate.hip", "raw_accumulate", [])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 
