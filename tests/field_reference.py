@@ -1,10 +1,10 @@
-"""A float64 reference of the deformation-field warp (mc_warp_frames: csrc/warp.hip, kernels warp_main,
+"""A float64 reference of the deformation-field warp (mc_warp_frames: csrc/warp_field.hip, kernels warp_main,
 warp_field2, warp_field3, warp_field_slow) driven with a hand-made (t, 2, GH, GW) Angstrom lattice, the cases the
 GPU tests run (tests/test_field_kernels_float64.py) and the host emulation of the documented dispatch rules
 (tests/test_field_reference_host.py).  Built on tests/rigid_reference.py.
 
 What is restated in fp32 and what is float64.  The reference project's coordinate chain is the specification and
-warp.hip reproduces it operation by operation wherever FMA contraction is off.  Those parts are restated here in
+warp_field.hip reproduces it operation by operation wherever FMA contraction is off.  Those parts are restated here in
 numpy fp32, every operation rounded on its own, and are bit-reproducible by construction:
 
   axis tables (warp_axis_tables)  u = _grid_chain(fp32(fp32(p / (n - 1)) * (G - 1)), G); taps
@@ -73,7 +73,7 @@ PIXEL_SPACINGS = (1.0, 0.83, 1.3)
 
 
 def horner_weights_f32(t):
-    """cubic_coeffs of warp.hip under contract(off): ATen's Horner forms, every operation rounded to fp32."""
+    """cubic_coeffs of warp_common.h under contract(off): ATen's Horner forms, every operation rounded to fp32."""
     t = np.asarray(t, dtype=F32)
     A = F32(-0.75)
     a5, a8, a4 = F32(5) * A, F32(8) * A, F32(4) * A

@@ -1716,7 +1716,7 @@ def test_fp16_frames_through_the_field_warp(mc, dev, shape, grid, ps, monkeypatc
 
 def test_field_warp_with_more_frames_than_one_plan_block(mc, dev):
     """130 frames: the tile kernel keeps its per-frame plan entries in LDS 128 frames at a time
-    (warp.hip, warp_field3) -- frames 128, 129 come from the second block.  fp32 and fp16 frames,
+    (warp_field.hip, warp_field3) -- frames 128, 129 come from the second block.  fp32 and fp16 frames,
     frames and sum, against the oracle (correct_motion.py:81-185)."""
     t, h, w = 130, 416, 512
     g = torch.Generator().manual_seed(130)

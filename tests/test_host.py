@@ -483,7 +483,7 @@ def test_every_name_the_reference_exports_is_exported_here():
 
 
 def test_three_operation_division_is_the_correctly_rounded_quotient():
-    """warp.hip grid_chain divides by the invariant d = 0.5 n - 0.5 as q = c r; e = fma(-q, d, c);
+    """warp_common.h grid_chain divides by the invariant d = 0.5 n - 0.5 as q = c r; e = fma(-q, d, c);
     q' = fma(e, r, q).  Checked here against exact rational arithmetic (the reference divides)."""
     from fractions import Fraction
     import math

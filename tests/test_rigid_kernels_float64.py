@@ -1,5 +1,5 @@
-"""Every rigid-warp kernel (csrc/warp.hip: warp_rigid_dma, warp_rigid, warp_rigid_dma_h, warp_rigid_raw) against
-the float64 gather resampler of tests/rigid_reference.py at FRACTIONAL shifts, on frames of one to 1024 tiles, with
+"""Every rigid-warp kernel (csrc/warp_rigid.hip: warp_rigid_dma, warp_rigid, warp_rigid_dma_h;
+csrc/warp_rigid_raw.hip: warp_rigid_raw) against the float64 gather resampler of tests/rigid_reference.py at FRACTIONAL shifts, on frames of one to 1024 tiles, with
 no knife-edge mask and no excluded pixel (the share of pixels left out is 0).
 
 The kernels are driven through the C ABI (mc_warp_rigid_phase_t, mc_warp_rigid_raw, mc_warp_rigid_raw_accumulate)

@@ -106,7 +106,7 @@ def _invariant_shifts(n):
 
 @pytest.mark.parametrize("n", INVARIANT_SIZES)
 def test_floor_offset_takes_two_adjacent_values(n):
-    """What rigid_base / rigid_weights (csrc/warp.hip) assume: with u = the fp32 grid chain of c = fp32(p + s) and
+    """What rigid_base / rigid_weights (csrc/warp_rigid.hip) assume: with u = the fp32 grid chain of c = fp32(p + s) and
     S = min over ALL p of floor(u(p)) - p (rigid_base's reduction), d = floor(u(p)) - p - S is 0 or 1 for every p
     whose coordinate lies inside [0, n - 1].  rigid_weights writes all-zero weights for any other d, so a
     violation would be rows or columns silently zeroed by the kernels."""

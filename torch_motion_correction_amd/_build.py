@@ -22,10 +22,12 @@ SOURCES = [("xcg_fft.hip", "xcg_fft_p3", ["-DXCG_PART=3"]), ("xcg_fft.hip", "xcg
            ("xcg_fft.hip", "xcg_fft_p0", ["-DXCG_PART=0"]), ("xcg_fft.hip", "xcg_fft_p1", ["-DXCG_PART=1"]),
            ("xc_fft.hip", "xc_fft", []), ("full_fft.hip", "full_fft", ["-DFULL_FFT_PART=0"]),
            ("full_fft.hip", "full_fft_sums", ["-DFULL_FFT_PART=1"]), ("fourier_crop.hip", "fourier_crop", []),
-           # warp.hip: the SLP vectoriser turns the per-pixel coordinate chain into v_pk_* instructions fed by
-           # ~1300 v_mov_b32 per kernel and 90 more VGPRs (warp_field 215 -> 160); packed fp32 issues at half
-           # the scalar rate on gfx950, so nothing is gained for it
-           ("warp.hip", "warp", ["-fno-slp-vectorize"]), ("plan_stats.hip", "plan_stats", []),
+           # warp_*.hip (one object per kernel family): the SLP vectoriser turns the per-pixel coordinate chain
+           # into v_pk_* instructions fed by ~1300 v_mov_b32 per kernel and 90 more VGPRs (warp_field 215 -> 160);
+           # packed fp32 issues at half the scalar rate on gfx950, so nothing is gained for it
+           ("warp_field.hip", "warp_field", ["-fno-slp-vectorize"]), ("plan_stats.hip", "plan_stats", []),
+           ("warp_rigid.hip", "warp_rigid", ["-fno-slp-vectorize"]),
+           ("warp_rigid_raw.hip", "warp_rigid_raw", ["-fno-slp-vectorize"]),
            ("field_post.hip", "field_post", []), ("local_motion.hip", "local_motion", []),
            ("polyphase.hip", "polyphase", []), ("xc_refine.hip", "xc_refine", []),
            ("xc_refine_patches.hip", "xc_refine_patches", []), ("raw_accumulate.hip", "raw_accumulate", [])]
