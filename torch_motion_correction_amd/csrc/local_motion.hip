@@ -146,7 +146,9 @@ extern "C" {
 
 int mc_local_loss_tiles(int nkx, int nky, int* ntiles) {
   if (!ntiles || nkx < 1 || nky < 1) return MC_ERR_ARG;
-  *ntiles = (nkx * nky + LM_TILE - 1) / LM_TILE;
+  const int64_t nbins = (int64_t)nkx * nky;
+  if (nbins > 0x7fffffff - LM_TILE) return MC_ERR_ARG;  // the bin index is an int
+  *ntiles = (int)((nbins + LM_TILE - 1) / LM_TILE);
   return MC_OK;
 }
 
@@ -155,10 +157,12 @@ static int lm_launch(int mode, const void* spectra, const float* shifts_px, cons
                      void* stream) {
   if (!spectra || !shifts_px || !fy || !fx || !partial || (mode == 1 && !ab)) return MC_ERR_ARG;
   if (npatch < 1 || t < 1 || t > LM_MAXT || nkx < 1 || nky < 1 || npatch > 65535) return MC_ERR_ARG;
+  const int64_t nbins = (int64_t)nkx * nky;
+  if (nbins > 0x7fffffff - LM_TILE) return MC_ERR_ARG;  // the bin index is an int
   LmArgs a;
   a.P = (const float2*)spectra; a.shifts = shifts_px; a.fy = fy; a.fx = fx; a.hx = hx; a.ab = ab;
   a.out = partial; a.t = t; a.nkx = nkx; a.nky = nky;
-  a.ntiles = (nkx * nky + LM_TILE - 1) / LM_TILE;
+  a.ntiles = (int)((nbins + LM_TILE - 1) / LM_TILE);
   dim3 grid(a.ntiles, npatch), block(LM_WG);
   if (mode == 0) hipLaunchKernelGGL(local_loss_kernel<0>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(local_loss_kernel<1>, grid, block, 0, (hipStream_t)stream, a);
