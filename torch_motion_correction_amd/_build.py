@@ -20,8 +20,10 @@ LIB_PATH = os.path.join(PKG_DIR, "libmcorr.so")
 # family each (XCG_PART): the 97 generic-length kernels took five minutes as one translation unit
 SOURCES = [("xcg_fft.hip", "xcg_fft_p3", ["-DXCG_PART=3"]), ("xcg_fft.hip", "xcg_fft_p2", ["-DXCG_PART=2"]),
            ("xcg_fft.hip", "xcg_fft_p0", ["-DXCG_PART=0"]), ("xcg_fft.hip", "xcg_fft_p1", ["-DXCG_PART=1"]),
-           ("xc_fft.hip", "xc_fft", []), ("full_fft.hip", "full_fft", ["-DFULL_FFT_PART=0"]),
+           # the power-of-two engine, one object per pass family (K1 / K2-K3 / K4-K6)
+           ("xc_rows_fwd.hip", "xc_rows_fwd", []), ("full_fft.hip", "full_fft", ["-DFULL_FFT_PART=0"]),
            ("full_fft.hip", "full_fft_sums", ["-DFULL_FFT_PART=1"]), ("fourier_crop.hip", "fourier_crop", []),
+           ("xc_cols.hip", "xc_cols", []), ("xc_search.hip", "xc_search", []),
            # warp_*.hip (one object per kernel family): the SLP vectoriser turns the per-pixel coordinate chain
            # into v_pk_* instructions fed by ~1300 v_mov_b32 per kernel and 90 more VGPRs (warp_field 215 -> 160);
            # packed fp32 issues at half the scalar rate on gfx950, so nothing is gained for it

@@ -3,7 +3,7 @@
 // exposure-filtered frame sum (examples/ttMotion.py:331-351: rfft2 -> dose_weight_movie -> irfft2 ->
 // sum) run on.
 //
-// The pruned engine of xc_fft.hip hands its row pass output to the column pass TRANSPOSED
+// The pruned engine (xc_common.h) hands its row pass output to the column pass TRANSPOSED
 // (T1[job][kx][y]); with all nkx = W/2 + 1 bins kept that needs an LDS stage of nkx x RG bins per
 // workgroup (147 KB for W = 4096: one workgroup per CU, 1.1 TB/s -- 1.9 ms per 15 frames, two thirds
 // of correct_motion_fast's 12 ms per 40 x 4096^2 stack).  Here the spectrum stays row-major,

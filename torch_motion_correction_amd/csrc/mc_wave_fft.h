@@ -46,6 +46,16 @@ typedef float wf2 __attribute__((ext_vector_type(2)));  // (re, im)
 #define WF_N 2048       // complex points per line
 #define WF_SLAB 1024    // complex entries of a wave's LDS slab (8 KiB)
 
+#ifdef __HIPCC__
+__device__ __forceinline__ void wf_sync() {
+  // wave-private LDS hand-off: DS operations of one wave execute in order, so this only
+  // has to stop the compiler from moving a lane's reads above other lanes' writes
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+#endif
+
 MC_HD wf2 wf_make(float re, float im) { return wf2{re, im}; }
 MC_HD wf2 wf_from(cfloat c) { return wf2{c.x, c.y}; }
 MC_HD cfloat wf_to(wf2 v) { return cfloat{v.x, v.y}; }

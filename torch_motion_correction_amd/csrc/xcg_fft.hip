@@ -1,6 +1,7 @@
 // Pruned, separable 2-D real FFT engine for transform lengths that are not powers of two: the xcg_*
 // kernels (direct mixed-radix lines for the K3 formats, Bluestein chirp-z for everything else) with the
-// same pruning, layouts (T1, S, T2) and fused prologues / epilogues as xc_fft.hip.  Split from xc_fft.hip
+// same pruning, layouts (T1, S, T2) and fused prologues / epilogues as the power-of-two engine (xc_rows_fwd.hip,
+// xc_cols.hip, xc_search.hip; map of the passes in xc_common.h).  Split from it
 // in round 3 (one translation unit took five minutes to compile).
 #include "xc_common.h"
 
@@ -627,8 +628,7 @@ int mc_xcg_rows_inverse(const void* T2, float* part_val, int* part_idx, int* pea
     hipError_t e = hipMemsetD32Async((hipDeviceptr_t)best, pat, npairs, (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
   }
-  int near = (64 + g.RG - 1) / g.RG;
-  if (2 * near > ngrp) near = ngrp / 2;
+  const int near = xc_near_groups(g);
   float* bounds = part_val + (int64_t)npairs * ngrp;
   if (ngrp - 2 * near > 0)
     mc_launch_row_bounds((const cfloat*)T2, bounds, g.nkx, g.H, npairs, (hipStream_t)stream);
