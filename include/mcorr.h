@@ -444,7 +444,7 @@ int mc_rigid_tables_from_shifts(const float* shifts, float pixel_spacing, const 
 
 /* Rigid special case of mc_warp_frames: a (2,nt,1,1) field gives each frame ONE shift,
  * shifts_px[f] = (sy, sx) in pixels (device).  The coordinate chain is then separable
- * and the resample is a regular 5x5 separable correlation (see warp.hip).  Same
+ * and the resample is a regular 5x5 separable correlation (see warp_rigid.hip).  Same
  * outputs/contract as mc_warp_frames.  scratch: mc_warp_rigid_scratch_bytes(). */
 int mc_warp_rigid_scratch_bytes(int nframes, int h, int w, int64_t* bytes /*host*/);
 int mc_warp_rigid(const float* frames, int nframes, int h, int w, const float* shifts_px,

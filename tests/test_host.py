@@ -317,6 +317,52 @@ def test_raw_entry_points_validate_on_the_host():
     assert lib.mc_warp_rigid_raw(p[0], U8, None, p[2], 4, 64, 64, p[3], p[4], p[5], None, 0, None) == -1
 
 
+def test_storage_kind_entries_keep_their_order_of_argument_checks():
+    """The four entries that dispatch over the storage kind (u8, i16, f16, f32) return, for a kind outside
+    0..3 and for null pointers, the codes their argument checks have always returned, in the same order:
+    the two `condition` entries test the kind together with the pointers (MC_ERR_ARG), the two `raw_`
+    entries test the pointers first (MC_ERR_ARG), then the kind (MC_ERR_UNSUPPORTED: the caller falls
+    back), then the box (MC_ERR_ARG).  Every call ends in a check: nothing is launched."""
+    lib = _lib.load()
+    ARG, UNSUPPORTED = -1, -2
+    p = [ctypes.c_void_p(0x10000 * (i + 1)) for i in range(8)]  # aligned, never dereferenced
+    box, off_box = (16, 48, 16, 48), (16, 80, 16, 48)
+
+    def cond(kind, raw=p[0], out=p[3], t=4, hw=4096, mean_zero=1, sums=p[2]):
+        return lib.mc_condition_movie(raw, kind, p[1], t, hw, mean_zero, sums, out, None)
+
+    def cond_hot(kind, raw=p[0], thr=10.0, stats=p[2], out=p[4]):
+        return lib.mc_condition_movie_hot(raw, kind, p[1], 4, 64, 64, 1, thr, stats, p[3], out, None)
+
+    def stats(kind, raw=p[0], b=box, st=p[2], mu=p[3], sub=p[4], mr=p[5], t=4):
+        return lib.mc_raw_movie_stats(raw, kind, p[1], t, 64, 64, *b, 1, st, mu, sub, mr, None)
+
+    def detect(kind, raw=p[0], gain=p[1], b=box, w=64, keys=p[4], cap=100):
+        return lib.mc_raw_hot_detect(raw, kind, gain, 4, 64, w, *b, 10.0, p[2], p[3], keys, p[5], cap, p[6], p[7],
+                                     None)
+
+    for kind in (-1, 4):
+        assert cond(kind) == ARG and cond_hot(kind) == ARG, kind
+        assert stats(kind) == UNSUPPORTED and detect(kind) == UNSUPPORTED, kind
+        # pointers before the kind, the kind before the box and before the shape
+        assert stats(kind, raw=None) == ARG and detect(kind, gain=None) == ARG, kind
+        assert stats(kind, b=off_box) == UNSUPPORTED and detect(kind, b=off_box) == UNSUPPORTED, kind
+        assert detect(kind, w=60) == UNSUPPORTED, kind
+    for kind in (0, 1, 2, 3):
+        assert cond(kind, raw=None) == ARG and cond(kind, out=None) == ARG and cond(kind, sums=None) == ARG
+        assert cond(kind, t=0) == ARG and cond(kind, hw=0) == ARG
+        assert cond_hot(kind, raw=None) == ARG and cond_hot(kind, out=None) == ARG and cond_hot(kind, stats=None) == ARG
+        assert cond_hot(kind, thr=0.0) == ARG and cond_hot(kind, thr=float("nan")) == ARG
+        assert stats(kind, raw=None) == ARG and stats(kind, st=None) == ARG and stats(kind, mu=None) == ARG
+        assert stats(kind, sub=None) == ARG and stats(kind, mr=None) == ARG and stats(kind, t=0) == ARG
+        assert stats(kind, b=off_box) == ARG
+        assert detect(kind, raw=None) == ARG and detect(kind, gain=None) == ARG and detect(kind, keys=None) == ARG
+        assert detect(kind, cap=0) == ARG and detect(kind, b=off_box) == ARG
+        assert detect(kind, w=60) == UNSUPPORTED  # rows of whole 8-sample groups only
+        # u8 samples are read 8 bytes at a time, every other kind 16
+        assert detect(kind, raw=ctypes.c_void_p(0x10004 if kind == 0 else 0x10008)) == UNSUPPORTED
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "torch_motion_correction_amd")
     for fn in os.listdir(pkg):

@@ -1,6 +1,6 @@
 """Host checks of tests/hot_reference.py (no GPU): the float64 definitions agree with independent naive restatements,
 every input of tests/test_hot_kernels_float64.py has no undecided pixel, a numpy fp32 stand-in that follows the kernels'
-operation order (csrc/plan_stats.hip, csrc/full_fft.hip) lies inside every bound -- its worst error / bound is printed
+operation order (csrc/condition.hip, csrc/hot_pixels.hip and the engines' correction kernels) lies inside every bound -- its worst error / bound is printed
 and recorded in the GPU file's docstring -- and every comparison rejects a deliberately wrong stand-in."""
 
 import numpy as np

@@ -27,11 +27,12 @@ SOURCES = [("xcg_fft.hip", "xcg_fft_p3", ["-DXCG_PART=3"]), ("xcg_fft.hip", "xcg
            # warp_*.hip (one object per kernel family): the SLP vectoriser turns the per-pixel coordinate chain
            # into v_pk_* instructions fed by ~1300 v_mov_b32 per kernel and 90 more VGPRs (warp_field 215 -> 160);
            # packed fp32 issues at half the scalar rate on gfx950, so nothing is gained for it
-           ("warp_field.hip", "warp_field", ["-fno-slp-vectorize"]), ("plan_stats.hip", "plan_stats", []),
-           ("warp_rigid.hip", "warp_rigid", ["-fno-slp-vectorize"]),
+           ("warp_field.hip", "warp_field", ["-fno-slp-vectorize"]), ("warp_rigid.hip", "warp_rigid", ["-fno-slp-vectorize"]),
            ("warp_rigid_raw.hip", "warp_rigid_raw", ["-fno-slp-vectorize"]),
+           # conditioning, statistics and hot pixels of raw movies over cond_common.h; the plan's tables
+           ("hot_pixels.hip", "hot_pixels", []), ("condition.hip", "condition", []),
            ("field_post.hip", "field_post", []), ("local_motion.hip", "local_motion", []),
-           ("polyphase.hip", "polyphase", []), ("xc_refine.hip", "xc_refine", []),
+           ("polyphase.hip", "polyphase", []), ("plan_tables.hip", "plan_tables", []), ("xc_refine.hip", "xc_refine", []),
            ("xc_refine_patches.hip", "xc_refine_patches", []), ("raw_accumulate.hip", "raw_accumulate", [])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]

@@ -160,7 +160,7 @@ __global__ __launch_bounds__(WG) void full_cols_shift(cfloat* __restrict__ S, in
 }
 
 // Exposure filter of examples/ttMotion.py:331-351 (crit_exposure_bfactor = -1), as dose_accumulate_kernel
-// (plan_stats.hip) defines it: q_f(k) = exp(-0.5 N_f / N_c(|k|)), N_c = (0.24499 |k|^-1.6649 + 2.8141)
+// (polyphase.hip) defines it: q_f(k) = exp(-0.5 N_f / N_c(|k|)), N_c = (0.24499 |k|^-1.6649 + 2.8141)
 // vscale, N_f = pre + dose_per_frame (f + 1), |k| in 1/Angstrom clamped at 1e-6.
 __device__ __forceinline__ float full_dose_mh(int kx, int ky, int W, int H, float pixel_size, float vscale) {
   const float fy = full_fy(ky, H);

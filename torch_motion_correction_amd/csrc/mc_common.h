@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define MC_OK 0
 #define MC_ERR_ARG -1      // bad argument (null pointer, unsupported size ...)
@@ -54,4 +55,23 @@ static inline int mc_ilog2(int n) {
   int l = 0;
   while ((1 << l) < n) ++l;
   return l;
+}
+
+// Launch selection.  Kernels are templates on what they read and write; these call `go` with a tag type for
+// a runtime choice, so that exactly the instantiations an entry point can reach exist.
+template <class Go>
+static inline void mc_pick(bool v, Go&& go) {
+  if (v) go(std::true_type{});
+  else go(std::false_type{});
+}
+// the storage kind of a raw movie, MC_STORE_U8 .. MC_STORE_F32: go(std::integral_constant<int, K>), K = 0..3.
+// Entry points reject any other kind before they get here.
+template <class Go>
+static inline void mc_pick_kind(int kind, Go&& go) {
+  switch (kind) {
+    case 0: go(std::integral_constant<int, 0>{}); break;
+    case 1: go(std::integral_constant<int, 1>{}); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    default: go(std::integral_constant<int, 3>{}); break;
+  }
 }

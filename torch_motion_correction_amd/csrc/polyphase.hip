@@ -19,6 +19,9 @@
 // So the whole step is pointwise on (E, O): one pass over the two spectra, in place.
 // Layout: S[(job)][kx'][ky] complex as mc_xc_cols_forward writes it for the full geometry of an
 // (H, N2) frame (all H rows kept, natural order); job j = even columns of frame j, job j + n = odd.
+//
+// The exposure-weighted sum has the same two forms, and its plain one (mc_dose_accumulate, whose other user is
+// this path) lives here with the definition of the exposure filter.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -53,6 +56,55 @@ __global__ __launch_bounds__(256) void polyphase_shift_kernel(float2* __restrict
   const float2 D = make_float2(0.5f * (YA.x - YB.x), 0.5f * (YA.y - YB.y));
   *pe = P;
   *po = make_float2(wc * D.x + ws * D.y, wc * D.y - ws * D.x);  // conj(w) D
+}
+
+// ------------------------------------------------------------------ dose weighting
+// The plain form (mc_dose_accumulate: a spectrum S[f][kx][ky] of W / 2 + 1 columns) carries the DEFINITION of
+// the exposure filter; the polyphase form below and full_dose_mh (full_fft.hip) restate it.
+// Exposure filter of the reference's example pipeline (examples/ttMotion.py:331-351:
+// rfft2 -> dose_weight_movie(crit_exposure_bfactor=-1) -> irfft2 -> sum), accumulated in
+// Fourier space so that only ONE inverse transform per movie is needed:
+//   A[kx][ky] (+)= sum_f q_f(k) S[f][kx][ky],   q_f = exp(-0.5 N_f / N_c(k)),
+//   N_f = pre_exposure + dose_per_frame (f + 1)   (dose at the END of frame f),
+//   N_c(k) = (0.24499 k^-1.6649 + 2.8141) * voltage_scale,  k = |f| / pixel_size  [1/A]
+// (Grant & Grigorieff 2015), and on the last chunk A *= 1 / sqrt(sum_f q_f^2) over ALL frames
+// ("restore power").  |f| as torch_fourier_filter builds it: sqrt(fy^2 + fx^2) from
+// fftfreq / rfftfreq in fp32, clamped at 1e-6 (the DC term keeps weight ~1).  The third-party
+// package is absent from the reference tree and the reference has no test for this step:
+// semantics as restated in oracle/thirdparty_semantics.py, parity unpinned.
+__global__ void dose_accumulate_kernel(const float2* __restrict__ S, int nframes, int frame0,
+                                       int total_frames, float2* __restrict__ A, int W, int H,
+                                       int nkx, float pixel_size, float pre_exposure,
+                                       float dose_per_frame, float vscale, int first, int last) {
+#pragma clang fp contract(off)  // |f| and the weights in the fp32 op order of the torch expressions
+  const int64_t n = (int64_t)nkx * H;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int kx = (int)(i / H), ky = (int)(i - (int64_t)kx * H);
+  const int kk = (ky < (H + 1) / 2) ? ky : ky - H;
+  const float fy = (float)kk * (float)(1.0 / (double)H);
+  const float fx = (float)kx * (float)(1.0 / (double)W);
+  const float f = fmaxf(sqrtf(fy * fy + fx * fx) / pixel_size, 1e-6f);
+  const float ncrit = (0.24499f * powf(f, -1.6649f) + 2.8141f) * vscale;
+  const float mh = -0.5f / ncrit;
+  float2 a = first ? make_float2(0.f, 0.f) : A[i];
+  for (int j = 0; j < nframes; ++j) {
+    const float q = expf(mh * (pre_exposure + dose_per_frame * (float)(frame0 + j + 1)));
+    const float2 v = S[(int64_t)j * n + i];
+    a.x += q * v.x;
+    a.y += q * v.y;
+  }
+  if (last) {
+    float qq = 0.f;
+    for (int j = 0; j < total_frames; ++j) {
+      const float q = expf(mh * (pre_exposure + dose_per_frame * (float)(j + 1)));
+      qq += q * q;
+    }
+    const float r = 1.0f / sqrtf(qq);
+    a.x *= r;
+    a.y *= r;
+  }
+  A[i] = a;
 }
 
 // Exposure-weighted accumulation (mc_dose_accumulate, examples/ttMotion.py:331-351) in the same
@@ -105,6 +157,21 @@ __global__ __launch_bounds__(256) void polyphase_dose_kernel(const float2* __res
   }
   A[i] = ya;
   A[plane + i] = yb;
+}
+
+extern "C" int mc_dose_accumulate(const void* S, int nframes, int frame0, int total_frames, void* A, int W, int H,
+                                  float pixel_size, float pre_exposure, float dose_per_frame, float voltage,
+                                  int first, int last, void* stream) {
+  if (!S || !A || nframes < 1 || frame0 < 0 || total_frames < frame0 + nframes || W < 2 ||
+      H < 1 || !(pixel_size > 0.f) || !(dose_per_frame >= 0.f))
+    return MC_ERR_ARG;
+  const float vscale = voltage >= 300.f ? 1.0f : (voltage >= 200.f ? 0.8f : 0.75f);
+  const int nkx = W / 2 + 1;
+  const int64_t n = (int64_t)nkx * H;
+  hipLaunchKernelGGL(dose_accumulate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const float2*)S, nframes, frame0, total_frames, (float2*)A, W,
+                     H, nkx, pixel_size, pre_exposure, dose_per_frame, vscale, first, last);
+  return mc_check_launch();
 }
 
 extern "C" int mc_polyphase_dose_accumulate(const void* S, int nframes, int frame0, int total_frames, void* A,

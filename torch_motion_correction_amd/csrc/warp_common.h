@@ -5,7 +5,6 @@
 // FMA contraction is part of the bit-exact contract the float64 tests pin, so every helper here sets
 // its own mode at the start of its body and compiles the same wherever the header is included.
 #pragma once
-#include <type_traits>
 #include "mc_common.h"
 
 // ATen cubic convolution coefficients, A = -0.75 (UpSample.h / GridSamplerKernel.cpp); strict
@@ -113,14 +112,8 @@ static inline RigidTables rigid_tables_layout(float* scratch, int nframes, int h
 __attribute__((visibility("hidden"))) void mc_rigid_tables_launch(const float* shifts_px, int nframes, int h, int w,
                                                                   const RigidTables& t, hipStream_t s);
 
-// Launch selection.  The kernels are templates on what they write; these call `go` with the matching
-// std::bool_constant tags, so that exactly the combinations an entry point can reach are instantiated.
-// Entry points reject "neither frames nor sum" before they get here.
-template <class Go>
-static inline void mc_pick(bool v, Go&& go) {
-  if (v) go(std::true_type{});
-  else go(std::false_type{});
-}
+// Launch selection (mc_pick, mc_common.h) over what a warp kernel writes: `go` gets the matching
+// std::bool_constant tags.  Entry points reject "neither frames nor sum" before they get here.
 template <class Go>
 static inline void mc_pick_outputs(bool frames, bool sum, Go&& go) {  // go(FRAMES, SUM)
   if (frames && sum) go(std::true_type{}, std::true_type{});

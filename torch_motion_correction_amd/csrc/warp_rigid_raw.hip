@@ -396,6 +396,53 @@ __global__ __launch_bounds__(RIGID_LANES * 8, 2) void warp_rigid_raw(RigidRawArg
   }
 }
 
+// ------------------------------------------------------------------ hot pixels of a raw movie
+// Warp correction, step 1: hot pixel q of frame f adds delta * wy(py, qy) * wx(px, qx) to every output p
+// whose taps read q.  wy / wx are warp_rigid_raw's own weights from its tables (Wy[f][h][5],
+// Wx[f][5][w], S[f][2]: output p reads clip(p + S - 1 + k) with weight W[p][k], k = 0..4), summed over the
+// taps that clip onto q at the frame edge; outputs of the zero-outside rule have all-zero weights.  The
+// outputs lie in [q - S - 3, q - S + 1] per axis (clipped taps included); a 7 x 7 window around that covers
+// them.  One record (key = f h w + p, value) per window position, key HOT_NONE where the weight is zero.
+#define HOT_WIN 7
+#define HOT_NONE 0x7fffffffffffffffLL
+__global__ __launch_bounds__(256) void warp_rigid_hot_taps(const long long* __restrict__ keys,
+                                                           const float2* __restrict__ rv, int64_t n, int h,
+                                                           int w, const float* __restrict__ Wy,
+                                                           const float* __restrict__ Wx, const int* __restrict__ S,
+                                                           long long* __restrict__ rec_key,
+                                                           float* __restrict__ rec_val) {
+#pragma clang fp contract(off)  // delta * wy * wx in a fixed operation order (tests/hot_reference.py)
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= n * HOT_WIN * HOT_WIN) return;
+  const int64_t e = gid / (HOT_WIN * HOT_WIN);
+  const int tap = (int)(gid - e * (HOT_WIN * HOT_WIN));
+  const int64_t hw = (int64_t)h * w;
+  const long long key = keys[e];
+  const int f = (int)(key / hw);
+  const int64_t q = key - (long long)f * hw;
+  const int qy = (int)(q / w), qx = (int)(q - (int64_t)qy * w);
+  const int Sy = S[2 * f], Sx = S[2 * f + 1];
+  const int py = qy - Sy - 4 + tap / HOT_WIN, px = qx - Sx - 4 + tap % HOT_WIN;
+  long long out_key = HOT_NONE;
+  float val = 0.f;
+  if (py >= 0 && py < h && px >= 0 && px < w) {
+    float wy = 0.f, wx = 0.f;
+    for (int k = 0; k < 5; ++k) {
+      const int ry = min(max(py + Sy - 1 + k, 0), h - 1);
+      const int rx = min(max(px + Sx - 1 + k, 0), w - 1);
+      if (ry == qy) wy += Wy[((int64_t)f * h + py) * 5 + k];
+      if (rx == qx) wx += Wx[((int64_t)f * 5 + k) * w + px];
+    }
+    if (wy != 0.f && wx != 0.f) {
+      const float2 p = rv[e];
+      val = (p.x - p.y) * wy * wx;
+      out_key = (long long)f * hw + (int64_t)py * w + px;
+    }
+  }
+  rec_key[gid] = out_key;
+  rec_val[gid] = val;
+}
+
 // N2: the rigid warp straight from a raw u8 / i16 movie + gain reference (warp_rigid_raw); phase as in
 // mc_warp_rigid_phase.  Shapes it has no kernel for (w % 4, unaligned buffers): MC_ERR_UNSUPPORTED -- the
 // caller conditions the movie into an fp32 copy first.
@@ -443,6 +490,17 @@ int mc_warp_rigid_raw_accumulate(const void* raw, int storage, const float* gain
   if (!raw || !gain || !mu || !shifts_px || !scratch || !out_sum) return MC_ERR_ARG;
   return warp_rigid_raw_impl(raw, storage, gain, mu, nframes, h, w, shifts_px, scratch, out_frames, out_sum, phase,
                              true, stream);
+}
+
+int mc_warp_rigid_hot_taps(const long long* keys, const float* rv, int64_t n, int nframes, int h, int w,
+                           const float* scratch, long long* rec_key, float* rec_val, void* stream) {
+  if (!keys || !rv || !scratch || !rec_key || !rec_val || n < 0 || nframes < 1 || h < 2 || w < 2) return MC_ERR_ARG;
+  if (n == 0) return MC_OK;
+  const RigidTables t = rigid_tables_layout(const_cast<float*>(scratch), nframes, h, w);  // read only
+  const int64_t m = n * HOT_WIN * HOT_WIN;
+  hipLaunchKernelGGL(warp_rigid_hot_taps, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keys,
+                     (const float2*)rv, n, h, w, t.Wy, t.Wx, t.S, rec_key, rec_val);
+  return mc_check_launch();
 }
 
 }  // extern "C"

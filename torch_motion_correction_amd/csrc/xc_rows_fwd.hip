@@ -1,7 +1,8 @@
 // K1 of the pruned cross-correlation engine (xc_common.h has the map of the passes): forward row transforms,
 //   gather + (x - mean) * rstd * mask^e -> real FFT(W) -> first nkx bins -> T1[job][kx][ysupport]
 // by three engines -- a workgroup per row group (any power-of-two width), a wavefront per 4096-sample row
-// and a wavefront per 1024-sample patch row -- and the kernels of the fused frame statistics.
+// and a wavefront per 1024-sample patch row -- the kernels of the fused frame statistics, and the hot-pixel
+// correction of a raw movie's T1.
 #include "xc_common.h"
 
 // ------------------------------------------------------------------ K1: rows forward
@@ -861,12 +862,51 @@ __global__ void xc_stats_finalize(const double* __restrict__ acc_slots, double c
   out3[2] = stdf;
 }
 
+// ------------------------------------------------------------------ K1 from raw frames: hot pixels
+// K1 (raw) transformed A = (v - sub_f) * rstd * mask; a hot pixel's sample is
+// (r - sub_f) * rstd * mask, so every kept bin of its row gains  dA * exp(-2 pi i kx x / W),
+// dA = (r - v) * rstd * mask(y, x)  (the forward rfft convention of K1: no scale, negative exponent).
+// One workgroup per (frame, row) segment of the sorted list -- the workgroup of the segment's first entry;
+// the others return at once -- so every T1 element is written by one workgroup, in list order.
+__global__ __launch_bounds__(256) void xc_rows_hot_fix(const long long* __restrict__ keys, const float2* __restrict__ rv,
+                                                       int64_t n, int frame0, int njobs, int h, int w,
+                                                       const float* __restrict__ mask,
+                                                       const float* __restrict__ mean_rstd, cfloat* __restrict__ T1,
+                                                       int W, int nkx, int y0, int ny) {
+#pragma clang fp contract(off)  // dA and the sums in a fixed operation order (tests/hot_reference.py)
+  const int64_t e0 = blockIdx.x;
+  if (e0 >= n) return;
+  const long long seg = keys[e0] / w;  // f * h + y
+  if (e0 > 0 && keys[e0 - 1] / w == seg) return;
+  const int f = (int)(seg / h), y = (int)(seg - (long long)f * h);
+  if (f < frame0 || f >= frame0 + njobs || y < y0 || y >= y0 + ny) return;
+  const float rstd = mean_rstd[1];
+  cfloat* col = T1 + (int64_t)(f - frame0) * nkx * ny + (y - y0);
+  for (int kx = threadIdx.x; kx < nkx; kx += 256) {
+    float ar = 0.f, ai = 0.f;
+    for (int64_t e = e0; e < n && keys[e] / w == seg; ++e) {
+      const int x = (int)(keys[e] - seg * w);
+      const float m = mask ? mask[(int64_t)y * w + x] : 1.f;
+      if (m == 0.f) continue;
+      const float2 p = rv[e];
+      const float dA = (p.x - p.y) * rstd * m;
+      const int ph = (int)(((int64_t)kx * x) % W);  // exact phase index; the angle in revolutions ph / W
+      const float rev = (float)ph / (float)W;        // in [0, 1): v_sin / v_cos take revolutions
+      ar += dA * __builtin_amdgcn_cosf(rev);
+      ai -= dA * __builtin_amdgcn_sinf(rev);
+    }
+    cfloat* o = col + (int64_t)kx * ny;
+    o->x += ar;
+    o->y += ai;
+  }
+}
+
 // ------------------------------------------------------------------ host dispatch
 // mc_xc_row_engine(): 0 = automatic (wave-per-row kernel whenever the shape fits),
 // 1 = always the workgroup-per-row kernels (A/B timing and cross-checks of the engines).
 static int g_row_engine = 0;
 
-// go(A, B) with std::bool_constant tags of two runtime choices (as mc_pick in warp_common.h), so that exactly
+// go(A, B) with std::bool_constant tags of two runtime choices (as mc_pick in mc_common.h), so that exactly
 // the combinations an entry point can reach are instantiated
 template <class Go>
 static void xc_pick2(bool a, bool b, Go&& go) {
@@ -1133,6 +1173,18 @@ int mc_xc_rows_forward_raw(const void* raw, int storage, const float* gain, cons
                        mean_rstd, (cfloat*)T1, (const cfloat*)tw_row, g, b, (double*)nullptr, (const int2*)row_chord, 0,
                        gain, job_sub);
   });
+  return mc_check_launch();
+}
+
+// the sparse hot-pixel correction of T1 after mc_xc_rows_forward_raw (xc_rows_hot_fix)
+int mc_xc_rows_hot_correct(const long long* keys, const float* rv, int64_t n, int frame0, int njobs, int h, int w,
+                           const float* mask, const float* mean_rstd, void* T1, const mc_xc_geom* q, void* stream) {
+  if (!keys || !rv || !mean_rstd || !T1 || !q || n < 0 || frame0 < 0 || njobs < 1 || h < 1 || w < 1 || q->W != w ||
+      q->nkx < 1 || q->ny < 1 || q->y0 < 0 || q->y0 + q->ny > h || n > 0x7fffffffLL)
+    return MC_ERR_ARG;
+  if (n == 0) return MC_OK;
+  hipLaunchKernelGGL(xc_rows_hot_fix, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, keys, (const float2*)rv, n,
+                     frame0, njobs, h, w, mask, mean_rstd, (cfloat*)T1, q->W, q->nkx, q->y0, q->ny);
   return mc_check_launch();
 }
 
