@@ -612,6 +612,19 @@ int mc_sum_frames(const float* frames, int nframes, int64_t hw, float* sum, void
 int mc_raw_pixel_sums(const void* raw, int is_i16, int t, int h, int w, long long* sum, unsigned long long* sumsq,
                       void* stream);
 
+/* Rolling frame-group sums of a raw movie (MotionCor2 -Group, RELION --group_frames): out (t, h, w) int16, frame i
+ * = the sum of the input frames max(0, i - lo) .. min(t - 1, i + hi) with lo = (group - 1) / 2, hi = group / 2:
+ * the centred window of `group` frames clipped at the ends of the movie; group == 1 widens the movie.  raw:
+ * contiguous (t, h, w), storage MC_STORE_U8 or MC_STORE_I16 (anything else: MC_ERR_UNSUPPORTED).  Exact integers:
+ * a u8 window of min(group, t) <= 128 frames cannot leave int16; an i16 window may hold up to 32768 frames (longer
+ * windows of either kind: MC_ERR_UNSUPPORTED) and sets *overflow = 1 (device memory, zeroed by the caller) when a
+ * window sum leaves [-32768, 32767] -- the output of such a call is unspecified.  One read of the movie plus the
+ * re-read of each window's trailing frame, one write of the output; any h, w, t >= 1 (rows of whole 16-byte pieces
+ * at 16-byte addresses, input and output, take the vector path, everything else one load per pixel with the same
+ * results). */
+int mc_raw_group_frames(const void* raw, int storage, int t, int h, int w, int group, short* out, int* overflow,
+                        void* stream);
+
 /* ---- estimate_local_motion (estimate_motion_optimizer.py:28-439): loss + gradient ------
  * The reference rebuilds, every iteration and for every patch, rfftn(patch * mask), the
  * Fourier shift by the spline-predicted shifts, the band-pass and B-factor filters, the

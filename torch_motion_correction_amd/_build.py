@@ -33,7 +33,8 @@ SOURCES = [("xcg_fft.hip", "xcg_fft_p3", ["-DXCG_PART=3"]), ("xcg_fft.hip", "xcg
            ("hot_pixels.hip", "hot_pixels", []), ("condition.hip", "condition", []),
            ("field_post.hip", "field_post", []), ("local_motion.hip", "local_motion", []),
            ("polyphase.hip", "polyphase", []), ("plan_tables.hip", "plan_tables", []), ("xc_refine.hip", "xc_refine", []),
-           ("xc_refine_patches.hip", "xc_refine_patches", []), ("raw_accumulate.hip", "raw_accumulate", [])]
+           ("xc_refine_patches.hip", "xc_refine_patches", []), ("raw_accumulate.hip", "raw_accumulate", []),
+           ("raw_group.hip", "raw_group", [])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 

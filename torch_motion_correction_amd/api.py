@@ -1174,6 +1174,114 @@ def _motion_correct_raw_binned(movie, gain, pixel_spacing, binning, patch_sidele
     return tuple(x.to(out_dev) for x in out)
 
 
+# ------------------------------------------------------------------ frame groups (low-dose movies)
+
+
+def _check_group_args(movie, group):
+    """A (t, h, w) uint8 / int16 movie without an empty axis and a `group` its window sums exactly -> group as an
+    int; ValueError otherwise (before any device is touched)."""
+    if not isinstance(movie, torch.Tensor) or movie.dim() != 3 or min(movie.shape) < 1:
+        raise ValueError(f"movie must be (t, h, w), got {tuple(getattr(movie, 'shape', ()))}")
+    if movie.dtype not in RAW_DTYPES:
+        raise ValueError(f"movie must be a uint8 or int16 tensor, got {movie.dtype}")
+    return engine.check_group(group, movie.shape[0], movie.dtype)
+
+
+def group_frames_raw(movie, group, device=None):
+    """Rolling frame-group sums of a RAW uint8 / int16 (t, h, w) movie (MotionCor2 ``-Group``, RELION
+    ``--group_frames``): the int16 (t, h, w) movie whose frame ``i`` is the sum of the frames ``max(0, i - lo) ..
+    min(t - 1, i + hi)``, ``lo = (group - 1) // 2``, ``hi = group // 2`` -- the centred window of ``group`` frames,
+    clipped at the ends of the movie; ``group=1`` widens the movie.  At 0.05 - 0.3 e/A^2 per frame a single frame's
+    correlation peak drowns in noise; the estimators are then run on these sums.  ``(sum raw) * gain = sum (raw *
+    gain)``, so the result is a raw movie for every ``*_raw*`` function, with the same gain -- 2 bytes per pixel and
+    no fp32 copy (mc_raw_group_frames: one streaming pass).
+
+    Exact integers.  A uint8 window may hold ``min(group, t) <= 128`` frames (255 * 128 fits int16), an int16 window
+    32768; longer ones, a ``group`` that is not an int >= 1 and movies of any other type raise ValueError before any
+    device is touched.  An int16 window sum outside [-32768, 32767] raises ValueError naming ``group`` (a device
+    flag, the one device-to-host read)."""
+    group = _check_group_args(movie, group)
+    return _group_frames_raw(movie, group, device)
+
+
+@_on_gpu
+def _group_frames_raw(movie, group, device):
+    out_dev, dev, raw, _ = _stage_raw(movie, None, device)
+    return engine.group_frames_raw(raw, group).to(out_dev)
+
+
+def motion_correct_raw_grouped(movie, gain, pixel_spacing, group, patch_sidelength=None, reference_frame=None,
+                               b_factor=500, frequency_range=(300, 10), grid_type="catmull_rom", mean_zero=True,
+                               dose_per_frame=None, pre_exposure=0.0, voltage=300.0, return_plain_sum=False,
+                               device=None):
+    """Motion correction of a low-dose RAW uint8 / int16 movie: the estimate on the rolling sums of ``group``
+    neighbouring frames, the sums from the individual frames.  With ``grouped = group_frames_raw(movie, group)`` the
+    result is, bit for bit,
+
+    * ``patch_sidelength=None``: the field ``motion_correct_raw_fast(grouped, gain, pixel_spacing, reference_frame,
+      b_factor, frequency_range, mean_zero)`` returns and ``motion_correct_sum_fast_raw(movie, gain, field,
+      pixel_spacing, mean_zero, None, dose_per_frame, pre_exposure, voltage, return_plain_sum)`` -> ``(field, sum[,
+      plain sum])``;
+    * with a ``patch_sidelength``: ``field, centres`` of ``motion_correct_raw_patches(grouped, gain, pixel_spacing,
+      patch_sidelength, reference_frame, b_factor=b_factor, frequency_range=frequency_range, grid_type=grid_type,
+      mean_zero=mean_zero)`` and ``motion_correct_sum_raw(movie, gain, field, pixel_spacing, grid_type, mean_zero,
+      None, dose_per_frame, pre_exposure, voltage)`` -> ``(field, centres, sum)``; ``return_plain_sum`` belongs to
+      the whole-image route only.
+
+    A centred window of a steady drift averages to the frame's own shift, so the field of the grouped movie is applied
+    to the frames as it is.  Argument rules as ``group_frames_raw`` and the composed functions, all before any device
+    is touched; what those refuse on the device (McorrUnsupported for patch sizes without a kernel, ...) propagates.
+    There is no hot-pixel step: hot pixels of a grouped movie need a rule of their own."""
+    dose = _check_dose(dose_per_frame)  # every argument rule before any device
+    group = _check_group_args(movie, group)
+    _check_raw_args(movie, gain)
+    p = None
+    if patch_sidelength is not None:
+        p = _check_patch_sidelength(patch_sidelength)
+        if return_plain_sum:
+            raise ValueError("return_plain_sum belongs to the whole-image route (patch_sidelength=None)")
+    _check_fast_sum_args(dose, return_plain_sum)
+    return _motion_correct_raw_grouped(movie, gain, pixel_spacing, group, p, reference_frame, b_factor,
+                                       frequency_range, grid_type, mean_zero, dose, pre_exposure, voltage,
+                                       bool(return_plain_sum), device)
+
+
+@_on_gpu
+def _motion_correct_raw_grouped(movie, gain, pixel_spacing, group, patch_sidelength, reference_frame, b_factor,
+                                frequency_range, grid_type, mean_zero, dose, pre_exposure, voltage, want_plain, device):
+    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
+    t, h, w = raw.shape
+    ps = float(pixel_spacing)
+    grouped = engine.group_frames_raw(raw, group)
+    if patch_sidelength is None:
+        ref = t // 2 if reference_frame is None else int(reference_frame)
+        fused_sums = not engine.POLYPHASE_FOURIER_SHIFT and engine._full_row_major_ok(h, w)
+
+        def estimate(shifts_of, fused):  # motion_correct_raw_fast's routes, without the sums of the grouped movie
+            def run(src):
+                field = image_shifts_to_deformation_field(
+                    shifts_of(src, ref, ps, float(b_factor), tuple(frequency_range)), ps)
+                if fused and not fused_sums:  # where its fused sums refuse the shape it estimates on the conditioned movie
+                    raise McorrUnsupported(f"no fused Fourier-shift sums for frames of {h} x {w}")
+                return field
+            return run
+
+        field, _ = _raw_or_conditioned(grouped, gd, mean_zero, None, estimate(engine.global_shifts_raw, True),
+                                       estimate(engine.global_shifts, False))
+        sums = _motion_correct_sum_fast_raw(raw, gd, field, ps, mean_zero, None, dose, pre_exposure, voltage,
+                                            want_plain, None)
+        out = [field, *(sums if want_plain else (sums,))]
+    else:
+        # the public route itself on the device-resident grouped movie (its aligned sum of the groups is dropped):
+        # which shapes take its fused kernels is decided there
+        field, centers, _ = motion_correct_raw_patches(grouped, gd, ps, patch_sidelength, reference_frame,
+                                                       b_factor=b_factor, frequency_range=frequency_range,
+                                                       grid_type=grid_type, mean_zero=mean_zero)
+        out = [field, centers, _motion_correct_sum_raw(raw, gd, field, ps, grid_type, mean_zero, None, dose,
+                                                       pre_exposure, voltage, False, False, None)]
+    return tuple(x.to(out_dev) for x in out)
+
+
 @_on_gpu
 def get_pixel_shifts(frame, pixel_spacing, frame_deformation_grid, pixel_grid=None):
     """(h,w,2) per-pixel shifts in px from a (2,G_h,G_w) Angstrom lattice

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 
 import numpy as np
 import torch
@@ -1717,6 +1718,46 @@ def condition_movie(raw, gain=None, mean_zero=True, hot_pixel_threshold=None, re
     check(lib.mc_condition_movie(ptr(raw), _RAW_KINDS[raw.dtype], ptr(gain), t, h * w, 1 if mean_zero else 0,
                                  ptr(sums), ptr(out), stream_ptr(dev)), "mc_condition_movie")
     return (out, torch.zeros(t, dtype=torch.int32, device=dev)) if return_hot_counts else out
+
+
+GROUP_WINDOW_MAX = {torch.uint8: 128, torch.int16: 32768}  # frames of a window whose sum stays exact (raw_group.hip)
+
+
+def check_group(group, t, dtype):
+    """`group` as an int >= 1 (bools refused) whose window of min(group, t) frames the kernel sums exactly;
+    ValueError otherwise (before anything is launched)."""
+    try:
+        g = None if isinstance(group, bool) else operator.index(group)
+    except TypeError:
+        g = None
+    if g is None or g < 1:
+        raise ValueError(f"group must be an int >= 1, got {group!r}")
+    group = g
+    if min(group, t) > GROUP_WINDOW_MAX[dtype]:
+        raise ValueError(f"group={group}: a window of {min(group, t)} {dtype} frames is more than the "
+                         f"{GROUP_WINDOW_MAX[dtype]} whose sum is exact")
+    return group
+
+
+def group_frames_raw(raw, group):
+    """raw (t,h,w) u8 / i16 on the GPU -> the int16 (t,h,w) movie of rolling frame-group sums: frame i is the sum of
+    the frames max(0, i - (group - 1) // 2) .. min(t - 1, i + group // 2) (mc_raw_group_frames).  Exact integers;
+    an i16 window sum outside int16 raises ValueError (the flag's read is the one device-to-host copy).  Nothing
+    frame-sized is allocated besides the output."""
+    lib = _lib.load()
+    t, h, w = raw.shape
+    dev = raw.device
+    group = check_group(group, t, raw.dtype)
+    raw = raw.contiguous()
+    out = torch.empty((t, h, w), dtype=torch.int16, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    # (a reach of t frames covers the movie from any frame: 2 t stands for every larger group)
+    check(lib.mc_raw_group_frames(ptr(raw), _RAW_KINDS[raw.dtype], t, h, w, min(group, 2 * t), ptr(out), ptr(flag),
+                                  stream_ptr(dev)), "mc_raw_group_frames")
+    if raw.dtype == torch.int16 and int(flag.item()):
+        raise ValueError(f"group={group}: a sum of {min(group, t)} frames of this int16 movie leaves the int16 range "
+                         "[-32768, 32767]; use a smaller group")
+    return out
 
 
 def sum_frames(frames):
