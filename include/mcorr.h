@@ -40,7 +40,10 @@ typedef struct mc_xc_geom {
 /* Soft-edged disk mask (h*w floats): replaces torch_grid_utils.circle as called at
  * estimate_motion_xc.py:69-74 and :262-264 -- 1 where |p-c| < radius (c = (h//2,w//2)),
  * cos(pi/2 * d/smoothing_radius) of the exact Euclidean distance transform d to the
- * disk for 0 < d <= smoothing_radius, else 0.  halfw: scratch of h ints. */
+ * disk for 0 < d <= smoothing_radius, else 0.  A radius that no pixel is inside of
+ * (radius = 0: the test is strict, the centre pixel has distance 0) leaves no disk to
+ * measure a distance to: the table is all zeros, whatever the smoothing radius.
+ * halfw: scratch of h ints. */
 int mc_circle_mask(float* mask, int* halfw, int h, int w, float radius, float smoothing_radius,
                    void* stream);
 
