@@ -361,7 +361,7 @@ int mc_field_accumulate(const int* peaks, const float* nb, const int* frames, in
 int mc_field_smooth_center(const float* field_in, float* field_out, int t, int npatch, int window,
                            int subtract_mean, void* stream);
 
-/* ---- a14/a16: cubic spline grids ------------------------------------------------- */
+/* ---- a14/a16: cubic spline grids (csrc/field_tables.hip) -------------------------- */
 /* Evaluate a (c,nt,nh,nw) uniform cubic spline grid on the tensor-product lattice
  * given by per-axis tap tables: for lattice coordinate i of an axis, 4 sample indices
  * idx_*[4*i+k] and 4 weights w_*[4*i+k] (basis weights of the Catmull-Rom or B-spline
@@ -379,7 +379,10 @@ int mc_spline_points(const float* data, int c, int nt, int nh, int nw, const int
                      const int* idx_y, const float* w_y, const int* idx_x, const float* w_x, int64_t npoints,
                      float* out, void* stream);
 
-/* ---- a15/a17/a18: deformation-field warp ------------------------------------------ */
+/* ---- a15/a17/a18: deformation-field warp ------------------------------------------
+ * csrc/warp_field.hip (entry points, route rule, warp_field_plan / warp_field3 / warp_field_slow),
+ * csrc/warp_field_fallback.hip (warp_main, warp_field2: fp32 frames only), csrc/field_tables.hip (the
+ * lattice tables every route reads, mc_pixel_shifts*, mc_warp_scratch_bytes). */
 /* lattice: (nframes, 2, GH, GW) Angstrom shifts on the 10x-oversampled lattice
  * (evaluate_deformation_field_at_t, correct_motion.py:67-72).  For every frame:
  * bicubic/reflection upsample to per-pixel shifts (get_pixel_shifts,

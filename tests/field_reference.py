@@ -1,10 +1,11 @@
-"""A float64 reference of the deformation-field warp (mc_warp_frames: csrc/warp_field.hip, kernels warp_main,
-warp_field2, warp_field3, warp_field_slow) driven with a hand-made (t, 2, GH, GW) Angstrom lattice, the cases the
+"""A float64 reference of the deformation-field warp (mc_warp_frames: csrc/warp_field.hip with warp_field_plan,
+warp_field3, warp_field_slow and the route rule; csrc/warp_field_fallback.hip with warp_main, warp_field2; the
+tables of csrc/field_tables.hip) driven with a hand-made (t, 2, GH, GW) Angstrom lattice, the cases the
 GPU tests run (tests/test_field_kernels_float64.py) and the host emulation of the documented dispatch rules
 (tests/test_field_reference_host.py).  Built on tests/rigid_reference.py.
 
 What is restated in fp32 and what is float64.  The reference project's coordinate chain is the specification and
-warp_field.hip reproduces it operation by operation wherever FMA contraction is off.  Those parts are restated here in
+those three objects reproduce it operation by operation wherever FMA contraction is off.  Those parts are restated here in
 numpy fp32, every operation rounded on its own, and are bit-reproducible by construction:
 
   axis tables (warp_axis_tables)  u = _grid_chain(fp32(fp32(p / (n - 1)) * (G - 1)), G); taps

@@ -1,7 +1,8 @@
 """Shared pieces of tests/test_post_reference_host.py and tests/test_post_kernels_float64.py: the float64 definitions of
 the three small kernel families every patch estimate and every field warp passes through -- the leave-one-out reference
 spectra (mc_xc_ref_mean_except_current with lattice.leave_one_out_schedule), the temporal smoothing and centring of the
-patch field (mc_field_smooth_center), the cubic spline grids (spline.axis_taps with mc_spline_lattice / mc_spline_points)
+patch field (mc_field_smooth_center), the cubic spline grids (spline.axis_taps with mc_spline_lattice / mc_spline_points,
+csrc/field_tables.hip)
 and the plan's tables (mc_circle_mask, mc_xc_filter) -- with the error bound of each and the case lists.
 
 TEST INFRASTRUCTURE ONLY: numpy (and torch on the CPU for linspace / searchsorted, the two operations that DEFINE a spline

@@ -1,5 +1,6 @@
-"""Every deformation-field warp kernel (csrc/warp_field.hip: warp_main, warp_field2, warp_field3 fp32 / fp16 / raw u8 /
-raw i16 / ACCUM, warp_field_plan, warp_field_slow, warp_pixel_shifts, warp_pixel_shifts_at) against the float64
+"""Every deformation-field warp kernel (csrc/warp_field.hip: warp_field3 fp32 / fp16 / raw u8 / raw i16 / ACCUM,
+warp_field_plan, warp_field_slow; csrc/warp_field_fallback.hip: warp_main, warp_field2; csrc/field_tables.hip:
+warp_axis_tables, warp_etab, warp_pixel_shifts, warp_pixel_shifts_at) against the float64
 reference of tests/field_reference.py, through the C ABI with hand-made (t, 2, GH, GW) lattices: no spline, no
 estimator, no knife-edge mask and no excluded pixel.
 
@@ -41,7 +42,7 @@ frames without the pixels that have a midpoint candidate, sum.  Recorded, not as
   where the kernel's coordinate may be anywhere in [u_lo, u_hi] and the bound's leading term r D is the first-order
   effect of exactly that; everywhere else the headroom is that of the rigid kernels.
 
-Arithmetic-only mutations of warp_field.hip / warp_common.h, each run once (new tests of this file that fail / the
+Arithmetic-only mutations of warp_field.hip (as one file, before it was split by job) / warp_common.h, each run once (new tests of this file that fail / the
 older 1e-4 tests of test_gpu_parity.py and test_raw_local_motion.py):
 
   c[3] of cubic_coeffs_factored * (1 + 1e-5)                 0 of 34 / none.  |c3| <= 0.11, so the weight moves by

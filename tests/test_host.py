@@ -290,6 +290,77 @@ def test_fp16_stacks_never_reach_an_fp32_only_kernel():
     assert "#define MC_STORE_F16 2" in header and "#define MC_STORE_F32 3" in header and F32 == 3
 
 
+def test_field_warp_entry_points_reject_in_a_fixed_order():
+    """The return code of mc_warp_frames_t and mc_warp_frames_raw for inputs that reach each early return, with
+    pointers that are never dereferenced (no case gets as far as a launch).  What matters is the ORDER of the
+    checks where an input fails two of them: for fp16 storage the shape checks (w % 8, alignment, lattice density)
+    come before the null-pointer checks, so an unsupported shape with a null lattice is -2 (MC_ERR_UNSUPPORTED),
+    not -1 (MC_ERR_ARG) -- except a frame beyond 32-bit offsets, which is refused after them; for raw storage
+    every argument check comes before every shape check.  The expected codes were taken by running this test
+    against the library as it was before the route decision moved into one function (field_route, warp_field.hip):
+    it passed there unchanged."""
+    lib = _lib.load()
+    fake = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+    U8, I16, F16, F32 = 0, 1, 2, 3
+    FR, LAT, SCR, OUT, GAIN, MU = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000
+
+    def warp_t(storage, frames=FR, t=4, h=256, w=64, lattice=LAT, GH=10, GW=10, ps=1.0, scratch=SCR, out=OUT, out_sum=0):
+        return lib.mc_warp_frames_t(fake(frames), storage, t, h, w, fake(lattice), GH, GW, ps, fake(scratch), fake(out),
+                                    fake(out_sum), None)
+
+    for tag in (U8, I16, 7, -1):  # a bad storage tag wins over everything, null pointers included
+        assert warp_t(tag) == -2 and warp_t(tag, frames=0, lattice=0, scratch=0, out=0) == -2
+    fp16_shapes = [dict(w=68), dict(w=66), dict(frames=FR + 4), dict(frames=FR + 8), dict(GH=64, GW=64), dict(h=193, GH=11)]
+    for shape in fp16_shapes:  # fp16: the shape first ...
+        assert warp_t(F16, **shape) == -2, shape
+        assert warp_t(F16, lattice=0, **shape) == -2, shape
+        assert warp_t(F16, lattice=0, scratch=0, out=0, t=0, **shape) == -2, shape
+    assert warp_t(F16, h=193, lattice=0) == -1 and warp_t(F16, h=192, lattice=0) == -2  # 64 (GH - 1) <= 3 (h - 1), GH = 10
+    assert warp_t(F32, h=1) == -1 and warp_t(F16, h=1) == -2 and warp_t(F16, h=1, GH=1) == -1  # one row is a dense lattice
+    assert warp_t(F32, w=1) == -1 and warp_t(F16, w=1) == -2
+    # ... but not the 32-bit offset rule: with a bad argument that frame is MC_ERR_ARG
+    assert warp_t(F16, h=65536, w=32768, lattice=0) == -1 and warp_t(F16, h=65536, w=32768, out=0) == -1
+    assert warp_t(F16, h=65536, w=32772, lattice=0) == -2  # w % 8 != 0 still comes first
+    for storage in (F16, F32):
+        for null in ("frames", "lattice", "scratch"):
+            assert warp_t(storage, **{null: 0}) == -1, (storage, null)
+        assert warp_t(storage, out=0, out_sum=0) == -1  # no output requested
+        for bad in (dict(t=0), dict(w=0), dict(GH=0), dict(GW=0), dict(ps=0.0), dict(ps=-1.0),
+                    dict(ps=float("nan"))):
+            assert warp_t(storage, **bad) == -1, (storage, bad)
+        assert warp_t(storage, scratch=SCR + 4) == -1 and warp_t(storage, scratch=SCR + 8) == -1  # misaligned scratch
+    # fp32 shapes that only a fallback kernel takes are no error: with a bad argument they are MC_ERR_ARG
+    for shape in (dict(w=66), dict(frames=FR + 4), dict(GH=64, GW=64), dict(h=65536, w=32768)):
+        assert warp_t(F32, lattice=0, **shape) == -1, shape
+
+    def warp_raw(storage, raw=FR, gain=GAIN, mu=MU, t=4, h=256, w=64, lattice=LAT, GH=10, GW=10, ps=1.0, scratch=SCR,
+                 out=OUT, out_sum=0, entry=lib.mc_warp_frames_raw):
+        return entry(fake(raw), storage, fake(gain), fake(mu), t, h, w, fake(lattice), GH, GW, ps, fake(scratch),
+                     fake(out), fake(out_sum), None)
+
+    for tag in (F16, F32, 7, -1):
+        assert warp_raw(tag) == -2 and warp_raw(tag, raw=0, lattice=0) == -2
+    raw_shapes = {U8: [dict(w=72), dict(w=68)], I16: [dict(w=68), dict(w=66)]}  # raw w not a multiple of the unit
+    for storage in (U8, I16):
+        for null in ("raw", "gain", "mu", "lattice", "scratch"):
+            assert warp_raw(storage, **{null: 0}) == -1, (storage, null)
+        assert warp_raw(storage, out=0, out_sum=0) == -1
+        for bad in (dict(t=0), dict(h=1), dict(w=0), dict(GH=0), dict(GW=0), dict(ps=0.0), dict(ps=float("nan"))):
+            assert warp_raw(storage, **bad) == -1, (storage, bad)
+        assert warp_raw(storage, scratch=SCR + 8) == -1
+        shapes = raw_shapes[storage] + [dict(raw=FR + 8), dict(gain=GAIN + 2), dict(GH=64, GW=64),  # ... a dense lattice
+                                        dict(h=65536, w=32768)]
+        for shape in shapes:  # raw: every argument check first
+            assert warp_raw(storage, **shape) == -2, (storage, shape)
+            if "gain" not in shape:
+                assert warp_raw(storage, gain=0, **shape) == -1, (storage, shape)
+            assert warp_raw(storage, lattice=0, **shape) == -1 and warp_raw(storage, scratch=SCR + 4, **shape) == -1
+        # the accumulating entry needs the sum, whatever else it is given
+        acc = lib.mc_warp_frames_raw_accumulate
+        assert warp_raw(storage, entry=acc) == -1 and warp_raw(storage, entry=acc, w=68, out_sum=OUT) == -2
+        assert warp_raw(7, entry=acc) == -1 and warp_raw(7, entry=acc, out_sum=OUT) == -2
+
+
 def test_raw_entry_points_validate_on_the_host():
     """N2 entry points (mc_raw_movie_stats, mc_xc_rows_forward_raw, mc_warp_rigid_raw) check storage tags,
     shapes and pointers before any launch."""

@@ -1,7 +1,8 @@
 """The small kernels every patch estimate and every field warp passes through, against the float64 definitions of
 tests/post_reference.py: mc_xc_ref_mean_except_current fed by lattice.leave_one_out_schedule (schedule and kernel checked
 together, against the (t, t) table itself), mc_field_smooth_center (every window, both routes, the mean subtraction, one
-to three trips of the series loop, in place), spline.axis_taps with mc_spline_lattice / mc_spline_points through
+to three trips of the series loop, in place), spline.axis_taps with mc_spline_lattice / mc_spline_points
+(csrc/field_tables.hip: spline_lattice_kernel, spline_points_kernel) through
 engine.spline_lattice / engine.spline_points and the four public routes on top of them, and the plan's tables
 mc_circle_mask and mc_xc_filter called directly.  Every output goes into a NaN-filled buffer (the engine's own
 allocations through the `nan_empty` fixture), no element, frame or bin is left out of a comparison, and every test

@@ -24,11 +24,15 @@ SOURCES = [("xcg_fft.hip", "xcg_fft_p3", ["-DXCG_PART=3"]), ("xcg_fft.hip", "xcg
            ("xc_rows_fwd.hip", "xc_rows_fwd", []), ("full_fft.hip", "full_fft", ["-DFULL_FFT_PART=0"]),
            ("full_fft.hip", "full_fft_sums", ["-DFULL_FFT_PART=1"]), ("fourier_crop.hip", "fourier_crop", []),
            ("xc_cols.hip", "xc_cols", []), ("xc_search.hip", "xc_search", []),
-           # warp_*.hip (one object per kernel family): the SLP vectoriser turns the per-pixel coordinate chain
-           # into v_pk_* instructions fed by ~1300 v_mov_b32 per kernel and 90 more VGPRs (warp_field 215 -> 160);
-           # packed fp32 issues at half the scalar rate on gfx950, so nothing is gained for it
-           ("warp_field.hip", "warp_field", ["-fno-slp-vectorize"]), ("warp_rigid.hip", "warp_rigid", ["-fno-slp-vectorize"]),
-           ("warp_rigid_raw.hip", "warp_rigid_raw", ["-fno-slp-vectorize"]),
+           # warp_*.hip and field_tables.hip (one object per kernel family; the field warp is three objects over
+           # warp_field_common.h: production kernels, the two fallback kernels, lattice tables and splines): the SLP
+           # vectoriser turns the per-pixel coordinate chain into v_pk_* instructions fed by ~1300 v_mov_b32 per
+           # kernel and 90 more VGPRs (warp_field 215 -> 160); packed fp32 issues at half the scalar rate on gfx950,
+           # so nothing is gained for it
+           ("warp_field.hip", "warp_field", ["-fno-slp-vectorize"]),
+           ("warp_field_fallback.hip", "warp_field_fallback", ["-fno-slp-vectorize"]),
+           ("warp_rigid.hip", "warp_rigid", ["-fno-slp-vectorize"]), ("warp_rigid_raw.hip", "warp_rigid_raw", ["-fno-slp-vectorize"]),
+           ("field_tables.hip", "field_tables", ["-fno-slp-vectorize"]),
            # conditioning, statistics and hot pixels of raw movies over cond_common.h; the plan's tables
            ("hot_pixels.hip", "hot_pixels", []), ("condition.hip", "condition", []),
            ("field_post.hip", "field_post", []), ("local_motion.hip", "local_motion", []),

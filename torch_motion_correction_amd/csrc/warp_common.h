@@ -1,5 +1,5 @@
-// What more than one of the warp translation units uses (warp_rigid.hip, warp_rigid_raw.hip,
-// warp_field.hip): the strict-fp32 coordinate helpers, the tile geometry, the rigid warp's argument
+// What more than one of the warp translation units uses (warp_rigid.hip, warp_rigid_raw.hip, and the
+// field-warp objects through warp_field_common.h): the strict-fp32 coordinate helpers, the tile geometry, the rigid warp's argument
 // struct and weight tables, and the host helpers that pick a kernel's <frames, sum> instantiation.
 //
 // FMA contraction is part of the bit-exact contract the float64 tests pin, so every helper here sets
