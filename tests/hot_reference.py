@@ -1,7 +1,7 @@
 """float64 definitions, derived bounds, shared cases and comparisons for the conditioning and hot-pixel kernels
 (csrc/condition.hip: mc_condition_movie, mc_raw_movie_stats; csrc/hot_pixels.hip: mc_condition_movie_hot,
 mc_raw_hot_detect, mc_raw_hot_finalize, mc_hot_scatter_add; and with the engine each corrects, csrc/xc_rows_fwd.hip:
-mc_xc_rows_hot_correct, csrc/warp_rigid_raw.hip: mc_warp_rigid_hot_taps, csrc/full_fft.hip: mc_full_rows_hot_correct).  tests/test_hot_reference_host.py checks this file on the host (independent restatements,
+mc_xc_rows_hot_correct, csrc/warp_rigid_raw.hip: mc_warp_rigid_hot_taps, csrc/full_sums.hip: mc_full_rows_hot_correct).  tests/test_hot_reference_host.py checks this file on the host (independent restatements,
 an fp32 stand-in that follows the kernels' operation order, deliberately wrong stand-ins that every comparison must
 reject); tests/test_hot_kernels_float64.py runs the same comparisons on the kernels' output.
 

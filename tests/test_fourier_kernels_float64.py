@@ -1,5 +1,5 @@
 """Every Fourier-shift and exposure-sum kernel against the float64 definitions of tests/fourier_reference.py
-(fourier_shift64, exposure_weights64, shift_sums64): the row-major engine (csrc/full_fft.hip: row passes of 64 to
+(fourier_shift64, exposure_weights64, shift_sums64): the row-major engine (csrc/full_fft.hip and full_sums.hip: row passes of 64 to
 8192, 5760 and 11520 columns, column passes of 256 to 2048 rows, the radix-16 4096, the mixed-radix 4092 / 8184, the
 fused shift-sum pass in its four modes, row-major and column-major fed, one chunk and several), the pruned engine in
 its transposed layout (native, direct mixed-radix, chirp-z and odd unpacked lines; mc_dose_accumulate), the

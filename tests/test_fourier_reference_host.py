@@ -263,7 +263,7 @@ def test_angle_term_bounds_an_fp32_evaluation(h, w):
 
 @pytest.mark.parametrize("h,w", [(256, 256), (4092, 64), (121, 135)])
 def test_exposure_term_bounds_an_fp32_evaluation(h, w):
-    """The chain of csrc/full_fft.hip::full_dose_mh and the accumulation kernels in numpy fp32: k, powf, N_c,
+    """The chain of csrc/full_sums.hip::full_dose_mh and the accumulation kernels in numpy fp32: k, powf, N_c,
     -0.5 / N_c, N_f, expf, sum of squares, root, quotient."""
     t = 5
     ky = np.arange(h)

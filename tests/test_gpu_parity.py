@@ -1804,7 +1804,7 @@ def test_evaluate_deformation_field_on_scattered_points(mc, dev):
             assert float((got - ref).abs().max()) <= 2e-5 * max(1.0, float(ref.abs().max()))
 
 
-# ------------------------------------------------------------------ row-major full-spectrum kernels (full_fft.hip)
+# ------------------------------------------------------------------ row-major full-spectrum kernels (full_fft.hip, full_sums.hip)
 
 
 @pytest.mark.parametrize("shape", [(3, 256, 64), (2, 256, 256), (2, 512, 1024), (3, 1024, 512), (2, 2048, 256),

@@ -361,6 +361,155 @@ def test_field_warp_entry_points_reject_in_a_fixed_order():
         assert warp_raw(7, entry=acc) == -1 and warp_raw(7, entry=acc, out_sum=OUT) == -2
 
 
+def test_full_spectrum_and_generic_length_entry_points_reject_in_a_fixed_order():
+    """The return code of every early return of the row-major full-spectrum entry points (full_fft.hip,
+    full_sums.hip), of mc_xcg_rows_forward_raw and of the geometry and line checks of the generic-length engine
+    (xcg_common.h, reached through mc_xcg_cols_forward), with pointers that are never dereferenced: no case gets
+    as far as a launch.  Inputs that fail two checks at once pin the ORDER: arguments (MC_ERR_ARG, -1) come before
+    sizes (MC_ERR_UNSUPPORTED, -2) in the full-spectrum entries, except that the raw row pass looks at `kind`
+    between the two; the raw generic-length row pass looks at the storage tag first, then geometry, then the line,
+    then the pointers, then the line code.  The expected codes were taken by running this test against the library
+    as it was when full_fft.hip and xcg_fft.hip were each one file compiled several times under a macro: it passed
+    there unchanged."""
+    lib = _lib.load()
+    fake = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+    ARG, UNS, OK = -1, -2, 0
+    A, B, C_, D, E, F = (0x10000 * (i + 1) for i in range(6))  # 16-byte aligned, never dereferenced
+    good = dict(h=256, w=64, pitch=48)
+    bad_sizes = [dict(h=4000), dict(h=128), dict(h=8192), dict(w=4000), dict(w=32), dict(w=16384), dict(pitch=49),
+                 dict(pitch=32), dict(h=257)]
+
+    def rows_fwd(src=A, off=B, stride=64, S=C_, tw=D, n=1, h=256, w=64, pitch=48):
+        return lib.mc_full_rows_forward(fake(src), fake(off), stride, fake(S), fake(tw), n, h, w, pitch, None)
+
+    def rows_inv(S=A, out=B, off=C_, stride=64, tw=D, n=1, h=256, w=64, pitch=48):
+        return lib.mc_full_rows_inverse(fake(S), fake(out), fake(off), stride, fake(tw), n, h, w, pitch, None)
+
+    def rows_raw(kind, raw=A, gain=B, mu=C_, off=D, S=E, tw=F, n=1, h=256, w=64, pitch=48):
+        return lib.mc_full_rows_forward_raw(fake(raw), kind, fake(gain), fake(mu), fake(off), fake(S), fake(tw), n, h, w,
+                                            pitch, None)
+
+    def cols_shift(S=A, shifts=B, tw=C_, n=1, h=256, w=64, pitch=48):
+        return lib.mc_full_cols_shift(fake(S), fake(shifts), fake(tw), 1.0, n, h, w, pitch, None)
+
+    def transpose(S=A, ST=B, n=1, h=256, w=64, pitch=48):
+        return lib.mc_full_transpose(fake(S), fake(ST), n, h, w, pitch, None)
+
+    def hot(keys=A, rv=B, n=1, frame0=0, njobs=1, h=256, w=64, S=C_, pitch=48):
+        return lib.mc_full_rows_hot_correct(fake(keys), fake(rv), n, frame0, njobs, h, w, fake(S), pitch, None)
+
+    def sums(entry, S=A, shifts=B, nframes=2, frame0=0, total=2, acc=C_, plain=D, tw=E, h=256, w=64, pitch=48, ps=1.0,
+             dose=1.0):
+        return entry(fake(S), fake(shifts), nframes, frame0, total, fake(acc), fake(plain), fake(tw), h, w, pitch, ps,
+                     0.0, dose, 300.0, 1, 1, 1.0, None)
+
+    assert good == dict(h=256, w=64, pitch=lib.mc_full_spectrum_pitch(64))
+    for entry, nulls in ((rows_fwd, ("src", "off", "S", "tw")), (rows_inv, ("S", "out", "off", "tw")),
+                         (cols_shift, ("S", "shifts", "tw")), (transpose, ("S", "ST"))):
+        for null in nulls:
+            assert entry(**{null: 0}) == ARG, (entry.__name__, null)
+            assert entry(h=4000, **{null: 0}) == ARG, (entry.__name__, null)  # null pointer + unsupported size
+        assert entry(n=0) == ARG and entry(n=0, w=4000) == ARG and entry(n=-1, pitch=49) == ARG
+        for size in bad_sizes:
+            assert entry(**size) == UNS, (entry.__name__, size)
+    assert rows_fwd(src=A + 4) == UNS and rows_fwd(stride=65) == UNS and rows_fwd(src=A + 4, S=0) == ARG
+    assert rows_inv(out=B + 4) == UNS and rows_inv(stride=65) == UNS and rows_inv(out=B + 4, tw=0) == ARG
+    # the raw row pass: pointers, then the kind, then sizes and alignment (u8 pairs: 2 bytes, i16 pairs: 4, gain: 8)
+    for kind in (0, 1):
+        for null in ("raw", "gain", "mu", "off", "S", "tw"):
+            assert rows_raw(kind, **{null: 0}) == ARG and rows_raw(kind, h=4000, **{null: 0}) == ARG, (kind, null)
+        assert rows_raw(kind, n=0) == ARG
+        for size in bad_sizes:
+            assert rows_raw(kind, **size) == UNS, (kind, size)
+        assert rows_raw(kind, raw=A + 1) == UNS and rows_raw(kind, gain=B + 4) == UNS
+    assert rows_raw(1, raw=A + 2) == UNS
+    for kind in (2, 3, 4, -1):
+        assert rows_raw(kind) == UNS and rows_raw(kind, h=4000) == UNS
+        assert rows_raw(kind, gain=0) == ARG and rows_raw(kind, n=0) == ARG  # bad kind + null pointer
+    # the hot-pixel fix: arguments, sizes and the alignment of rv, and only then "nothing to do"
+    assert hot(n=0) == OK and hot(n=0, keys=0, rv=0) == OK
+    assert hot(n=0, h=4000) == UNS and hot(n=0, rv=B + 4) == UNS and hot(n=0, pitch=49) == UNS
+    assert hot(n=0, S=0) == ARG and hot(n=0, S=0, h=4000) == ARG and hot(n=0, njobs=0) == ARG and hot(n=0, frame0=-1) == ARG
+    assert hot(n=-1) == ARG and hot(n=1 << 31) == ARG and hot(n=1 << 31, h=4000) == ARG
+    assert hot(keys=0) == ARG and hot(rv=0) == ARG and hot(rv=0, w=4000) == ARG and hot(h=0) == ARG and hot(w=1) == ARG
+    assert hot(h=4000) == UNS and hot(rv=B + 4) == UNS
+    # the fused sums, row-major and column-major
+    for entry in (lib.mc_full_cols_shift_sum, lib.mc_full_cols_shift_sum_cm):
+        for bad in (dict(S=0), dict(acc=0, plain=0), dict(tw=0), dict(nframes=0), dict(frame0=-1), dict(total=1),
+                    dict(frame0=1), dict(shifts=0), dict(shifts=0, acc=0), dict(ps=0.0), dict(ps=-1.0),
+                    dict(ps=float("nan")), dict(dose=-1.0), dict(dose=float("nan")), dict(ps=0.0, plain=0)):
+            assert sums(entry, **bad) == ARG, bad
+            assert sums(entry, h=4000, **bad) == ARG, bad  # ... each of them before the sizes
+        for size in bad_sizes:
+            assert sums(entry, **size) == UNS, size
+            assert sums(entry, ps=0.0, acc=0, **size) == UNS, size  # the plain sum alone has no pixel size to check
+    for h in (256, 512, 1024, 2048):  # column-major copies: only for the columns that are read from one
+        assert sums(lib.mc_full_cols_shift_sum_cm, h=h) == UNS and sums(lib.mc_full_cols_shift_sum_cm, h=h, plain=0) == UNS
+        assert sums(lib.mc_full_cols_shift_sum_cm, h=h, shifts=0) == ARG  # P without shifts comes first
+        assert sums(lib.mc_full_cols_shift_sum_cm, h=h, ps=0.0) == ARG
+        assert sums(lib.mc_full_cols_shift_sum_cm, h=h, pitch=49) == UNS
+
+    # ---- the generic-length engine: geom_from_g, then line_from, then the entry's own pointers
+    def geom(**kw):
+        f = dict(W=5760, H=4092, nkx=100, kyp=50, kyn=50, y0=0, ny=4092, x0=0, x1=5760, RG=4)
+        f.update(kw)
+        return _lib.XcGeom(**f)
+
+    def line(M, keep=0, tw_m=A, chirp=B, bspec=C_):
+        return _lib.XcLine(tw_m, chirp, bspec, M, keep)
+
+    def cols_fwd(g=geom(), ln=line(4092), T1=D, S=E, n=1):
+        return lib.mc_xcg_cols_forward(fake(T1), None, fake(S), ln, n, g, None)
+
+    assert cols_fwd(g=None) == ARG and cols_fwd(g=None, ln=None) == ARG
+    for size in (dict(W=3), dict(W=16386), dict(W=8193), dict(H=1), dict(H=8193)):
+        assert cols_fwd(g=geom(**size)) == UNS, size
+        assert cols_fwd(g=geom(nkx=0, **size)) == UNS and cols_fwd(g=geom(**size), ln=None, T1=0) == UNS, size
+    for bad in (dict(nkx=0), dict(nkx=2882), dict(kyp=-1), dict(kyn=-1), dict(kyp=0, kyn=0), dict(kyp=4092, kyn=1),
+                dict(RG=0), dict(ny=0), dict(ny=4090), dict(RG=5, ny=4090), dict(y0=-4), dict(y0=4), dict(x0=-2),
+                dict(x1=5762), dict(x0=100, x1=100), dict(x0=1), dict(x1=5759)):
+        assert cols_fwd(g=geom(**bad)) == ARG, bad
+        assert cols_fwd(g=geom(**bad), ln=line(3000)) == ARG, bad  # the geometry before the line
+    assert cols_fwd(ln=None) == ARG and cols_fwd(ln=None, T1=0) == ARG
+    for null in ("tw_m", "chirp", "bspec"):
+        assert cols_fwd(ln=line(4092, **{null: 0})) == ARG and cols_fwd(ln=line(3000, **{null: 0})) == ARG, null
+    for M in (3000, 16, 32768, 5120 * 3):  # no line engine for M, or M outside 32 .. 16384
+        assert cols_fwd(ln=line(M)) == UNS and cols_fwd(ln=line(M), T1=0) == UNS and cols_fwd(ln=line(M, keep=-1)) == UNS, M
+    assert cols_fwd(ln=line(8192, keep=-1)) == ARG and cols_fwd(ln=line(8192, keep=8)) == ARG  # columns take no pruned plan
+    assert cols_fwd(ln=line(4096)) == UNS and cols_fwd(ln=line(4096), T1=0) == UNS  # chirp-z needs M >= 2 n - 1
+    assert cols_fwd(ln=line(8192, keep=8, chirp=0)) == ARG
+    for ln in (line(4092), line(8192)):  # a direct and a chirp-z plan that pass: the entry's pointers are next
+        assert cols_fwd(ln=ln, T1=0) == ARG and cols_fwd(ln=ln, S=0) == ARG and cols_fwd(ln=ln, n=0) == ARG
+
+    U8, I16, F16, F32 = 0, 1, 2, 3
+
+    def xcg_raw(storage, g=geom(), ln=line(2880), raw=A, gain=B, off=C_, mask=D, sub=E, mr=F, T1=A + 64, tw=B + 64, n=1):
+        return lib.mc_xcg_rows_forward_raw(fake(raw), storage, fake(gain), fake(off), 5760, fake(mask), fake(sub),
+                                           fake(mr), fake(T1), fake(tw), ln, n, g, None)
+
+    for tag in (F16, F32, 7, -1):  # the storage tag before everything, a missing geometry included
+        assert xcg_raw(tag) == UNS and xcg_raw(tag, g=None) == UNS and xcg_raw(tag, raw=0, ln=None) == UNS
+    for st in (U8, I16):
+        assert xcg_raw(st, g=None) == ARG and xcg_raw(st, g=geom(W=3)) == UNS and xcg_raw(st, g=geom(nkx=0)) == ARG
+        odd = geom(W=5761, x1=5761)
+        assert xcg_raw(st, g=odd) == UNS and xcg_raw(st, g=odd, ln=None) == UNS and xcg_raw(st, g=odd, raw=0) == UNS
+        assert xcg_raw(st, ln=None) == ARG and xcg_raw(st, ln=line(3000)) == UNS and xcg_raw(st, ln=line(3000), raw=0) == UNS
+        assert xcg_raw(st, ln=line(8192, keep=100)) == ARG  # a pruned plan must keep nkx + 1 outputs
+        assert xcg_raw(st, ln=line(2048, keep=101)) == ARG  # ... in M >= n + 2 keep - 1 points
+        for null in ("raw", "gain", "off", "mask", "sub", "mr", "T1", "tw"):
+            assert xcg_raw(st, **{null: 0}) == ARG, (st, null)
+        assert xcg_raw(st, n=0) == ARG
+        # a line code other than 22 / 23 (direct 2880 / 5760 points): chirp-z plans, the direct column lengths
+        others = [(geom(), line(8192)), (geom(), line(8192, keep=101)), (geom(W=8184, x1=8184), line(4092)),
+                  (geom(W=16368, x1=16368), line(8184)), (geom(W=1000, x1=1000), line(1024))]
+        for g, ln in others:
+            assert xcg_raw(st, g=g, ln=ln) == UNS, (st, g.W, ln.M, ln.keep)
+            assert xcg_raw(st, g=g, ln=ln, raw=0) == ARG and xcg_raw(st, g=g, ln=ln, n=0) == ARG  # the pointers first
+        # the staging tile beyond a CU's LDS: the last check, and an argument error
+        big = geom(W=11520, H=8184, nkx=2881, ny=8184, x1=11520, RG=6)
+        assert xcg_raw(st, g=big, ln=line(5760)) == ARG and xcg_raw(st, g=big, ln=line(5760), raw=0) == ARG
+
+
 def test_raw_entry_points_validate_on_the_host():
     """N2 entry points (mc_raw_movie_stats, mc_xc_rows_forward_raw, mc_warp_rigid_raw) check storage tags,
     shapes and pointers before any launch."""

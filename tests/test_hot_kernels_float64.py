@@ -1,6 +1,6 @@
 """The conditioning, raw-statistics and hot-pixel kernels (csrc/condition.hip, csrc/hot_pixels.hip, and the corrections
 that live with their engines: xc_rows_hot_fix of csrc/xc_rows_fwd.hip, warp_rigid_hot_taps of csrc/warp_rigid_raw.hip,
-full_rows_hot_fix of csrc/full_fft.hip)
+full_rows_hot_fix of csrc/full_sums.hip)
 against the float64 definitions of tests/hot_reference.py, whose docstring derives every bound.  No pixel, list entry or
 bin is skipped; every test asserts which entry points of libmcorr ran (a recorder around the loaded library).
 

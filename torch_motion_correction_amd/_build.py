@@ -16,13 +16,14 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 LIB_PATH = os.path.join(PKG_DIR, "libmcorr.so")
-# (source, object stem, extra flags), slowest first.  xcg_fft.hip is compiled as four objects, one kernel
-# family each (XCG_PART): the 97 generic-length kernels took five minutes as one translation unit
-SOURCES = [("xcg_fft.hip", "xcg_fft_p3", ["-DXCG_PART=3"]), ("xcg_fft.hip", "xcg_fft_p2", ["-DXCG_PART=2"]),
-           ("xcg_fft.hip", "xcg_fft_p0", ["-DXCG_PART=0"]), ("xcg_fft.hip", "xcg_fft_p1", ["-DXCG_PART=1"]),
+# (source, object stem, extra flags), slowest first.  The generic-length engine is four sources over xcg_common.h,
+# one kernel family each: its 101 kernels took five minutes as one translation unit, 75 s each side by side
+SOURCES = [("xcg_rows_inv.hip", "xcg_rows_inv", []), ("xcg_cols_inv.hip", "xcg_cols_inv", []),
+           ("xcg_rows_fwd.hip", "xcg_rows_fwd", []), ("xcg_cols_fwd.hip", "xcg_cols_fwd", []),
            # the power-of-two engine, one object per pass family (K1 / K2-K3 / K4-K6)
-           ("xc_rows_fwd.hip", "xc_rows_fwd", []), ("full_fft.hip", "full_fft", ["-DFULL_FFT_PART=0"]),
-           ("full_fft.hip", "full_fft_sums", ["-DFULL_FFT_PART=1"]), ("fourier_crop.hip", "fourier_crop", []),
+           ("xc_rows_fwd.hip", "xc_rows_fwd", []),
+           # row-major full spectra over full_common.h: per-frame transforms / fused sums and the raw row pass
+           ("full_fft.hip", "full_fft", []), ("full_sums.hip", "full_sums", []), ("fourier_crop.hip", "fourier_crop", []),
            ("xc_cols.hip", "xc_cols", []), ("xc_search.hip", "xc_search", []),
            # warp_*.hip and field_tables.hip (one object per kernel family; the field warp is three objects over
            # warp_field_common.h: production kernels, the two fallback kernels, lattice tables and splines): the SLP

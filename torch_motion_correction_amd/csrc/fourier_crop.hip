@@ -3,8 +3,8 @@
 //
 //   F = rfft2(x)  (H, W/2 + 1)  ->  G = rows -H/4 <= ky < H/4, columns 0 <= kx <= W/4  ->  irfft2(G, (H/2, W/2))
 //
-// The row passes are full_fft.hip's as they are (mc_full_rows_forward / _raw at (H, W), mc_full_rows_inverse at
-// (H/2, W/2), whose c2r ignores the imaginary parts of its DC and Nyquist bins); between them
+// The row passes are full_fft.hip's and full_sums.hip's as they are (mc_full_rows_forward / _raw at (H, W),
+// mc_full_rows_inverse at (H/2, W/2), whose c2r ignores the imaginary parts of its DC and Nyquist bins); between them
 //
 //   full_cols_crop  cols:  S column (pair), kx <= W/4 only -> FFT(H) -> keep ky < H/4 or ky >= 3H/4, * 1 / (H2 W2),
 //                          at ky' = ky (mod H/2) of an H/2-point line -> IFFT(H/2) -> S2[job][y'][pitch2]
@@ -16,7 +16,7 @@
 // (ky < H/4 -> [0, H/4), ky >= 3H/4 -> [H/4, H/2): the new Nyquist row H/4 comes from ky = 3H/4, the negative
 // side).  LDS per workgroup is therefore that of full_cols_shift: NC lines of lds_len(H) bins.  The inverse
 // transform reads the H-point twiddle table at stride 2.
-#include "full_cols.h"
+#include "full_common.h"
 #include "mc_fft.h"
 #include "mcorr.h"
 
@@ -62,7 +62,7 @@ extern "C" int mc_full_cols_crop(const void* S, void* S2, const void* tw_col, in
     constexpr int NC = full_nc<HV>(), WG = full_wg<HV>();                                                           \
     auto k = full_cols_crop<HV, NC, WG>;                                                                            \
     const size_t lds = NC * sizeof(cfloat) * (size_t)lds_len(HV);                                                   \
-    MC_FULL_SET_LDS(k, lds);                                                                                        \
+    MC_SET_LDS(k, lds);                                                                                             \
     hipLaunchKernelGGL(k, dim3(pitch2 / NC, njobs), dim3(WG), lds, (hipStream_t)stream, (const cfloat*)S,           \
                        (cfloat*)S2, W, pitch, pitch2, (const cfloat*)tw_col, scale);                                \
   } break;

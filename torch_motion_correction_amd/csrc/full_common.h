@@ -1,8 +1,9 @@
-// Helpers of the column passes over a ROW-MAJOR full spectrum S[job][y][pitch] (full_fft.hip,
-// fourier_crop.hip): which columns a workgroup owns, how it stages them in LDS, and the sizes the
-// row-major transforms take.
+// Shared by the passes over a ROW-MAJOR full spectrum S[job][y][pitch] (full_fft.hip, full_sums.hip,
+// fourier_crop.hip): which columns a workgroup owns, how it stages them in LDS, the sizes the row-major
+// transforms take, the dispatch over them and the row passes' grid.
 #pragma once
 #include "mc_fft.h"
+#include "mcorr.h"
 
 // blockIdx.x -> column pair: the 8 pairs of one 128-byte line group on one XCD, consecutively
 // (single columns, NC = 1: the same with 16 columns per group -- npairs is then the column count / 2
@@ -82,13 +83,10 @@ __device__ __forceinline__ void full_cols_store(cfloat* const* lines, cfloat* ba
   }
 }
 
-static bool full_rows_ok(int W) {
+static inline bool full_rows_ok(int W) {
   return (mc_is_pow2(W) && W >= 64 && W <= 8192) || W == 5760 || W == 11520;
 }
-static bool full_cols_ok(int H) { return (mc_is_pow2(H) && H >= 256 && H <= 4096) || H == 4092 || H == 8184; }
-
-#define MC_FULL_SET_LDS(k, bytes) \
-  (void)hipFuncSetAttribute((const void*)(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
+static inline bool full_cols_ok(int H) { return (mc_is_pow2(H) && H >= 256 && H <= 4096) || H == 4092 || H == 8184; }
 
 // columns per workgroup: pairs while two lines fit twice into a CU's LDS, single columns above;
 // threads per workgroup: 512 for 8184 rows (264 radix-31 butterflies per column)
@@ -96,3 +94,41 @@ template <int H>
 constexpr int full_nc() { return H > 4096 ? 1 : 2; }
 template <int H>
 constexpr int full_wg() { return H > 4096 ? 512 : MC_WG; }
+
+static inline bool full_sizes_ok(int H, int W, int pitch) {
+  return full_rows_ok(W) && full_cols_ok(H) && pitch >= W / 2 + 1 && (pitch % 16) == 0;
+}
+
+// Row passes: 8 rows per workgroup (the kernels' rows_per_wg), one grid column per job
+constexpr int FULL_ROWS_PER_WG = 8;
+static inline dim3 full_rows_grid(int H, int njobs) {
+  return dim3((H + FULL_ROWS_PER_WG - 1) / FULL_ROWS_PER_WG, njobs);
+}
+
+#define MC_FULL_CASE(V, ...) \
+  case V: {                  \
+    constexpr int L = V;     \
+    __VA_ARGS__              \
+  } break;
+// complex points of a row line (W / 2)
+#define MC_FULL_DISPATCH_ROWS(NV, ...)                                                              \
+  switch (NV) {                                                                                     \
+    MC_FULL_CASE(32, __VA_ARGS__) MC_FULL_CASE(64, __VA_ARGS__) MC_FULL_CASE(128, __VA_ARGS__)      \
+    MC_FULL_CASE(256, __VA_ARGS__) MC_FULL_CASE(512, __VA_ARGS__) MC_FULL_CASE(1024, __VA_ARGS__)   \
+    MC_FULL_CASE(2048, __VA_ARGS__) MC_FULL_CASE(4096, __VA_ARGS__) MC_FULL_CASE(2880, __VA_ARGS__) \
+    MC_FULL_CASE(5760, __VA_ARGS__)                                                                 \
+    default: return MC_ERR_UNSUPPORTED;                                                             \
+  }
+// rows of a column line (H) taken by the staged kernels (4096: the register-resident kernels)
+#define MC_FULL_DISPATCH_COLS(HV, ...)                                                             \
+  switch (HV) {                                                                                    \
+    MC_FULL_CASE(256, __VA_ARGS__) MC_FULL_CASE(512, __VA_ARGS__) MC_FULL_CASE(1024, __VA_ARGS__)  \
+    MC_FULL_CASE(2048, __VA_ARGS__) MC_FULL_CASE(4092, __VA_ARGS__) MC_FULL_CASE(8184, __VA_ARGS__) \
+    default: return MC_ERR_UNSUPPORTED;                                                            \
+  }
+
+// signed frequency of row ky of an H-point transform (torch.fft.fftfreq)
+__device__ __forceinline__ float full_fy(int ky, int H) {
+  const int kk = (ky < (H + 1) / 2) ? ky : ky - H;
+  return (float)kk * (float)(1.0 / (double)H);
+}

@@ -1,7 +1,7 @@
 // Hot-pixel removal of raw movies: the dense form (mc_condition_movie_hot writes the conditioned movie) and
 // the sparse form of the fused raw path (detection into a sorted list, the statistics' correction, and the
 // sorted scatter-add that applies correction records).  The correction of an engine's own output lives with that
-// engine: xc_rows_hot_fix in xc_rows_fwd.hip, full_rows_hot_fix in full_fft.hip, warp_rigid_hot_taps in
+// engine: xc_rows_hot_fix in xc_rows_fwd.hip, full_rows_hot_fix in full_sums.hip, warp_rigid_hot_taps in
 // warp_rigid_raw.hip.  Detection and replacement follow a fixed operation order, without FMA contraction.
 #include "cond_common.h"
 #include "mcorr.h"

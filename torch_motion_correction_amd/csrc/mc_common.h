@@ -50,6 +50,10 @@ static inline int mc_check_launch() {
   return e == hipSuccess ? MC_OK : (int)e;
 }
 
+// dynamic LDS above the 64 KiB a kernel may use by default: raise kernel k's limit before its launch
+#define MC_SET_LDS(k, bytes) \
+  (void)hipFuncSetAttribute((const void*)(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
+
 static inline bool mc_is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
 static inline int mc_ilog2(int n) {
   int l = 0;

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void polyphase_shift_kernel(float2* __restrict
 
 // ------------------------------------------------------------------ dose weighting
 // The plain form (mc_dose_accumulate: a spectrum S[f][kx][ky] of W / 2 + 1 columns) carries the DEFINITION of
-// the exposure filter; the polyphase form below and full_dose_mh (full_fft.hip) restate it.
+// the exposure filter; the polyphase form below and full_dose_mh (full_sums.hip) restate it.
 // Exposure filter of the reference's example pipeline (examples/ttMotion.py:331-351:
 // rfft2 -> dose_weight_movie(crit_exposure_bfactor=-1) -> irfft2 -> sum), accumulated in
 // Fourier space so that only ONE inverse transform per movie is needed:

@@ -1,6 +1,6 @@
 // Types and host helpers shared by the pruned, separable 2-D real FFT engines of the cross-correlation shift
 // search (reference: estimate_motion_xc.py:76-123 for whole frames, :338-355 for patches): xc_rows_fwd.hip,
-// xc_cols.hip and xc_search.hip (power-of-two lengths) and xcg_fft.hip (any other length: mixed radix /
+// xc_cols.hip and xc_search.hip (power-of-two lengths) and xcg_*.hip over xcg_common.h (any other length: mixed radix /
 // chirp-z).
 //
 // The reference materialises full spectra and full correlation maps.  Here the binary band-pass

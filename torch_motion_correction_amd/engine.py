@@ -1006,7 +1006,7 @@ DOSE_COLUMN_MAJOR = True  # tests / A-B: False feeds the exposure-weighted pass 
 
 
 def _full_row_major_ok(h, w):
-    """Frames the row-major full-spectrum kernels (csrc/full_fft.hip) take: power-of-two rows and
+    """Frames the row-major full-spectrum kernels (csrc/full_fft.hip, full_sums.hip) take: power-of-two rows and
     columns, and the K3 detector's 5760 / 11520 columns and 4092 / 8184 rows (mixed radix)."""
     rows_ok = (_pow2(w) and 64 <= w <= 8192) or w in (5760, 11520)
     cols_ok = (_pow2(h) and 256 <= h <= 4096) or h in (4092, 8184)
