@@ -62,6 +62,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from kernel_harness import rng as _rng
 from rigid_reference import KERNEL_SHIFT_POOL, conditioning_error
 
 F32 = np.float32
@@ -441,10 +442,6 @@ def check_scatter(before, after, keys, vals, limit, what):
 
 
 # ------------------------------------------------------------------ shared cases
-
-
-def _rng(*seed):
-    return np.random.default_rng([int(s) for s in seed])
 
 
 def make_gain(h, w, seed=5):

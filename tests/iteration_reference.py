@@ -90,6 +90,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from kernel_harness import rng as _rng
+
 F32 = np.float32
 U = 2.0 ** -24
 SQ2 = np.sqrt(2.0)
@@ -403,10 +405,6 @@ def check_update_patches(shifts, max_r, before_s, before_m, ref4, ref, q0, nq, w
 
 
 # ------------------------------------------------------------------ shared cases
-
-
-def _rng(*seed):
-    return np.random.default_rng([int(s) for s in seed])
 
 
 def freqs(nkx, nky):

@@ -1,0 +1,240 @@
+"""What the float64 kernel tests (tests/test_*_kernels_float64.py and their neighbours) measure with, defined once:
+which entry points of libmcorr ran (Recorder, `calls`), that nothing was written outside an output buffer (nan_buffer,
+assert_guards, nan_empty), the inputs (float_stack, raw_movie, gain, raw_setup), the worst error over bound per
+output family (ratios_fixture, worse) and the engine's test switches (`switches`).  tests/test_kernel_harness_host.py
+pins every one of them on the CPU.
+
+A test module takes a fixture with `from kernel_harness import calls  # noqa: F401`."""
+
+import numpy as np
+import pytest
+import torch
+
+GUARD = 8  # NaN words kept on either side of an output buffer
+
+
+# ------------------------------------------------------------------ the package, the library, which entry points ran
+
+
+@pytest.fixture(scope="module")
+def mc():
+    import torch_motion_correction_amd as m
+
+    return m
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from torch_motion_correction_amd import _lib
+
+    return _lib.load()
+
+
+class Recorder:
+    """The loaded library with the names and the arguments of the entry points that are CALLED written down, in
+    order.  Looking an entry point up records nothing."""
+
+    def __init__(self, lib):
+        self._lib, self.names, self.args = lib, [], {}
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*a):
+            self.names.append(name)
+            self.args.setdefault(name, []).append(a)
+            return fn(*a)
+
+        return call
+
+    def count(self, name):
+        return self.names.count(name)
+
+    def clear(self):
+        del self.names[:]
+        self.args.clear()
+
+    def ran(self, *want, absent=()):
+        for name in want:
+            assert self.count(name) >= 1, f"{name} did not run ({sorted(set(self.names))})"
+        for name in absent:
+            assert self.count(name) == 0, f"{name} ran ({sorted(set(self.names))})"
+
+    def only(self, name, times):
+        assert self.names == [name] * times, f"expected {times} x {name}, ran {self.names}"
+
+
+@pytest.fixture
+def calls(monkeypatch):
+    from torch_motion_correction_amd import _lib
+
+    rec = Recorder(_lib.load())
+    monkeypatch.setattr(_lib, "load", lambda: rec)
+    return rec
+
+
+# ------------------------------------------------------------------ NaN-filled and NaN-guarded buffers
+
+
+@pytest.fixture
+def nan_empty(monkeypatch):
+    """torch.empty hands out NaN-filled floating-point buffers: what a kernel leaves unwritten fails its comparison."""
+    real = torch.empty
+
+    def empty(*a, **k):
+        out = real(*a, **k)
+        return out.fill_(float("nan")) if out.is_floating_point() else out
+
+    monkeypatch.setattr(torch, "empty", empty)
+
+
+def nan(shape, dev):
+    return torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+
+
+def nan_buffer(shape, dev, offset=0):
+    """A NaN-filled fp32 buffer of `shape` that starts `offset` floats past a 16-byte boundary, inside a larger
+    NaN-filled allocation -> (view, whole allocation)."""
+    n = int(np.prod(shape))
+    lead = 4 * ((GUARD + 3) // 4) + offset
+    flat = torch.full((lead + n + GUARD,), float("nan"), dtype=torch.float32, device=dev)
+    assert flat.data_ptr() % 16 == 0
+    view = flat[lead:lead + n].view(*shape)
+    assert view.data_ptr() % 16 == (4 * offset) % 16
+    return view, flat
+
+
+def assert_guards(view, flat, what):
+    n, lead = view.numel(), (view.data_ptr() - flat.data_ptr()) // 4
+    assert bool(torch.isnan(flat[:lead]).all()) and bool(torch.isnan(flat[lead + n:]).all()), \
+        f"{what}: wrote outside its output buffer"
+
+
+def offset_copy(src, offset):
+    """`src` copied to `offset` elements past a 16-byte boundary of a larger allocation."""
+    flat = torch.zeros(src.numel() + 16, dtype=src.dtype, device=src.device)
+    assert flat.data_ptr() % 16 == 0
+    view = flat[offset:offset + src.numel()].view(src.shape)
+    view.copy_(src)
+    return view
+
+
+# ------------------------------------------------------------------ inputs
+
+
+def rng(*seed):
+    """numpy's generator seeded with a tuple of integers (the reference modules' cases)."""
+    return np.random.default_rng([int(s) for s in seed])
+
+
+def float_stack(t, h, w, dtype=torch.float32):
+    g = torch.Generator().manual_seed(t * 7919 + h * 31 + w)
+    st = (torch.randn(t, h, w, generator=g) * 2 + 5).to(dtype)
+    assert not bool((st == 0).any())  # the references divide the zeros of an output from its values
+    return st
+
+
+def drifting_raw_movie(dy, dx, h, w, dtype, seed, pad=64):
+    """A texture in [10, 50) cropped at the integer drift (dy[f], dx[f]) + noise, rounded to the detector's integers
+    (i16: scaled and offset so that negative counts occur)."""
+    g = torch.Generator().manual_seed(seed)
+    base = torch.rand(h + 2 * pad, w + 2 * pad, generator=g) * 40 + 10
+    raw = torch.empty((len(dy), h, w), dtype=dtype)
+    for f, (a, b) in enumerate(zip(dy, dx)):
+        v = base[pad - a: pad - a + h, pad - b: pad - b + w] + 2 * torch.randn(h, w, generator=g)
+        raw[f] = (v * 8 - 100).round().clamp(-32768, 32767).to(dtype) if dtype == torch.int16 else \
+            v.round().clamp(0, 255).to(dtype)
+    return raw
+
+
+def raw_movie(t, h, w, dtype, seed):
+    """drifting_raw_movie without a drift and without a margin: a static texture + noise."""
+    return drifting_raw_movie([0] * t, [0] * t, h, w, dtype, seed, pad=0)
+
+
+def gain(h, w, seed=9):
+    """A gain reference with a large dynamic range, log-uniform in [0.25, 4]: a wrong gain row or column (a cache
+    offset error) changes the output by a factor, which a constant or near-constant gain would hide."""
+    g = torch.Generator().manual_seed(seed + h * 7 + w)
+    out = 4.0 ** (2 * torch.rand(h, w, generator=g) - 1)
+    assert float(out.min()) >= 0.25 and float(out.max()) <= 4.0 and float(out.max() / out.min()) > 8
+    return out
+
+
+def raw_setup(dev, t, h, w, dtype, with_gain, seed):
+    """-> (raw, gain or None, engine.RawMovie of both on `dev`: kind, mu; the all-ones gain for None)."""
+    from torch_motion_correction_amd import engine
+
+    raw = raw_movie(t, h, w, dtype, seed)
+    g = gain(h, w) if with_gain else None
+    rm = engine.RawMovie(raw.to(dev), None if g is None else g.to(dev))
+    torch.cuda.synchronize()
+    return raw, g, rm
+
+
+# ------------------------------------------------------------------ worst error / bound per output family
+
+
+def ratio_lines(ratios, prefix="RATIO"):
+    return [f"{prefix} {k}: {ratios[k]:.3f}" for k in sorted(ratios)]
+
+
+def ratios_fixture(prefix="RATIO"):
+    """`ratios = ratios_fixture()` in a test module: a dict filled through worse(), printed when the module is done."""
+
+    @pytest.fixture(scope="module")
+    def ratios():
+        r = {}
+        yield r
+        for line in ratio_lines(r, prefix):
+            print(line)
+
+    return ratios
+
+
+def worse(ratios, key, value):
+    ratios[key] = max(ratios.get(key, 0.0), value)
+    return value
+
+
+def rel_err(a, b):
+    """max |a - b| / max |b| in float64."""
+    a, b = a.detach().cpu().double(), b.detach().cpu().double()
+    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
+
+
+def assert_sum(total, want, bound, what, border=None):
+    """Every pixel of a frame sum within its bound.  Returns the worst |got - want| / bound, over the pixels outside
+    `border` where one is given (a kernel that writes the allowed 0 on the border sits at the end of its interval by
+    design)."""
+    got = total.detach().cpu().double().numpy()
+    d = np.abs(got - want)
+    ok = d <= bound
+    if not bool(ok.all()):
+        bad = np.argwhere(~ok)
+        raise AssertionError(f"{what}: {len(bad)} pixels of the sum beyond the bound, first (row, col) "
+                             f"{[tuple(int(v) for v in b) for b in bad[:8]]}: got {got[tuple(bad[0])]!r} "
+                             f"want {want[tuple(bad[0])]!r} bound {bound[tuple(bad[0])]!r}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.nan_to_num(d / bound, nan=0.0, posinf=0.0)
+    return float(ratio.max() if border is None else np.where(border, 0.0, ratio).max())
+
+
+# ------------------------------------------------------------------ the engine's test switches
+
+ENGINE_SWITCHES = ("FUSED_SEARCH", "USE_ROW_CHORDS", "WORKSPACE_BYTES", "FULL_ROW_MAJOR", "DOSE_COLUMN_MAJOR",
+                   "POLYPHASE_FOURIER_SHIFT")
+
+
+@pytest.fixture
+def switches(monkeypatch):
+    """-> (engine, plan).  A test assigns the switches plainly; every one is back at its former value afterwards, and
+    plan's line cache is cleared before and after the test."""
+    from torch_motion_correction_amd import engine, plan
+
+    for name in ENGINE_SWITCHES:
+        monkeypatch.setattr(engine, name, getattr(engine, name))
+    monkeypatch.setattr(plan, "USE_DIRECT_LINES", plan.USE_DIRECT_LINES)
+    plan._LINES.clear()
+    yield engine, plan
+    plan._LINES.clear()

@@ -63,45 +63,17 @@ import torch
 from field_reference import (ACCUM_CASES, ACCUM_RUNS, ACCUM_SPACINGS, CASE_STORAGE, FAMILIES, FIELD_CASES, ULP,
                              accumulate_lattices, case_launches, case_lattices, field_reference, shift_at,
                              shift_interval, sum_reference, tile_plan)
+from kernel_harness import (assert_guards, assert_sum, float_stack, lib, nan_buffer, offset_copy,  # noqa: F401
+                            raw_setup)
 from rigid_reference import condition_float64, conditioning_error
 
 pytestmark = pytest.mark.gpu
 
 MODES = ("frames", "sum", "frames+sum")
-GUARD = 8
 MC_ERR_ARG, MC_ERR_UNSUPPORTED = -1, -2
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from torch_motion_correction_amd import _lib
-
-    return _lib.load()
-
-
 # ------------------------------------------------------------------ buffers and launches
-
-
-def _nan_buffer(shape, dev):
-    n = int(np.prod(shape))
-    lead = 4 * ((GUARD + 3) // 4)
-    flat = torch.full((lead + n + GUARD,), float("nan"), dtype=torch.float32, device=dev)
-    assert flat.data_ptr() % 16 == 0
-    return flat[lead:lead + n].view(*shape), flat
-
-
-def _assert_guards(view, flat, what):
-    n, lead = view.numel(), (view.data_ptr() - flat.data_ptr()) // 4
-    assert bool(torch.isnan(flat[:lead]).all()) and bool(torch.isnan(flat[lead + n:]).all()), \
-        f"{what}: wrote outside its output buffer"
-
-
-def _offset_copy(src, offset):
-    """`src` copied to `offset` elements past a 16-byte boundary of a larger allocation."""
-    flat = torch.zeros(src.numel() + 16, dtype=src.dtype, device=src.device)
-    view = flat[offset:offset + src.numel()].view(src.shape)
-    view.copy_(src)
-    return view
 
 
 def _scratch(lib, t, h, w, GH, GW, dev):
@@ -147,45 +119,9 @@ def _raw_launcher(lib, rm, accumulate=False):
 # ------------------------------------------------------------------ inputs and references
 
 
-def _float_stack(t, h, w, dtype=torch.float32):
-    g = torch.Generator().manual_seed(t * 7919 + h * 31 + w)
-    st = (torch.randn(t, h, w, generator=g) * 2 + 5).to(dtype)
-    assert not bool((st == 0).any())
-    return st
-
-
 def _float_reference(src):
     values = src.float().numpy().astype(np.float64)
     return lambda lat, ps: field_reference(values, lat, ps)
-
-
-def _raw_movie(t, h, w, dtype, seed):
-    """A static texture in [10, 50) + noise, rounded to the detector's integers (i16: scaled and offset so that
-    negative counts occur) -- test_rigid_kernels_float64._raw_movie."""
-    g = torch.Generator().manual_seed(seed)
-    base = torch.rand(h, w, generator=g) * 40 + 10
-    raw = torch.empty((t, h, w), dtype=dtype)
-    for f in range(t):
-        v = base + 2 * torch.randn(h, w, generator=g)
-        raw[f] = (v * 8 - 100).round().clamp(-32768, 32767).to(dtype) if dtype == torch.int16 else \
-            v.round().clamp(0, 255).to(dtype)
-    return raw
-
-
-def _gain(h, w, seed=9):
-    """log-uniform in [0.25, 4]: a gain read at a wrong pixel changes the output by a factor."""
-    g = torch.Generator().manual_seed(seed + h * 7 + w)
-    return 4.0 ** (2 * torch.rand(h, w, generator=g) - 1)
-
-
-def _raw_setup(dev, t, h, w, dtype, with_gain, seed):
-    from torch_motion_correction_amd import engine
-
-    raw = _raw_movie(t, h, w, dtype, seed)
-    gain = _gain(h, w) if with_gain else None
-    rm = engine.RawMovie(raw.to(dev), None if gain is None else gain.to(dev))  # kind, mu; the all-ones gain for None
-    torch.cuda.synchronize()
-    return raw, gain, rm
 
 
 def _raw_reference(raw, gain, mu):
@@ -198,22 +134,6 @@ def _raw_reference(raw, gain, mu):
     assert not (v == 0).any(), "a conditioned sample is exactly zero: pick another gain / movie"
     err = conditioning_error(raw_np, gain_np, mu_np)
     return lambda lat, ps, a=0, n=None: field_reference(v[a:a + (n or len(v))], lat, ps, err=err[a:a + (n or len(v))])
-
-
-def _assert_sum(total, want, bound, what, border=None):
-    """Every pixel of the sum within its bound.  Returns the worst |got - want| / bound over the pixels that are on
-    the border in no frame (there a kernel that writes the allowed 0 sits at the end of its interval by design)."""
-    got = total.detach().cpu().double().numpy()
-    d = np.abs(got - want)
-    ok = d <= bound
-    if not bool(ok.all()):
-        bad = np.argwhere(~ok)
-        raise AssertionError(f"{what}: {len(bad)} pixels of the sum beyond the bound, first (row, col) "
-                             f"{[tuple(int(v) for v in b) for b in bad[:8]]}: got {got[tuple(bad[0])]!r} "
-                             f"want {want[tuple(bad[0])]!r} bound {bound[tuple(bad[0])]!r}")
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.nan_to_num(d / bound, nan=0.0, posinf=0.0)
-    return float(ratio.max() if border is None else np.where(border, 0.0, ratio).max())
 
 
 def _run_case(lib, launch, reference, case, dev, what, slow=True):
@@ -231,17 +151,17 @@ def _run_case(lib, launch, reference, case, dev, what, slow=True):
         want, sum_bound = sum_reference(ref, 1 if slow else 0)
         for mode in MODES:
             tag = f"{what} launch {no} ps {ps} [{mode}]"
-            frames, frames_all = _nan_buffer((t, h, w), dev) if "frames" in mode else (None, None)
-            total, total_all = _nan_buffer((h, w), dev) if "sum" in mode else (None, None)
+            frames, frames_all = nan_buffer((t, h, w), dev) if "frames" in mode else (None, None)
+            total, total_all = nan_buffer((h, w), dev) if "sum" in mode else (None, None)
             check(launch(ld, ps, scratch, frames, total), tag)
             torch.cuda.synchronize()
             if frames is not None:
-                _assert_guards(frames, frames_all, tag)
+                assert_guards(frames, frames_all, tag)
                 worst_f = max(worst_f, ref.check(frames.cpu().numpy(), tag))
                 worst_p = max(worst_p, ref.worst_plain)
             if total is not None:
-                _assert_guards(total, total_all, tag)
-                worst_s = max(worst_s, _assert_sum(total, want, sum_bound, tag, ref.border.any(0)))
+                assert_guards(total, total_all, tag)
+                worst_s = max(worst_s, assert_sum(total, want, sum_bound, tag, ref.border.any(0)))
     print(f"RATIO {what}: frames {worst_f:.3f} (without midpoint candidates {worst_p:.3f}) sum {worst_s:.3f}")
 
 
@@ -255,15 +175,15 @@ def _case_id(case):
 @pytest.mark.parametrize("case", FIELD_CASES["warp_main"], ids=_case_id)
 def test_warp_main_matches_the_float64_reference(lib, dev, case):
     """w % 4 != 0: the untiled kernel (its 5 x 8 register window and its clipped-tap branch)."""
-    src = _float_stack(*case[:3])
+    src = float_stack(*case[:3])
     _run_case(lib, _float_launcher(lib, src.to(dev)), _float_reference(src), case, dev, f"warp_main {case}", slow=False)
 
 
 @pytest.mark.parametrize("case", FIELD_CASES["warp_main_unaligned"], ids=_case_id)
 def test_warp_main_takes_an_unaligned_stack(lib, dev, case):
     """w % 4 == 0 but `frames` one float past a 16-byte boundary: routed to warp_main."""
-    src = _float_stack(*case[:3])
-    sd = _offset_copy(src.to(dev), 1)
+    src = float_stack(*case[:3])
+    sd = offset_copy(src.to(dev), 1)
     assert sd.data_ptr() % 16 == 4
     _run_case(lib, _float_launcher(lib, sd), _float_reference(src), case, dev, f"warp_main unaligned {case}", slow=False)
 
@@ -271,7 +191,7 @@ def test_warp_main_takes_an_unaligned_stack(lib, dev, case):
 @pytest.mark.parametrize("case", FIELD_CASES["warp_field2"], ids=_case_id)
 def test_warp_field2_matches_the_float64_reference(lib, dev, case):
     """A lattice denser than 1.5 cells per 32 rows: warp_field2 + warp_field_slow."""
-    src = _float_stack(*case[:3])
+    src = float_stack(*case[:3])
     _run_case(lib, _float_launcher(lib, src.to(dev)), _float_reference(src), case, dev, f"warp_field2 {case}")
 
 
@@ -279,7 +199,7 @@ def test_warp_field2_matches_the_float64_reference(lib, dev, case):
 def test_warp_field3_matches_the_float64_reference(lib, dev, case):
     """The production kernel on fp32 frames: partial last tiles, exactly one tile, 16 tiles (remap) and 18 (none),
     interior and rim tile-frames, the clipped-column patch, 130 frames (the second plan block)."""
-    src = _float_stack(*case[:3])
+    src = float_stack(*case[:3])
     _run_case(lib, _float_launcher(lib, src.to(dev)), _float_reference(src), case, dev, f"warp_field3 {case}")
 
 
@@ -290,7 +210,7 @@ def test_warp_field3_matches_the_float64_reference(lib, dev, case):
 def test_warp_field3_half_matches_the_float64_reference(lib, dev, case):
     """fp16 frames (exact fp16 values, none zero) through warp_field3<HALF> and warp_field_slow<HALF>; the
     reference and the bound are taken on the up-cast."""
-    src = _float_stack(*case[:3], dtype=torch.float16)
+    src = float_stack(*case[:3], dtype=torch.float16)
     _run_case(lib, _float_launcher(lib, src.to(dev)), _float_reference(src), case, dev, f"warp_field3<HALF> {case}")
 
 
@@ -307,7 +227,7 @@ def test_warp_field3_raw_matches_the_float64_reference(lib, dev, case, dtype, wi
     """Raw frames through warp_field3<RAW> + warp_field_slow<RAW> with a gain of large dynamic range and with the
     all-ones gain, against the float64 conditioning (mu read back from engine.RawMovie) + resampler."""
     t, h, w = case[:3]
-    raw, gain, rm = _raw_setup(dev, t, h, w, dtype, with_gain, seed=700 + h + w)
+    raw, gain, rm = raw_setup(dev, t, h, w, dtype, with_gain, seed=700 + h + w)
     _run_case(lib, _raw_launcher(lib, rm), _raw_reference(raw, gain, rm.mu.cpu().numpy()), case, dev,
               f"warp_field3<RAW> {str(dtype)[6:]} {case} {'gain' if with_gain else 'no gain'}")
 
@@ -325,7 +245,7 @@ def test_warp_frames_raw_accumulate_sums_chunks(lib, dev, dtype, kind, ps):
 
     case = ACCUM_CASES[kind]
     t, h, w, GH, GW = case
-    raw, gain, rm = _raw_setup(dev, t, h, w, dtype, True, seed=77)
+    raw, gain, rm = raw_setup(dev, t, h, w, dtype, True, seed=77)
     reference = _raw_reference(raw, gain, rm.mu.cpu().numpy())
     for run, (families, n) in enumerate(ACCUM_RUNS):
         lat = accumulate_lattices(case, families, ps)
@@ -344,19 +264,19 @@ def test_warp_frames_raw_accumulate_sums_chunks(lib, dev, dtype, kind, ps):
         sums = []
         for rep in range(2 if run == 0 else 1):
             for with_frames in (False, True):
-                total, total_all = _nan_buffer((h, w), dev)
+                total, total_all = nan_buffer((h, w), dev)
                 for i, a in enumerate(range(0, t, n)):
                     win = rm.window(a, n)
-                    frames, frames_all = _nan_buffer((n, h, w), dev) if with_frames else (None, None)
+                    frames, frames_all = nan_buffer((n, h, w), dev) if with_frames else (None, None)
                     ld = torch.from_numpy(lat[a:a + n]).to(dev)
                     check(_raw_launcher(lib, win, accumulate=i > 0)(ld, ps, _scratch(lib, n, h, w, GH, GW, dev), frames,
                                                                     total), "mc_warp_frames_raw(_accumulate)")
                     torch.cuda.synchronize()
                     if with_frames:
-                        _assert_guards(frames, frames_all, "accumulate frames")
+                        assert_guards(frames, frames_all, "accumulate frames")
                         refs[i].check(frames.cpu().numpy(), f"accumulate {dtype} chunk {i} frames")
-                _assert_guards(total, total_all, "accumulate sum")
-                r = _assert_sum(total, want, bound, f"accumulate {dtype} chunks of {n} ps {ps} frames={with_frames}", edge)
+                assert_guards(total, total_all, "accumulate sum")
+                r = assert_sum(total, want, bound, f"accumulate {dtype} chunks of {n} ps {ps} frames={with_frames}", edge)
                 print(f"RATIO mc_warp_frames_raw_accumulate {str(dtype)[6:]} chunks of {n} ps {ps} frames={with_frames}: sum {r:.3f}")
                 sums.append(total.clone())
         for s in sums[1:]:
@@ -373,7 +293,7 @@ def test_argument_contract_before_any_launch(lib, dev):
     from torch_motion_correction_amd._lib import ptr, stream_ptr
 
     def outputs(t, h, w):
-        return _nan_buffer((t, h, w), dev)[0], _nan_buffer((h, w), dev)[0]
+        return nan_buffer((t, h, w), dev)[0], nan_buffer((h, w), dev)[0]
 
     def untouched(frames, total):
         torch.cuda.synchronize()
@@ -382,8 +302,8 @@ def test_argument_contract_before_any_launch(lib, dev):
     ps = 0.83
     # fp16: rows of whole 8-sample units, the sparse lattice, a 16-byte aligned stack
     for (t, h, w, GH, GW), offset in (((3, 33, 260, 2, 3), 0), ((3, 33, 264, 8, 5), 0), ((3, 33, 264, 2, 3), 1)):
-        src = _float_stack(t, h, w, torch.float16).to(dev)
-        src = _offset_copy(src, offset) if offset else src
+        src = float_stack(t, h, w, torch.float16).to(dev)
+        src = offset_copy(src, offset) if offset else src
         assert src.data_ptr() % 16 == 2 * offset
         lat = torch.from_numpy(case_lattices((t, h, w, GH, GW), ps, 0)).to(dev)
         frames, total = outputs(t, h, w)
@@ -392,7 +312,7 @@ def test_argument_contract_before_any_launch(lib, dev):
     # raw: rows of whole 16-byte units
     for dtype, w in ((torch.uint8, 264), (torch.int16, 260)):
         t, h, GH, GW = 3, 33, 2, 3
-        _, _, rm = _raw_setup(dev, t, h, w, dtype, True, seed=3)
+        _, _, rm = raw_setup(dev, t, h, w, dtype, True, seed=3)
         lat = torch.from_numpy(case_lattices((t, h, w, GH, GW), ps, 0)).to(dev)
         for acc in (False, True):
             frames, total = outputs(t, h, w)
@@ -400,7 +320,7 @@ def test_argument_contract_before_any_launch(lib, dev):
             assert rc == MC_ERR_UNSUPPORTED and untouched(frames, total), (dtype, w, acc, rc)
     # accumulate needs a sum; scratch must be 16-byte aligned
     t, h, w, GH, GW = 3, 33, 272, 2, 3
-    _, _, rm = _raw_setup(dev, t, h, w, torch.uint8, True, seed=4)
+    _, _, rm = raw_setup(dev, t, h, w, torch.uint8, True, seed=4)
     lat = torch.from_numpy(case_lattices((t, h, w, GH, GW), ps, 0)).to(dev)
     frames, total = outputs(t, h, w)
     scratch = _scratch(lib, t, h, w, GH, GW, dev)
@@ -410,7 +330,7 @@ def test_argument_contract_before_any_launch(lib, dev):
     assert off.data_ptr() % 16 == 4
     assert _raw_launcher(lib, rm, False)(lat, ps, off, frames, total) == MC_ERR_ARG and untouched(frames, total)
     assert _raw_launcher(lib, rm, True)(lat, ps, off, frames, total) == MC_ERR_ARG and untouched(frames, total)
-    src = _float_stack(t, h, w).to(dev)
+    src = float_stack(t, h, w).to(dev)
     assert _float_launcher(lib, src)(lat, ps, off, frames, total) == MC_ERR_ARG and untouched(frames, total)
     out = torch.full((h, w, 2), float("nan"), device=dev)
     assert lib.mc_pixel_shifts(ptr(lat[0]), GH, GW, h, w, ps, ptr(off), ptr(out), stream_ptr(dev)) == MC_ERR_ARG

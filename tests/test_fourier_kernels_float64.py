@@ -59,55 +59,13 @@ import pytest
 import torch
 
 import fourier_reference as fr
+import kernel_harness as kh
+from kernel_harness import calls, mc, switches  # noqa: F401
 from rigid_reference import condition_float64, conditioning_error
 
 pytestmark = pytest.mark.gpu
 
 U = fr.U
-
-
-@pytest.fixture(scope="module")
-def mc():
-    import torch_motion_correction_amd as m
-
-    return m
-
-
-class _Recorder:
-    """The loaded library with the names of the entry points that are looked up (= called) written down."""
-
-    def __init__(self, lib):
-        self._lib, self.names = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        self.names.append(name)
-        return fn
-
-    def count(self, name):
-        return self.names.count(name)
-
-
-@pytest.fixture
-def calls(monkeypatch):
-    from torch_motion_correction_amd import _lib
-
-    rec = _Recorder(_lib.load())
-    monkeypatch.setattr(_lib, "load", lambda: rec)
-    return rec
-
-
-@pytest.fixture
-def switches(monkeypatch):
-    """The engine's test switches at their defaults, restored afterwards; plan's line cache cleared around the test."""
-    from torch_motion_correction_amd import engine, plan
-
-    for name in ("FULL_ROW_MAJOR", "DOSE_COLUMN_MAJOR", "POLYPHASE_FOURIER_SHIFT", "WORKSPACE_BYTES"):
-        monkeypatch.setattr(engine, name, getattr(engine, name))
-    monkeypatch.setattr(plan, "USE_DIRECT_LINES", plan.USE_DIRECT_LINES)
-    plan._LINES.clear()
-    yield engine, plan
-    plan._LINES.clear()
 
 
 # ------------------------------------------------------------------ comparisons
@@ -176,13 +134,10 @@ def _shift_case(mc, dev, calls, case, layout, family, want, absent=()):
     worst = _Worst()
     for launch in range(fr.launches(t)):
         x, s, ref = fr.shifted_reference(t, h, w, offset, launch)
-        del calls.names[:]
+        calls.clear()
         got = mc.correct_motion_fast(x.to(dev), _field(s).to(dev))
         torch.cuda.synchronize()
-        for name in want:
-            assert calls.count(name) >= 1, f"{family} {case}: {name} did not run ({sorted(set(calls.names))})"
-        for name in absent:
-            assert calls.count(name) == 0, f"{family} {case}: {name} ran"
+        calls.ran(*want, absent=absent)
         b = fr.bounds(h, w, s, layout)
         rel_kinds = b["kinds"]
         worst.add(_assert_frames(got, ref, b["rel"], f"{family} {case[:3]} shifts {s.tolist()}"))
@@ -260,7 +215,7 @@ def test_fused_shift_sums(mc, dev, calls, switches, case, colmajor, two_per_chun
         ps, dose, pre, kv = expo
         expo_term = fr.exposure_term(t, h, w, ps, pre, dose, kv)
         # mode 6: the exposure-weighted sum of the frames as they are
-        del calls.names[:]
+        calls.clear()
         d6 = mc.dose_weighted_sum(img, ps, dose, pre_exposure=pre, voltage=kv)
         torch.cuda.synchronize()
         assert calls.count(entry) == chunks and calls.count(other) == 0 and calls.count("mc_dose_accumulate") == 0
@@ -278,7 +233,7 @@ def test_fused_shift_sums(mc, dev, calls, switches, case, colmajor, two_per_chun
             bound_p = fr.sum_l2_bound(b["rel"], ref["norm_y"], chunks)
             bound_d = fr.sum_l2_bound(b["rel"] + expo_term + 2 * U, ref["norm_d"], chunks)
             what = f"fused {case[:3]} {expo} shifts {used.tolist()}"
-            del calls.names[:]
+            calls.clear()
             plain = mc.motion_correct_sum_fast(img, field, ps)
             dw = mc.motion_correct_sum_fast(img, field, ps, dose_per_frame=dose, pre_exposure=pre, voltage=kv)
             dw3, plain3 = mc.motion_correct_sum_fast(img, field, ps, dose_per_frame=dose, pre_exposure=pre, voltage=kv,
@@ -340,7 +295,7 @@ def test_pruned_engine_fourier_shift_and_exposure_sum(mc, dev, calls, switches, 
     x = fr.case_frames(t, h, w, offset)
     for expo in fr.EXPOSURES:
         ps, dose, pre, kv = expo
-        del calls.names[:]
+        calls.clear()
         got = mc.dose_weighted_sum(x.to(dev), ps, dose, pre_exposure=pre, voltage=kv)
         torch.cuda.synchronize()
         assert calls.count("mc_dose_accumulate") == 1 and calls.count("mc_full_cols_shift_sum") == 0
@@ -371,7 +326,7 @@ def test_polyphase_fourier_shift_and_exposure_sum(mc, dev, calls, switches, case
     x = fr.case_frames(t, h, w, offset)
     for expo in fr.EXPOSURES:
         ps, dose, pre, kv = expo
-        del calls.names[:]
+        calls.clear()
         got = mc.dose_weighted_sum(x.to(dev), ps, dose, pre_exposure=pre, voltage=kv)
         torch.cuda.synchronize()
         assert calls.count("mc_polyphase_dose_accumulate") == 1 and calls.count("mc_dose_accumulate") == 0
@@ -382,25 +337,6 @@ def test_polyphase_fourier_shift_and_exposure_sum(mc, dev, calls, switches, case
 
 
 # ------------------------------------------------------------------ raw bytes
-
-
-def _raw_movie(t, h, w, dtype, seed):
-    """A static texture in [10, 50) + noise, rounded to the detector's integers (i16: scaled and offset so that
-    negative counts occur) -- the recipe of tests/test_rigid_kernels_float64.py."""
-    g = torch.Generator().manual_seed(seed)
-    base = torch.rand(h, w, generator=g) * 40 + 10
-    raw = torch.empty((t, h, w), dtype=dtype)
-    for f in range(t):
-        v = base + 2 * torch.randn(h, w, generator=g)
-        raw[f] = (v * 8 - 100).round().clamp(-32768, 32767).to(dtype) if dtype == torch.int16 else \
-            v.round().clamp(0, 255).to(dtype)
-    return raw
-
-
-def _gain(h, w):
-    """log-uniform in [0.25, 4]: a wrong gain row or column changes the output by a factor."""
-    g = torch.Generator().manual_seed(9 + h * 7 + w)
-    return 4.0 ** (2 * torch.rand(h, w, generator=g) - 1)
 
 
 @pytest.mark.parametrize("dtype", [torch.uint8, torch.int16], ids=["uint8", "int16"])
@@ -414,7 +350,7 @@ def test_raw_fused_shift_sums(mc, dev, calls, switches, shape, dtype):
     engine, _ = switches
     t, h, w = shape
     assert engine._full_row_major_ok(h, w)
-    raw, gain = _raw_movie(t, h, w, dtype, seed=700 + h), _gain(h, w)
+    raw, gain = kh.raw_movie(t, h, w, dtype, seed=700 + h), kh.gain(h, w)
     rm = engine.RawMovie(raw.to(dev), gain.to(dev))
     mu = rm.mu.cpu().numpy()
     v = condition_float64(raw.numpy(), gain.numpy(), mu)
@@ -435,7 +371,7 @@ def test_raw_fused_shift_sums(mc, dev, calls, switches, shape, dtype):
         s = fr.case_shifts(t)[launch * t:(launch + 1) * t]
         field = _field(s, ps).to(dev)
         used = _used_shifts(field, ps)
-        del calls.names[:]
+        calls.clear()
         dw, plain = mc.motion_correct_sum_fast_raw(raw.to(dev), gain.to(dev), field, ps, dose_per_frame=dose,
                                                    pre_exposure=pre, voltage=kv, return_plain_sum=True)
         torch.cuda.synchronize()
@@ -443,7 +379,7 @@ def test_raw_fused_shift_sums(mc, dev, calls, switches, shape, dtype):
         assert calls.count("mc_condition_movie") == 0
         compare(dw, plain, used, f"raw {str(dtype)[6:]} {shape} shifts {used.tolist()}")
     if shape == fr.RAW[0]:
-        del calls.names[:]
+        calls.clear()
         field, dw, plain = mc.motion_correct_raw_fast(raw.to(dev), gain.to(dev), ps, dose_per_frame=dose,
                                                       pre_exposure=pre, voltage=kv, return_plain_sum=True)
         torch.cuda.synchronize()
@@ -470,7 +406,7 @@ def test_fp16_stack_fused_shift_sums(mc, dev, calls, switches):
         s = fr.case_shifts(t)[launch * t:(launch + 1) * t]
         field = _field(s, ps).to(dev)
         used = _used_shifts(field, ps)
-        del calls.names[:]
+        calls.clear()
         dw, plain = mc.motion_correct_sum_fast(half.to(dev), field, ps, dose_per_frame=dose, pre_exposure=pre,
                                                voltage=kv, return_plain_sum=True)
         torch.cuda.synchronize()

@@ -22,22 +22,11 @@ import torch
 import oracle
 from oracle import thirdparty_semantics as tp
 from conftest import blob_stack, drift_stack, ramp_field
+from kernel_harness import mc, rel_err, switches  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 REL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def mc():
-    import torch_motion_correction_amd as m
-
-    return m
-
-
-def rel_err(a, b):
-    a, b = a.detach().cpu().double(), b.detach().cpu().double()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
 
 
 def knife_edge_mask(stack, field, pixel_spacing, grid_type, eps=1e-3):
@@ -612,7 +601,7 @@ def test_pruned_spectrum_on_arbitrary_sizes(dev, h, w, pruned_m):
 
 
 @pytest.mark.parametrize("t,h,w", [(3, 96, 5760), (2, 64, 11520), (3, 2880, 128), (2, 96, 7000), (2, 5760, 64)])
-def test_mixed_radix_lines(mc, dev, t, h, w):
+def test_mixed_radix_lines(mc, dev, switches, t, h, w):
     """Rows of 5760 / 11520 columns (K3 detectors) and columns of 2880 / 5760 rows are transformed
     DIRECTLY by radix-8/5/3 passes (n = 2880 = 2^6 3^2 5, 5760 = 2^7 3^2 5) instead of chirp-z; 7000
     columns take a chirp-z line of M = 5120 = 2^10 5.  The integer shifts must equal the oracle's,
@@ -638,13 +627,11 @@ def test_mixed_radix_lines(mc, dev, t, h, w):
     sub = spec[:, rows][:, :, : gm.nkx].transpose(1, 2)
     assert float((S - sub).abs().max() / sub.abs().max()) <= 5e-6
     if w // 2 in plan.DIRECT_LINE_LENGTHS or h in plan.DIRECT_LINE_LENGTHS:
-        try:
-            plan.USE_DIRECT_LINES = False
-            plan._LINES.clear()
-            S2 = torch.view_as_complex(engine._forward_spectra(d, off, w, None, pl, engine.central_box_stats(d)).cpu())
-        finally:
-            plan.USE_DIRECT_LINES = True
-            plan._LINES.clear()
+        plan.USE_DIRECT_LINES = False
+        plan._LINES.clear()
+        S2 = torch.view_as_complex(engine._forward_spectra(d, off, w, None, pl, engine.central_box_stats(d)).cpu())
+        plan.USE_DIRECT_LINES = True
+        plan._LINES.clear()
         assert float((S - S2).abs().max() / sub.abs().max()) <= 5e-6
 
 
@@ -848,7 +835,7 @@ def test_motion_correct_sum_with_dose_weighting(mc, dev):
 
 
 @pytest.mark.parametrize("rigid", [True, False])
-def test_motion_correct_sum_dose_weighting_streams_chunks(mc, dev, rigid):
+def test_motion_correct_sum_dose_weighting_streams_chunks(mc, dev, switches, rigid):
     """motion_correct_sum(dose_per_frame=...) without return_frames warps, transforms and weights the
     movie a chunk of frames at a time (the corrected movie is never held): same sum as the
     all-frames form and as the oracle's dose weighting of the corrected frames, with the workspace
@@ -863,12 +850,9 @@ def test_motion_correct_sum_dose_weighting_streams_chunks(mc, dev, rigid):
         field = (torch.randn(2, 7, 3, 4, generator=g) * 1.5).to(dev)
     whole, frames = mc.motion_correct_sum(st.to(dev), field, 1.0, return_frames=True, dose_per_frame=0.9,
                                           pre_exposure=0.5, voltage=200.0)
-    try:
-        ws, engine.WORKSPACE_BYTES = engine.WORKSPACE_BYTES, 2 * 256 * (512 // 2 + 16) * 8
-        streamed = mc.motion_correct_sum(st.to(dev), field, 1.0, dose_per_frame=0.9, pre_exposure=0.5,
-                                         voltage=200.0)
-    finally:
-        engine.WORKSPACE_BYTES = ws
+    ws, engine.WORKSPACE_BYTES = engine.WORKSPACE_BYTES, 2 * 256 * (512 // 2 + 16) * 8
+    streamed = mc.motion_correct_sum(st.to(dev), field, 1.0, dose_per_frame=0.9, pre_exposure=0.5, voltage=200.0)
+    engine.WORKSPACE_BYTES = ws
     ref = oracle.dose_weighted_sum(frames.cpu(), 1.0, 0.9, pre_exposure=0.5, voltage=200.0)
     assert float((streamed.cpu() - ref).abs().max()) <= 1e-4 * float(ref.abs().max())
     assert float((streamed - whole).abs().max()) <= 2e-5 * float(ref.abs().max())
@@ -1012,7 +996,7 @@ def test_product_matches_reference_helper_vectors(mc, dev):
 
 
 @pytest.mark.parametrize("strategy", ["mean_except_current", "middle_frame"])
-def test_patches_1024_near_window_search_with_sub_pixel(mc, dev, strategy):
+def test_patches_1024_near_window_search_with_sub_pixel(mc, dev, switches, strategy):
     """p = 1024 patches go through the wave kernels (rows 512-point dual, columns 1024-point)
     and the near-window search incl. the 3x3 neighbourhood read from the compact buffer; the
     result must equal the full-map path and the oracle."""
@@ -1020,14 +1004,11 @@ def test_patches_1024_near_window_search_with_sub_pixel(mc, dev, strategy):
 
     st, dy, dx = drift_stack(5, 1100, 1600, seed=17)  # 1 x 2 patches
     got = {}
-    try:
-        for fused in (False, True):
-            engine.FUSED_SEARCH = fused
-            f, pos = mc.estimate_motion_cross_correlation_patches(st.to(dev), 1.0, patch_sidelength=1024,
-                                                                  reference_strategy=strategy)
-            got[fused] = (f.cpu(), pos.cpu())
-    finally:
-        engine.FUSED_SEARCH = True
+    for fused in (False, True):
+        engine.FUSED_SEARCH = fused
+        f, pos = mc.estimate_motion_cross_correlation_patches(st.to(dev), 1.0, patch_sidelength=1024,
+                                                              reference_strategy=strategy)
+        got[fused] = (f.cpu(), pos.cpu())
     assert torch.equal(got[True][1], got[False][1])
     assert float((got[True][0] - got[False][0]).abs().max()) <= 1e-4
     of, opos = oracle.estimate_motion_cross_correlation_patches(st, 1.0, patch_sidelength=1024,
@@ -1318,7 +1299,7 @@ def test_local_motion_1024_patches_take_the_wave_engine(dev):
 
 
 @pytest.mark.parametrize("shape", [(3, 64, 128), (2, 100, 132), (2, 96, 120), (2, 33, 72)])
-def test_polyphase_fourier_shift_matches_direct_path_and_oracle(mc, dev, shape):
+def test_polyphase_fourier_shift_matches_direct_path_and_oracle(mc, dev, switches, shape):
     """correct_motion_fast through the x-polyphase form (even / odd columns transformed separately,
     csrc/polyphase.hip) -- the path frames wider than ~8190 columns take -- forced on small frames."""
     from torch_motion_correction_amd import engine
@@ -1329,15 +1310,13 @@ def test_polyphase_fourier_shift_matches_direct_path_and_oracle(mc, dev, shape):
     ref = oracle.correct_motion_fast(img, sh.clone())
     direct = mc.correct_motion_fast(img.to(dev), sh.clone().to(dev))
     engine.POLYPHASE_FOURIER_SHIFT = True
-    try:
-        poly = mc.correct_motion_fast(img.to(dev), sh.clone().to(dev))
-    finally:
-        engine.POLYPHASE_FOURIER_SHIFT = False
+    poly = mc.correct_motion_fast(img.to(dev), sh.clone().to(dev))
+    engine.POLYPHASE_FOURIER_SHIFT = False
     assert rel_err(poly, ref) <= 2e-5 and rel_err(poly, direct) <= 2e-5
 
 
 @pytest.mark.parametrize("shape,ps,dose", [((5, 64, 128), 1.0, 1.5), ((4, 90, 132), 0.83, 0.8), ((3, 33, 72), 1.3, 2.0)])
-def test_polyphase_dose_weighted_sum_matches_direct_path_and_oracle(mc, dev, shape, ps, dose):
+def test_polyphase_dose_weighted_sum_matches_direct_path_and_oracle(mc, dev, switches, shape, ps, dose):
     """dose_weighted_sum through the x-polyphase form (the path of frames wider than ~8190 columns),
     forced on small frames: equal to the direct path and to the oracle."""
     from torch_motion_correction_amd import engine
@@ -1347,10 +1326,8 @@ def test_polyphase_dose_weighted_sum_matches_direct_path_and_oracle(mc, dev, sha
     ref = oracle.dose_weighted_sum(m, ps, dose, pre_exposure=0.4, voltage=300.0)
     direct = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=0.4).cpu()
     engine.POLYPHASE_FOURIER_SHIFT = True
-    try:
-        poly = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=0.4).cpu()
-    finally:
-        engine.POLYPHASE_FOURIER_SHIFT = False
+    poly = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=0.4).cpu()
+    engine.POLYPHASE_FOURIER_SHIFT = False
     scale = float(ref.abs().max())
     assert float((poly - ref).abs().max()) <= 1e-4 * scale and float((poly - direct).abs().max()) <= 2e-5 * scale
 
@@ -1540,7 +1517,7 @@ def test_c3_full_frame_size_against_oracle(mc, dev):
 
 
 @pytest.mark.parametrize("t,h,w", [(6, 4092, 5760), (3, 8184, 11520)])
-def test_k3_formats_global_estimate_known_drift(mc, dev, t, h, w):
+def test_k3_formats_global_estimate_known_drift(mc, dev, switches, t, h, w):
     """estimate_global_motion on the K3 detector's two frame formats (BASELINE C3 / C5 frame sizes): the
     shifts equal the drift the stack was built with, with the direct mixed-radix lines (rows of
     2880 / 5760 points: radix 8 8 9 5 / 8 8 9 10; columns of 4092 / 8184 points: radix 31 11 12 / 31 11 24)
@@ -1554,13 +1531,11 @@ def test_k3_formats_global_estimate_known_drift(mc, dev, t, h, w):
     want_x = [float(d - dx[t // 2]) for d in dx]
     f = mc.estimate_global_motion(st, 1.0).cpu()
     assert f[0, :, 0, 0].tolist() == want_y and f[1, :, 0, 0].tolist() == want_x
-    try:
-        plan.USE_DIRECT_LINES = False
-        plan._LINES.clear()
-        fc = mc.estimate_global_motion(st, 1.0).cpu()
-    finally:
-        plan.USE_DIRECT_LINES = True
-        plan._LINES.clear()
+    plan.USE_DIRECT_LINES = False
+    plan._LINES.clear()
+    fc = mc.estimate_global_motion(st, 1.0).cpu()
+    plan.USE_DIRECT_LINES = True
+    plan._LINES.clear()
     assert torch.equal(fc, f)
     z = mc.dose_weighted_sum(st, 1.0, 0.0)
     plain = st.sum(0) / t**0.5
@@ -1813,7 +1788,7 @@ def test_evaluate_deformation_field_on_scattered_points(mc, dev):
                                    # radix-31 and radix-11 passes), alone and together
                                    (2, 256, 5760), (1, 512, 11520), (3, 4092, 64), (2, 8184, 128),
                                    (2, 4092, 5760), (1, 8184, 11520)])
-def test_row_major_fourier_shift(mc, dev, shape):
+def test_row_major_fourier_shift(mc, dev, switches, shape):
     """correct_motion_fast on power-of-two frames (rows forward, one in-place column kernel for
     forward + phase ramp + inverse, rows inverse; spectrum row-major) against the oracle, against
     the pruned engine's transposed layout, and -- for integer shifts -- against an exact roll."""
@@ -1826,11 +1801,9 @@ def test_row_major_fourier_shift(mc, dev, shape):
     got = mc.correct_motion_fast(img.to(dev), sh.clone().to(dev)).cpu()
     if h * w <= 1024 * 1024:
         assert rel_err(got, oracle.correct_motion_fast(img, sh.clone())) <= 2e-5
-    try:
-        engine.FULL_ROW_MAJOR = False
-        old = mc.correct_motion_fast(img.to(dev), sh.clone().to(dev)).cpu()
-    finally:
-        engine.FULL_ROW_MAJOR = True
+    engine.FULL_ROW_MAJOR = False
+    old = mc.correct_motion_fast(img.to(dev), sh.clone().to(dev)).cpu()
+    engine.FULL_ROW_MAJOR = True
     assert rel_err(got, old) <= 2e-5
     ish = torch.tensor([[3.0, -7.0]] * t).t()[:, :, None, None].contiguous()  # field +3 / -7 -> shift by (-3, +7)
     rolled = mc.correct_motion_fast(img.to(dev), ish.clone().to(dev)).cpu()
@@ -1844,7 +1817,7 @@ def test_row_major_fourier_shift(mc, dev, shape):
                                                   ((5, 4096, 128), 0.9, 1.1, 0.5, 300.0),
                                                   ((4, 8184, 128), 0.5, 0.9, 1.0, 300.0),
                                                   ((3, 256, 5760), 1.1, 1.0, 0.0, 200.0)])
-def test_row_major_dose_weighted_sum(mc, dev, shape, ps, dose, pre, kv):
+def test_row_major_dose_weighted_sum(mc, dev, switches, shape, ps, dose, pre, kv):
     """The exposure-filtered sum with the weighted accumulation inside the forward column pass
     (frame loop in registers, chunks of frames carried through A) against the oracle and against
     the separate accumulate kernel on the transposed layout."""
@@ -1855,23 +1828,19 @@ def test_row_major_dose_weighted_sum(mc, dev, shape, ps, dose, pre, kv):
     got = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=pre, voltage=kv).cpu()
     ref = oracle.dose_weighted_sum(m, ps, dose, pre_exposure=pre, voltage=kv)
     assert float((got - ref).abs().max()) <= 1e-4 * float(ref.abs().max())
-    try:  # two frames per chunk: the accumulator goes through A between chunks
-        ws, engine.WORKSPACE_BYTES = engine.WORKSPACE_BYTES, 2 * shape[1] * (shape[2] // 2 + 16) * 8
-        chunked = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=pre, voltage=kv).cpu()
-    finally:
-        engine.WORKSPACE_BYTES = ws
+    # two frames per chunk: the accumulator goes through A between chunks
+    ws, engine.WORKSPACE_BYTES = engine.WORKSPACE_BYTES, 2 * shape[1] * (shape[2] // 2 + 16) * 8
+    chunked = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=pre, voltage=kv).cpu()
+    engine.WORKSPACE_BYTES = ws
     assert float((chunked - ref).abs().max()) <= 1e-4 * float(ref.abs().max())
-    try:
-        engine.FULL_ROW_MAJOR = False
-        old = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=pre, voltage=kv).cpu()
-    finally:
-        engine.FULL_ROW_MAJOR = True
+    engine.FULL_ROW_MAJOR = False
+    old = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=pre, voltage=kv).cpu()
+    engine.FULL_ROW_MAJOR = True
     assert float((got - old).abs().max()) <= 2e-5 * float(ref.abs().max())
-    try:  # 4096 / 4092 rows: the column pass fed from the column-major copy (default) == fed from the rows
-        engine.DOSE_COLUMN_MAJOR = False
-        rowfed = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=pre, voltage=kv).cpu()
-    finally:
-        engine.DOSE_COLUMN_MAJOR = True
+    # 4096 / 4092 rows: the column pass fed from the column-major copy (default) == fed from the rows
+    engine.DOSE_COLUMN_MAJOR = False
+    rowfed = mc.dose_weighted_sum(m.to(dev), ps, dose, pre_exposure=pre, voltage=kv).cpu()
+    engine.DOSE_COLUMN_MAJOR = True
     assert float((got - rowfed).abs().max()) <= 2e-6 * float(ref.abs().max())
 
 

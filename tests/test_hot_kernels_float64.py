@@ -45,42 +45,12 @@ import pytest
 import torch
 
 import hot_reference as hr
+from kernel_harness import calls, ratios_fixture, worse  # noqa: F401
 from rigid_reference import (assert_frames, condition_float64, conditioning_error, rigid_resample_gather_stack)
 
 pytestmark = pytest.mark.gpu
 
 F32, U = np.float32, hr.U
-
-
-class _Recorder:
-    """The loaded library with the names of the entry points that are called written down."""
-
-    def __init__(self, lib):
-        self._lib, self.names = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-
-        def call(*a):
-            self.names.append(name)
-            return fn(*a)
-
-        return call
-
-    def ran(self, *want, absent=()):
-        for name in want:
-            assert name in self.names, f"{name} did not run ({sorted(set(self.names))})"
-        for name in absent:
-            assert name not in self.names, f"{name} ran ({sorted(set(self.names))})"
-
-
-@pytest.fixture
-def calls(monkeypatch):
-    from torch_motion_correction_amd import _lib
-
-    rec = _Recorder(_lib.load())
-    monkeypatch.setattr(_lib, "load", lambda: rec)
-    return rec
 
 
 def _api():
@@ -103,20 +73,10 @@ def _ids(c):
     return "-".join("x".join(map(str, v)) if isinstance(v, tuple) else str(v) for v in c)
 
 
+ratios = ratios_fixture()
+
+
 # ------------------------------------------------------------------ mc_condition_movie
-
-
-@pytest.fixture(scope="module")
-def ratios():
-    r = {}
-    yield r
-    for k in sorted(r):
-        print(f"RATIO {k}: {r[k]:.3f}")
-
-
-def _worse(ratios, key, value):
-    ratios[key] = max(ratios.get(key, 0.0), value)
-    return value
 
 
 @pytest.mark.parametrize("case", hr.condition_cases(), ids=_ids)
@@ -144,7 +104,7 @@ def test_condition_movie_matches_float64(calls, dev, ratios, case):
     assert np.isnan(g[:32 + ooff]).all() and np.isnan(g[32 + ooff + n:]).all(), "wrote outside its output"
     r = hr.check_condition(out.cpu().numpy(), raw, gain, mean_zero, 3 if tiled else 15, _ids(case))
     print(f"RATIO mc_condition_movie {_ids(case)}: {r:.3f}")
-    _worse(ratios, "mc_condition_movie", r)
+    worse(ratios, "mc_condition_movie", r)
 
 
 # ------------------------------------------------------------------ mc_raw_movie_stats
@@ -180,7 +140,7 @@ def test_raw_movie_stats_match_float64(calls, dev, ratios, case):
     mb = hr.moment_bounds(x, box, True, 3 if tiled else 0, 8 if tiled else 0)
     r = max(hr.assert_within(stats, hr.moments64(x, box), mb, "moments"), _check_stats(fin, x, box, mean_zero, mb, _ids(case)))
     print(f"RATIO mc_raw_movie_stats {_ids(case)}: {r:.3f}")
-    _worse(ratios, "mc_raw_movie_stats", r)
+    worse(ratios, "mc_raw_movie_stats", r)
 
 
 # ------------------------------------------------------------------ hot pixels: detection, list, moments, output
@@ -255,9 +215,9 @@ def test_hot_detect_finalize_and_condition_hot_match_float64(calls, dev, ratios,
                                                   f"mc_condition_movie_hot {_ids(case)} mean_zero={mean_zero}"))
     calls.ran("mc_raw_hot_detect", "mc_raw_hot_finalize", "mc_condition_movie_hot")
     print(f"RATIO hot {_ids(case)}: list {r_list:.3f} moments {r_mom:.3f} finalize {r_fin:.3f} output {r_out:.3f}")
-    _worse(ratios, "hot list r", r_list)
-    _worse(ratios, "hot moments", max(r_mom, r_fin))
-    _worse(ratios, "hot conditioned output", r_out)
+    worse(ratios, "hot list r", r_list)
+    worse(ratios, "hot moments", max(r_mom, r_fin))
+    worse(ratios, "hot conditioned output", r_out)
 
 
 def test_hot_route_through_the_engine_gives_the_same_list(calls, dev):
@@ -337,7 +297,7 @@ def test_xc_rows_hot_correct_matches_float64(calls, dev, ratios, shape, variant)
     r = hr.check_rows(T1, Td.cpu().numpy(), keys, rv, mask, float(rstd), h, w, nkx, y0, ny, frame0, njobs,
                       f"mc_xc_rows_hot_correct {shape} {variant}")
     print(f"RATIO mc_xc_rows_hot_correct {shape} {variant}: {r:.3f}")
-    _worse(ratios, "mc_xc_rows_hot_correct", r)
+    worse(ratios, "mc_xc_rows_hot_correct", r)
 
 
 @pytest.mark.parametrize("variant", ["all", "single", "first-in-window"])
@@ -366,7 +326,7 @@ def test_full_rows_hot_correct_matches_float64(calls, dev, ratios, shape, varian
     r = hr.check_rows(S[:, :, :nkx].transpose(0, 2, 1, 3), got[:, :, :nkx].transpose(0, 2, 1, 3), keys, rv, None, 1.0, h, w,
                       nkx, 0, h, frame0, njobs, f"mc_full_rows_hot_correct {shape} {variant}")
     print(f"RATIO mc_full_rows_hot_correct {shape} {variant}: {r:.3f}")
-    _worse(ratios, "mc_full_rows_hot_correct", r)
+    worse(ratios, "mc_full_rows_hot_correct", r)
 
 
 # ------------------------------------------------------------------ warp corrections
@@ -394,7 +354,7 @@ def test_warp_hot_corrections_match_float64(calls, dev, ratios, case):
     frames, total = engine.warp_rigid_raw(rm, None, 1.0, want_frames=True, want_sum=True, tables=(sd, scratch))
     torch.cuda.synchronize()
     calls.ran("mc_raw_hot_detect", "mc_raw_hot_finalize", "mc_warp_rigid_raw", "mc_warp_rigid_hot_taps", "mc_hot_scatter_add")
-    assert calls.names.count("mc_hot_scatter_add") == 2  # frames and sum
+    assert calls.count("mc_hot_scatter_add") == 2  # frames and sum
     sc = scratch.cpu()
     Wy = sc[:t * h * 5].view(t, h, 5).numpy()
     Wx = sc[t * h * 5:t * 5 * (h + w)].view(t, 5, w).numpy()
@@ -433,9 +393,9 @@ def test_warp_hot_corrections_match_float64(calls, dev, ratios, case):
                  + cs * U * as_ + U * (cs > 0) * (np.abs(ref_un).sum(0) + base.sum(0) + as_))
     r_sum = hr.assert_within(total.cpu().numpy(), want.sum(0), sum_bound, f"sum {_ids(case)}")
     print(f"RATIO warp hot {_ids(case)}: records {r_rec:.3f} frames {r_frames:.3f} sum {r_sum:.3f}")
-    _worse(ratios, "warp records", r_rec)
-    _worse(ratios, "warp frames", r_frames)
-    _worse(ratios, "warp sum", r_sum)
+    worse(ratios, "warp records", r_rec)
+    worse(ratios, "warp frames", r_frames)
+    worse(ratios, "warp sum", r_sum)
 
 
 def test_hot_scatter_add_on_hand_built_runs(calls, dev, ratios):
@@ -452,5 +412,5 @@ def test_hot_scatter_add_on_hand_built_runs(calls, dev, ratios):
         assert np.isnan(g[:32]).all() and np.isnan(g[32 + limit:]).all(), "wrote outside out"
         r = hr.check_scatter(out, od.cpu().numpy(), keys, vals, limit, "mc_hot_scatter_add")
         print(f"RATIO mc_hot_scatter_add m={len(keys)}: {r:.3f}")
-        _worse(ratios, "mc_hot_scatter_add", r)
+        worse(ratios, "mc_hot_scatter_add", r)
     calls.ran("mc_hot_scatter_add")

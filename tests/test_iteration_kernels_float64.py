@@ -36,6 +36,7 @@ import pytest
 import torch
 
 import iteration_reference as ir
+from kernel_harness import ratios_fixture, worse
 
 pytestmark = pytest.mark.gpu
 
@@ -54,16 +55,7 @@ def _ids(c):
     return "x".join(map(str, c)) if isinstance(c, tuple) else str(c)
 
 
-@pytest.fixture(scope="module")
-def ratios():
-    r = {}
-    yield r
-    for k in sorted(r):
-        print(f"RATIO {k}: {r[k]:.3f}")
-
-
-def _worse(ratios, key, value):
-    ratios[key] = max(ratios.get(key, 0.0), value)
+ratios = ratios_fixture()
 
 
 class _Guarded:
@@ -129,8 +121,8 @@ def test_loss_kernels_match_float64(dev, ratios, case):
             got = _loss_launch(1, Pd, sd, fyd, fxd, hd, abd, case, dev, f"mc_local_ncc_grad {what}")
             worst[1] = max(worst[1], ir.assert_within(got, ref, bound, f"mc_local_ncc_grad {what}"))
     print(f"RATIO loss kernels {_ids(case)}: sums {worst[0]:.3f} ncc grad {worst[1]:.3f}")
-    _worse(ratios, "mc_local_loss_sums", worst[0])
-    _worse(ratios, "mc_local_ncc_grad", worst[1])
+    worse(ratios, "mc_local_loss_sums", worst[0])
+    worse(ratios, "mc_local_ncc_grad", worst[1])
 
 
 def test_local_motion_problem_runs_more_than_one_tile(dev, ratios):
@@ -156,13 +148,13 @@ def test_local_motion_problem_runs_more_than_one_tile(dev, ratios):
         torch.cuda.synchronize()
         ref, bound = ir.loss_tiles64(P, shifts, fy, fx, hx if hermitian else None)
         rr = ir.assert_within(got.cpu().numpy(), ref.sum(axis=1), bound.sum(axis=1), f"LocalMotionProblem.sums {loss_type}")
-        _worse(ratios, "LocalMotionProblem.sums", rr)
+        worse(ratios, "LocalMotionProblem.sums", rr)
         print(f"RATIO LocalMotionProblem.sums {loss_type} ({prob.nkx} x {prob.nky} bins, {prob.ntiles} tiles): {rr:.3f}")
     got = prob.ncc_grad_sums(sd, abd)
     torch.cuda.synchronize()
     ref, bound = ir.ncc_grad_tiles64(P, shifts, fy, fx, hx, ab)
     rr = ir.assert_within(got.cpu().numpy(), ref.sum(axis=1), bound.sum(axis=1), "LocalMotionProblem.ncc_grad_sums")
-    _worse(ratios, "LocalMotionProblem.ncc_grad_sums", rr)
+    worse(ratios, "LocalMotionProblem.ncc_grad_sums", rr)
     print(f"RATIO LocalMotionProblem.ncc_grad_sums: {rr:.3f}")
 
 
@@ -211,10 +203,10 @@ def test_aligned_refs_match_float64(dev, ratios, case):
         a, b = ir.check_aligned(Gp, REFp, ref4, f"mc_xc_aligned_refs_patches {_ids(case)} range {(q0, nq)}")
         pg, pr = max(pg, a), max(pr, b)
     print(f"RATIO aligned refs {_ids(case)}: G' {rg:.3f} REF {rr:.3f}; patches G' {pg:.3f} REF {pr:.3f}")
-    _worse(ratios, "mc_xc_aligned_refs G'", rg)
-    _worse(ratios, "mc_xc_aligned_refs REF", rr)
-    _worse(ratios, "mc_xc_aligned_refs_patches G'", pg)
-    _worse(ratios, "mc_xc_aligned_refs_patches REF", pr)
+    worse(ratios, "mc_xc_aligned_refs G'", rg)
+    worse(ratios, "mc_xc_aligned_refs REF", rr)
+    worse(ratios, "mc_xc_aligned_refs_patches G'", pg)
+    worse(ratios, "mc_xc_aligned_refs_patches REF", pr)
 
 
 # ------------------------------------------------------------------ mc_xc_refine_update and its patch form
@@ -264,7 +256,7 @@ def test_update_kernels_match_float64(dev, ratios, t):
                                                f"mc_xc_refine_update_patches {what} range {(q0, nq)}")
                 w["ps"], w["pm"] = max(w["ps"], a), max(w["pm"], b)
     print(f"RATIO update kernels t={t}: shifts {w['s']:.3f} max_r {w['m']:.3f}; patches shifts {w['ps']:.3f} max_r {w['pm']:.3f}")
-    _worse(ratios, "mc_xc_refine_update shifts", w["s"])
-    _worse(ratios, "mc_xc_refine_update max_r", w["m"])
-    _worse(ratios, "mc_xc_refine_update_patches shifts", w["ps"])
-    _worse(ratios, "mc_xc_refine_update_patches max_r", w["pm"])
+    worse(ratios, "mc_xc_refine_update shifts", w["s"])
+    worse(ratios, "mc_xc_refine_update max_r", w["m"])
+    worse(ratios, "mc_xc_refine_update_patches shifts", w["ps"])
+    worse(ratios, "mc_xc_refine_update_patches max_r", w["pm"])

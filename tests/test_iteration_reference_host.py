@@ -12,6 +12,7 @@ import torch
 
 import global_refine_reference as grr
 import iteration_reference as ir
+from kernel_harness import ratios_fixture, worse
 from oracle.local_motion import compute_loss
 
 F32, U = np.float32, ir.U
@@ -267,16 +268,7 @@ def update_patches_standin(c, q0, nq, H, W, under):
 # ------------------------------------------------------------------ the stand-in inside every bound, every shared case
 
 
-@pytest.fixture(scope="module")
-def ratios():
-    r = {}
-    yield r
-    for k in sorted(r):
-        print(f"RATIO fp32 stand-in {k}: {r[k]:.3f}")
-
-
-def _worse(ratios, key, value):
-    ratios[key] = max(ratios.get(key, 0.0), value)
+ratios = ratios_fixture("RATIO fp32 stand-in")
 
 
 @pytest.mark.parametrize("case", ir.LOSS_CASES, ids=lambda c: "x".join(map(str, c)))
@@ -287,10 +279,10 @@ def test_loss_standin_within_bounds(ratios, case):
             hx = ir.make_hx(hf, case[2])
             ref, bound = ir.loss_tiles64(c["P"], c["shifts"], c["fy"], c["fx"], hx)
             r = ir.assert_within(loss_standin(c, hx, 0), ref, bound, f"loss sums {case} {sf} {hf}")
-            _worse(ratios, "mc_local_loss_sums", r)
+            worse(ratios, "mc_local_loss_sums", r)
             ref, bound = ir.ncc_grad_tiles64(c["P"], c["shifts"], c["fy"], c["fx"], hx, c["ab"])
             r = ir.assert_within(loss_standin(c, hx, 1), ref, bound, f"ncc grad {case} {sf} {hf}")
-            _worse(ratios, "mc_local_ncc_grad", r)
+            worse(ratios, "mc_local_ncc_grad", r)
             if sf == "aligned":  # the float64 q and d2 are at rounding level: far below the absolute bound's own size
                 q = ir.loss_sums64(c["P"], c["shifts"], c["fy"], c["fx"], hx)
                 assert np.abs(q[..., :3]).max() <= 1e-4 * max(np.abs(q[..., 5]).max(), 1e-30) * case[1] ** 2, (case, hf)
@@ -303,15 +295,15 @@ def test_aligned_refs_standin_within_bounds(ratios, case):
     G, REF = aligned_standin(c["S"][:, None], c["shifts"][:, None], zero, c["fy"], c["fx"], c["under"], 0, 1)
     rg, rr = ir.check_aligned(G[:, 0], REF[:, 0], ir.aligned_refs64(c["S"], c["shifts"], c["fy"], c["fx"], c["under"], True),
                               f"aligned refs {case}")
-    _worse(ratios, "mc_xc_aligned_refs G'", rg)
-    _worse(ratios, "mc_xc_aligned_refs REF", rr)
+    worse(ratios, "mc_xc_aligned_refs G'", rg)
+    worse(ratios, "mc_xc_aligned_refs REF", rr)
     p = ir.aligned_patch_case(case)
     for q0, nq in ir.PATCH_RANGES:
         G, REF = aligned_standin(p["S"], p["shifts"], p["offsets"], p["fy"], p["fx"], p["under"], q0, nq)
         ref4 = ir.aligned_refs_patches64(p["S"], p["shifts"], p["offsets"], p["fy"], p["fx"], p["under"], q0, nq, True)
         rg, rr = ir.check_aligned(G, REF, ref4, f"aligned refs patches {case} {(q0, nq)}")
-        _worse(ratios, "mc_xc_aligned_refs_patches G'", rg)
-        _worse(ratios, "mc_xc_aligned_refs_patches REF", rr)
+        worse(ratios, "mc_xc_aligned_refs_patches G'", rg)
+        worse(ratios, "mc_xc_aligned_refs_patches REF", rr)
 
 
 def _update_cases():
@@ -352,15 +344,15 @@ def test_update_standin_within_bounds(ratios):
         ref4 = ir.refine_update64(c["peaks"], c["nb"], c["shifts"], c["ref"], *shape, under, bounds=True)
         rs, rm = ir.check_update(*update_standin(c["peaks"], c["nb"], c["shifts"], c["ref"], *shape, under), ref4, c["ref"],
                                  f"update {(t, v, shape)}")
-        _worse(ratios, "mc_xc_refine_update shifts", rs)
-        _worse(ratios, "mc_xc_refine_update max_r", rm)
+        worse(ratios, "mc_xc_refine_update shifts", rs)
+        worse(ratios, "mc_xc_refine_update max_r", rm)
         for q0, nq in ir.PATCH_RANGES:
             p = ir.update_patch_case(t, v, shape, under, q0, nq)
             ref4 = ir.refine_update_patches64(p["peaks"], p["nb"], p["shifts"], p["ref"], q0, nq, *shape, under, p["max_r"], True)
             s, mr = update_patches_standin(p, q0, nq, *shape, under)
             rs, rm = ir.check_update_patches(s, mr, p["shifts"], p["max_r"], ref4, p["ref"], q0, nq, f"update patches {(t, v, shape, q0, nq)}")
-            _worse(ratios, "mc_xc_refine_update_patches shifts", rs)
-            _worse(ratios, "mc_xc_refine_update_patches max_r", rm)
+            worse(ratios, "mc_xc_refine_update_patches shifts", rs)
+            worse(ratios, "mc_xc_refine_update_patches max_r", rm)
 
 
 # ------------------------------------------------------------------ every comparison rejects its wrong stand-in

@@ -1,0 +1,214 @@
+"""tests/kernel_harness.py on the CPU: what "this entry point ran", "nothing was written outside the buffer" and "the
+same inputs as before" mean, pinned once for every kernel test that imports them."""
+
+import pytest
+import torch
+
+import kernel_harness as kh
+from kernel_harness import nan_empty, switches  # noqa: F401
+
+CPU = torch.device("cpu")
+
+
+# ------------------------------------------------------------------ Recorder
+
+
+class _FakeLib:
+    def mc_a(self, *a):
+        return ("a", a)
+
+    def mc_b(self, *a):
+        return ("b", a)
+
+
+def test_recorder_records_calls_not_lookups():
+    rec = kh.Recorder(_FakeLib())
+    fn = rec.mc_a  # looked up, never called
+    assert rec.names == [] and rec.args == {} and rec.count("mc_a") == 0
+    with pytest.raises(AssertionError, match="mc_a did not run"):
+        rec.ran("mc_a")
+    rec.ran(absent=("mc_a", "mc_b"))
+    assert fn(1, "x") == ("a", (1, "x"))  # the call goes through, with its arguments, and is written down
+    assert rec.mc_b(2) == ("b", (2,)) and rec.mc_a() == ("a", ())
+    assert rec.names == ["mc_a", "mc_b", "mc_a"]
+    assert rec.args == {"mc_a": [(1, "x"), ()], "mc_b": [(2,)]}
+    assert rec.count("mc_a") == 2 and rec.count("mc_b") == 1 and rec.count("mc_c") == 0
+    with pytest.raises(AttributeError):
+        rec.mc_c  # a missing entry point stays an error
+    assert rec._lib.mc_a(3) == ("a", (3,)) and rec.count("mc_a") == 2  # the library itself is not recorded
+
+
+def test_recorder_ran_absent_only_and_clear():
+    rec = kh.Recorder(_FakeLib())
+    rec.mc_a(1)
+    rec.mc_a(2)
+    rec.ran("mc_a", absent=("mc_b",))
+    rec.only("mc_a", 2)
+    with pytest.raises(AssertionError, match="mc_b did not run"):
+        rec.ran("mc_a", "mc_b")
+    with pytest.raises(AssertionError, match="mc_a ran"):
+        rec.ran(absent=("mc_a",))
+    with pytest.raises(AssertionError, match="expected 1 x mc_a"):
+        rec.only("mc_a", 1)
+    rec.mc_b()
+    with pytest.raises(AssertionError, match="expected 2 x mc_a"):
+        rec.only("mc_a", 2)  # another entry point ran too
+    rec.clear()
+    assert rec.names == [] and rec.args == {} and rec.count("mc_a") == 0
+    rec.only("mc_a", 0)
+    rec.ran(absent=("mc_a", "mc_b"))
+
+
+# ------------------------------------------------------------------ NaN-guarded buffers
+
+
+@pytest.mark.parametrize("offset", [0, 1, 2, 3])
+def test_nan_buffer_alignment_and_guards(offset):
+    shape = (3, 5, 7)
+    view, flat = kh.nan_buffer(shape, CPU, offset)
+    n = 3 * 5 * 7
+    lead = (view.data_ptr() - flat.data_ptr()) // 4
+    assert tuple(view.shape) == shape and view.dtype == torch.float32 and view.is_contiguous()
+    assert flat.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 * offset
+    assert lead >= kh.GUARD and flat.numel() - lead - n >= kh.GUARD and kh.GUARD >= 8
+    assert bool(torch.isnan(flat).all())
+    kh.assert_guards(view, flat, "untouched")
+    view.fill_(1.0)  # writing all of the buffer, and nothing else, passes
+    kh.assert_guards(view, flat, "filled")
+    for at in (lead - 1, lead + n):  # one element before the view, one element past it
+        saved = flat[at].clone()
+        flat[at] = 0.0
+        with pytest.raises(AssertionError, match="wrote outside its output buffer"):
+            kh.assert_guards(view, flat, "one write")
+        flat[at] = saved
+    kh.assert_guards(view, flat, "restored")
+
+
+def test_nan_and_nan_empty(nan_empty):
+    assert bool(torch.isnan(kh.nan((2, 3), CPU)).all()) and kh.nan((2, 3), CPU).dtype == torch.float32
+    assert bool(torch.isnan(torch.empty(4, 5)).all()) and bool(torch.isnan(torch.empty((3,), dtype=torch.float64)).all())
+    assert torch.empty(6, dtype=torch.int32).dtype == torch.int32  # integer buffers are handed out as they are
+
+
+# ------------------------------------------------------------------ inputs: the values every kernel test has seen so far
+
+# Recorded from the functions of tests/test_rigid_kernels_float64.py before they moved here: (sum, first row of frame 0).
+RAW_2x8x16 = {
+    torch.uint8: (7844, [44, 17, 47, 43, 49, 17, 16, 37, 10, 50, 33, 34, 14, 36, 39, 38]),
+    torch.int16: (37168, [252, 36, 273, 245, 289, 38, 30, 193, -16, 302, 167, 170, 12, 187, 215, 206]),
+}
+GAIN_8x16_ROW0 = ["0x1.ee46b60000000p+1", "0x1.1114c40000000p+1", "0x1.053e3c0000000p-1", "0x1.37c8c60000000p-2",
+                  "0x1.6a49ce0000000p+1", "0x1.1e0dd20000000p-1", "0x1.aeca2a0000000p+1", "0x1.9c5ab20000000p-1",
+                  "0x1.7a6e3c0000000p-1", "0x1.b2d9860000000p-1", "0x1.e2f79c0000000p-2", "0x1.3c2fe00000000p-1",
+                  "0x1.1f78520000000p+0", "0x1.9a48700000000p-1", "0x1.43a7940000000p-1", "0x1.de7f040000000p+1"]
+GAIN_8x16_SUM = float.fromhex("0x1.67a0204900000p+7")
+
+
+@pytest.mark.parametrize("dtype", [torch.uint8, torch.int16], ids=["uint8", "int16"])
+def test_raw_movie_is_the_recorded_one(dtype):
+    total, row = RAW_2x8x16[dtype]
+    raw = kh.raw_movie(2, 8, 16, dtype, 5)
+    assert raw.dtype == dtype and tuple(raw.shape) == (2, 8, 16)
+    assert int(raw.long().sum()) == total and raw[0, 0].tolist() == row
+    # the static recipe is the drifting one at zero drift without a margin; a drift crops the same texture
+    assert torch.equal(raw, kh.drifting_raw_movie([0, 0], [0, 0], 8, 16, dtype, 5, pad=0))
+    assert not torch.equal(kh.drifting_raw_movie([0, 0], [0, 0], 8, 16, dtype, 5, pad=4), raw)
+    if dtype == torch.int16:
+        assert int(raw.min()) < 0  # negative counts occur
+
+
+def test_gain_is_the_recorded_one():
+    g = kh.gain(8, 16)
+    assert g.dtype == torch.float32 and tuple(g.shape) == (8, 16)
+    assert [float(v).hex() for v in g[0]] == GAIN_8x16_ROW0
+    # 4 ** x differs in the last bit of a few elements between the scalar and the vector code of the CPU library: the
+    # sum over all 128 is held to 128 such bits of its largest element, 4 (a different seed moves it by O(10))
+    assert abs(float(g.double().sum()) - GAIN_8x16_SUM) <= 128 * 2.0 ** -22
+    assert float(g.min()) >= 0.25 and float(g.max()) <= 4.0 and float(g.max() / g.min()) > 8
+    assert torch.equal(kh.gain(8, 16, seed=9), g) and not torch.equal(kh.gain(8, 16, seed=10), g)
+
+
+def test_gain_refuses_a_small_dynamic_range(monkeypatch):
+    monkeypatch.setattr(torch, "rand", lambda h, w, generator=None: torch.full((h, w), 0.5))
+    with pytest.raises(AssertionError):
+        kh.gain(8, 16)
+
+
+def test_float_stack_and_offset_copy():
+    a = kh.float_stack(2, 5, 8)
+    g = torch.Generator().manual_seed(2 * 7919 + 5 * 31 + 8)
+    assert torch.equal(a, torch.randn(2, 5, 8, generator=g) * 2 + 5) and not bool((a == 0).any())
+    assert torch.equal(kh.float_stack(2, 5, 8, torch.float16), a.half())
+    for src, size in ((a, 4), (a.half(), 2)):
+        for offset in (0, 1, 3):
+            view = kh.offset_copy(src, offset)
+            assert torch.equal(view, src) and view.data_ptr() % 16 == size * offset
+
+
+def test_rel_err_and_assert_sum():
+    import numpy as np
+
+    want, bound = np.full((2, 3), 2.0), np.full((2, 3), 0.5)
+    got = torch.full((2, 3), 2.0)
+    got[0, 1], got[1, 2] = 2.25, 1.75
+    assert kh.rel_err(got, torch.from_numpy(want)) == 0.125
+    assert kh.assert_sum(got, want, bound, "sum") == 0.5
+    border = np.zeros((2, 3), dtype=bool)
+    border[0, 1] = border[1, 2] = True
+    assert kh.assert_sum(got, want, bound, "sum", border) == 0.0
+    got[1, 0] = 2.75
+    with pytest.raises(AssertionError, match=r"1 pixels of the sum beyond the bound, first \(row, col\) \[\(1, 0\)\]"):
+        kh.assert_sum(got, want, bound, "sum", border | True)  # the border only leaves pixels out of the ratio
+
+
+# ------------------------------------------------------------------ ratios
+
+
+def test_worse_keeps_the_maximum_and_returns_the_value():
+    r = {}
+    assert kh.worse(r, "k", 0.25) == 0.25 and kh.worse(r, "k", 0.125) == 0.125 and kh.worse(r, "a b", 1.0) == 1.0
+    assert r == {"k": 0.25, "a b": 1.0}
+    assert kh.ratio_lines(r) == ["RATIO a b: 1.000", "RATIO k: 0.250"]
+    assert kh.ratio_lines(r, "RATIO fp32 stand-in") == ["RATIO fp32 stand-in a b: 1.000", "RATIO fp32 stand-in k: 0.250"]
+
+
+ratios = kh.ratios_fixture("RATIO harness")
+
+
+@pytest.mark.parametrize("visit", [0, 1])
+def test_ratios_fixture_hands_out_one_dict_per_module(ratios, visit):
+    before, value = ratios.get("seen", 0.0), 1.0 - visit / 2
+    assert kh.worse(ratios, "seen", value) == value and ratios == {"seen": max(before, value)}
+
+
+# ------------------------------------------------------------------ switches
+
+
+def _switch_values():
+    from torch_motion_correction_amd import engine, plan
+
+    return {**{n: getattr(engine, n) for n in kh.ENGINE_SWITCHES}, "USE_DIRECT_LINES": plan.USE_DIRECT_LINES}
+
+
+@pytest.fixture
+def former():
+    """Set up before `switches`, torn down after it: the values before the test against the values after."""
+    before = _switch_values()
+    yield before
+    from torch_motion_correction_amd import plan
+
+    assert _switch_values() == before and plan._LINES == {}
+
+
+def test_switches_restores_every_switch_assigned_in_the_body(former, switches):
+    engine, plan = switches
+    assert set(former) == {"FUSED_SEARCH", "USE_ROW_CHORDS", "WORKSPACE_BYTES", "FULL_ROW_MAJOR", "DOSE_COLUMN_MAJOR",
+                           "POLYPHASE_FOURIER_SHIFT", "USE_DIRECT_LINES"}
+    assert plan._LINES == {}
+    for name in kh.ENGINE_SWITCHES:
+        value = getattr(engine, name)
+        setattr(engine, name, value + 12345 if name == "WORKSPACE_BYTES" else not value)  # plainly, as the tests do
+    plan.USE_DIRECT_LINES = not plan.USE_DIRECT_LINES
+    plan._LINES["stale"] = None
+    assert all(_switch_values()[k] != v for k, v in former.items())
+

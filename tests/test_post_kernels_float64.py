@@ -57,63 +57,12 @@ import pytest
 import torch
 
 import post_reference as pr
+from kernel_harness import calls, nan, nan_empty  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 U = pr.U
 F32 = np.float32
-
-
-class _Recorder:
-    """The loaded library with the names (and arguments) of the entry points that are called written down."""
-
-    def __init__(self, lib):
-        self._lib, self.names, self.args = lib, [], {}
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-
-        def call(*a):
-            self.names.append(name)
-            self.args.setdefault(name, []).append(a)
-            return fn(*a)
-
-        return call
-
-    def count(self, name):
-        return self.names.count(name)
-
-    def clear(self):
-        del self.names[:]
-        self.args.clear()
-
-    def only(self, name, times):
-        assert self.names == [name] * times, f"expected {times} x {name}, ran {self.names}"
-
-
-@pytest.fixture
-def calls(monkeypatch):
-    from torch_motion_correction_amd import _lib
-
-    rec = _Recorder(_lib.load())
-    monkeypatch.setattr(_lib, "load", lambda: rec)
-    return rec
-
-
-@pytest.fixture
-def nan_empty(monkeypatch):
-    """torch.empty hands out NaN-filled floating-point buffers: what a kernel leaves unwritten fails its comparison."""
-    real = torch.empty
-
-    def empty(*a, **k):
-        out = real(*a, **k)
-        return out.fill_(float("nan")) if out.is_floating_point() else out
-
-    monkeypatch.setattr(torch, "empty", empty)
-
-
-def _nan(shape, dev):
-    return torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
 
 
 def _close(got, want, bound, what):
@@ -149,7 +98,7 @@ def _ref_spectra(dev, calls, table, u, v):
     sp, si, sr = lattice.leave_one_out_schedule(table)
     sp, si, sr = (torch.from_numpy(a).to(dev) for a in (sp, si, sr))
     ud, vd = torch.from_numpy(u).to(dev), torch.from_numpy(v).to(dev)
-    ref = _nan(u.shape, dev)
+    ref = nan(u.shape, dev)
     calls.clear()
     check(lib.mc_xc_ref_mean_except_current(ptr(ud), ptr(vd), ptr(sp), ptr(si), ptr(sr), ptr(ref), t, npatch, length,
                                             1.0 / (t - 1), stream_ptr(dev)), "mc_xc_ref_mean_except_current")
@@ -185,7 +134,7 @@ def _smooth(dev, calls, x, window, subtract_mean, in_place=False):
     lib = _lib.load()
     _, t, npatch = x.shape
     xd = torch.from_numpy(x).to(dev)
-    out = xd if in_place else _nan(x.shape, dev)
+    out = xd if in_place else nan(x.shape, dev)
     calls.clear()
     check(lib.mc_field_smooth_center(ptr(xd), ptr(out), t, npatch, window, subtract_mean, stream_ptr(dev)),
           "mc_field_smooth_center")
@@ -346,7 +295,7 @@ def test_circle_mask(dev, calls, case):
 
     h, w, r, s = case
     inside, ring, value, halfw = pr.mask64(*case)
-    mask = _nan((h, w), dev)
+    mask = nan((h, w), dev)
     hw = torch.full((h,), -7, dtype=torch.int32, device=dev)
     calls.clear()
     check(_lib.load().mc_circle_mask(ptr(mask), ptr(hw), h, w, float(r), float(s), stream_ptr(dev)), "mc_circle_mask")
@@ -374,7 +323,7 @@ def test_xc_filter(dev, calls, case):
     low, high = plan.band_limits(band, ps)
     g = plan.xc_geometry(H, W, high, min(H, W) / 4, min(H, W) / 8)
     kept, value, bound = pr.filter64(W, H, g.nkx, g.kyp, g.kyn, low, high, B, ps)
-    filt = _nan((g.nkx, g.nky), dev)
+    filt = nan((g.nkx, g.nky), dev)
     calls.clear()
     check(_lib.load().mc_xc_filter(ptr(filt), g, low, high, float(B), float(ps), stream_ptr(dev)), "mc_xc_filter")
     torch.cuda.synchronize()

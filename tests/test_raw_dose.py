@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import oracle
+from kernel_harness import mc, rel_err, switches  # noqa: F401
 from oracle import thirdparty_semantics as tp
 from torch_motion_correction_amd import _lib, engine
 
@@ -19,18 +20,6 @@ pytestmark = pytest.mark.gpu
 
 REL = 2e-5
 HOT = 10.0
-
-
-@pytest.fixture(scope="module")
-def mc():
-    import torch_motion_correction_amd as m
-
-    return m
-
-
-def rel_err(a, b):
-    a, b = a.detach().cpu().double(), b.detach().cpu().double()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
 
 
 def raw_movie(dev, t, h, w, dtype, seed, hot=False):
@@ -123,7 +112,7 @@ def test_fused_equals_the_conditioned_route(mc, dev, shape, case, monkeypatch):
 
 
 @pytest.mark.parametrize("rigid", [True, False])
-def test_chunks_accumulate_the_plain_sum_in_order(mc, dev, rigid):
+def test_chunks_accumulate_the_plain_sum_in_order(mc, dev, switches, rigid):
     """Two frames per chunk, 7 frames: chunks [0,2) [2,4) [4,6) [6,7)."""
     t, h, w, ps = 7, 1024, 1024, 1.0
     raw, gain = raw_movie(dev, t, h, w, torch.uint8, seed=5)
@@ -134,12 +123,10 @@ def test_chunks_accumulate_the_plain_sum_in_order(mc, dev, rigid):
     dose = dict(dose_per_frame=0.9, pre_exposure=0.5, voltage=200.0)
     whole_plain = mc.motion_correct_sum_raw(raw, gain, field, ps)
     pitch = _lib.load().mc_full_spectrum_pitch(w)
-    try:
-        ws, engine.WORKSPACE_BYTES = engine.WORKSPACE_BYTES, 2 * h * pitch * 8
-        dw, plain = mc.motion_correct_sum_raw(raw, gain, field, ps, return_plain_sum=True, **dose)
-        want_dw, _ = conditioned(mc, raw, gain, field, ps, **dose)
-    finally:
-        engine.WORKSPACE_BYTES = ws
+    ws, engine.WORKSPACE_BYTES = engine.WORKSPACE_BYTES, 2 * h * pitch * 8
+    dw, plain = mc.motion_correct_sum_raw(raw, gain, field, ps, return_plain_sum=True, **dose)
+    want_dw, _ = conditioned(mc, raw, gain, field, ps, **dose)
+    engine.WORKSPACE_BYTES = ws
     assert rel_err(dw, want_dw) <= REL
     rm = engine.RawMovie(raw, gain)
     lat = engine.frame_lattices(field, t, grid_type)

@@ -55,6 +55,8 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import (assert_guards, assert_sum, float_stack, lib, mc, nan_buffer, offset_copy,  # noqa: F401
+                            raw_setup)
 from rigid_reference import (KERNEL_CASES, RECENTRE_SHIFTS, assert_frames, condition_float64, conditioning_error,
                              kernel_case_shifts, rigid_resample_gather_stack)
 
@@ -62,50 +64,9 @@ pytestmark = pytest.mark.gpu
 
 ULP = 2.0 ** -24
 MODES = ("frames", "sum", "frames+sum")
-GUARD = 8  # NaN words kept on either side of an output buffer
-
-
-@pytest.fixture(scope="module")
-def mc():
-    import torch_motion_correction_amd as m
-
-    return m
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from torch_motion_correction_amd import _lib
-
-    return _lib.load()
 
 
 # ------------------------------------------------------------------ buffers and launches
-
-
-def _nan_buffer(shape, dev, offset=0):
-    """A NaN-filled fp32 buffer of `shape` that starts `offset` floats past a 16-byte boundary, inside a larger
-    NaN-filled allocation -> (view, whole allocation)."""
-    n = int(np.prod(shape))
-    lead = 4 * ((GUARD + 3) // 4) + offset
-    flat = torch.full((lead + n + GUARD,), float("nan"), dtype=torch.float32, device=dev)
-    assert flat.data_ptr() % 16 == 0
-    view = flat[lead:lead + n].view(*shape)
-    assert view.data_ptr() % 16 == (4 * offset) % 16
-    return view, flat
-
-
-def _assert_guards(view, flat, what):
-    n, lead = view.numel(), (view.data_ptr() - flat.data_ptr()) // 4
-    assert bool(torch.isnan(flat[:lead]).all()) and bool(torch.isnan(flat[lead + n:]).all()), \
-        f"{what}: wrote outside its output buffer"
-
-
-def _offset_copy(src, offset):
-    """`src` copied to `offset` elements past a 16-byte boundary of a larger allocation."""
-    flat = torch.zeros(src.numel() + 16, dtype=src.dtype, device=src.device)
-    view = flat[offset:offset + src.numel()].view(src.shape)
-    view.copy_(src)
-    return view
 
 
 def _scratch(lib, t, h, w, dev):
@@ -183,19 +144,6 @@ def _sum_bound(ref, bound):
     return bound.sum(0) + ref.shape[0] * ULP * np.abs(ref).sum(0)
 
 
-def _assert_sum(total, want, bound, what):
-    got = total.detach().cpu().double().numpy()
-    d = np.abs(got - want)
-    ok = d <= bound
-    if not bool(ok.all()):
-        bad = np.argwhere(~ok)
-        raise AssertionError(f"{what}: {len(bad)} pixels of the sum beyond the bound, first (row, col) "
-                             f"{[tuple(int(v) for v in b) for b in bad[:8]]}: got {got[tuple(bad[0])]!r} "
-                             f"want {want[tuple(bad[0])]!r} bound {bound[tuple(bad[0])]!r}")
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return float(np.nan_to_num(d / bound, nan=0.0, posinf=0.0).max())
-
-
 def _run_case(lib, launch, reference, shape, shifts, dev, what, frames_offset=0, sum_offset=0, modes=MODES):
     """Every chunk of t shifts x every output combination against the reference (computed once per chunk).
     Returns the worst |got - ref| / bound of the frames and of the sums."""
@@ -209,16 +157,16 @@ def _run_case(lib, launch, reference, shape, shifts, dev, what, frames_offset=0,
         sum_bound = _sum_bound(ref, bound)
         for mode in modes:
             tag = f"{what} shifts {chunk.tolist()} [{mode}]"
-            frames, frames_all = _nan_buffer((t, h, w), dev, frames_offset) if "frames" in mode else (None, None)
-            total, total_all = _nan_buffer((h, w), dev, sum_offset) if "sum" in mode else (None, None)
+            frames, frames_all = nan_buffer((t, h, w), dev, frames_offset) if "frames" in mode else (None, None)
+            total, total_all = nan_buffer((h, w), dev, sum_offset) if "sum" in mode else (None, None)
             launch(sd, scratch, frames, total, 0)
             torch.cuda.synchronize()
             if frames is not None:
-                _assert_guards(frames, frames_all, tag)
+                assert_guards(frames, frames_all, tag)
                 worst_f = max(worst_f, assert_frames(frames, ref, bound, tag))
             if total is not None:
-                _assert_guards(total, total_all, tag)
-                worst_s = max(worst_s, _assert_sum(total, ref.sum(0), sum_bound, tag))
+                assert_guards(total, total_all, tag)
+                worst_s = max(worst_s, assert_sum(total, ref.sum(0), sum_bound, tag))
             del frames, frames_all, total, total_all
     print(f"RATIO {what}: frames {worst_f:.3f} sum {worst_s:.3f}")
     return worst_f, worst_s
@@ -231,19 +179,14 @@ def _assert_phases_split(lib, launch, shape, shifts, dev, what):
     out = []
     for phases in ((0,), (1, 2)):
         scratch = _scratch(lib, t, h, w, dev)
-        frames, _ = _nan_buffer((t, h, w), dev)
-        total, _ = _nan_buffer((h, w), dev)
+        frames, _ = nan_buffer((t, h, w), dev)
+        total, _ = nan_buffer((h, w), dev)
         for ph in phases:
             launch(sd, scratch, None if ph == 1 else frames, None if ph == 1 else total, ph)
         torch.cuda.synchronize()
         out.append((frames, total))
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1]), what
     assert not bool(torch.isnan(out[0][0]).any()) and not bool(torch.isnan(out[0][1]).any()), what
-
-
-def _float_stack(t, h, w, dtype=torch.float32):
-    g = torch.Generator().manual_seed(t * 7919 + h * 31 + w)
-    return (torch.randn(t, h, w, generator=g) * 2 + 5).to(dtype)  # no sample is zero (asserted by the reference)
 
 
 def _case_id(case):
@@ -260,7 +203,7 @@ def test_warp_rigid_dma_matches_the_float64_resampler(lib, dev, case):
     9 tiles, no remap; (2, 4096, 4096): the benchmark geometry, 1024 tiles (with fractional
     shifts).  The first case also runs the phase 1 + phase 2 split."""
     t, h, w = case[:3]
-    src = _float_stack(t, h, w)
+    src = float_stack(t, h, w)
     launch = _float_launcher(lib, src.to(dev))
     shifts = kernel_case_shifts(*case)
     _run_case(lib, launch, _float_reference(src), (t, h, w), shifts, dev, f"warp_rigid_dma {(t, h, w)}")
@@ -273,7 +216,7 @@ def test_warp_rigid_dma_unaligned_sum(lib, dev, case):
     """`out_sum` 4 bytes past a 16-byte boundary of a larger buffer, frames aligned: the scalar-store branch of the
     sum (full tiles, and a last tile of one row and one quad)."""
     t, h, w = case[:3]
-    src = _float_stack(t, h, w)
+    src = float_stack(t, h, w)
     _run_case(lib, _float_launcher(lib, src.to(dev)), _float_reference(src), (t, h, w), kernel_case_shifts(*case),
               dev, f"warp_rigid_dma unaligned sum {(t, h, w)}", sum_offset=1, modes=("sum", "frames+sum"))
 
@@ -290,8 +233,8 @@ def test_warp_rigid_register_tile_matches_the_float64_resampler(lib, dev, case, 
     """The fallback kernel: w % 4 != 0 ((3, 130, 250), (2, 96, 1030)), and w % 4 == 0 with the frames -- or only
     out_frames -- one float off a 16-byte boundary, where dma_ok is false although the rows are whole quads."""
     t, h, w = case[:3]
-    src = _float_stack(t, h, w)
-    sd = src.to(dev) if variant != "frames pointer + 4 bytes" else _offset_copy(src.to(dev), 1)
+    src = float_stack(t, h, w)
+    sd = src.to(dev) if variant != "frames pointer + 4 bytes" else offset_copy(src.to(dev), 1)
     assert sd.data_ptr() % 16 == (4 if variant == "frames pointer + 4 bytes" else 0)
     launch = _float_launcher(lib, sd)
     shifts = kernel_case_shifts(*case)
@@ -311,7 +254,7 @@ def test_warp_rigid_dma_h_matches_the_float64_resampler(lib, dev, case):
     of 512.  The bound is the fp32 one on the up-cast values.  The first case also runs the phase split, the last
     one an unaligned sum."""
     t, h, w = case[:3]
-    src = _float_stack(t, h, w, torch.float16)
+    src = float_stack(t, h, w, torch.float16)
     launch = _float_launcher(lib, src.to(dev))
     shifts = kernel_case_shifts(*case)
     _run_case(lib, launch, _float_reference(src), (t, h, w), shifts, dev, f"warp_rigid_dma_h {(t, h, w)}")
@@ -325,38 +268,6 @@ def test_warp_rigid_dma_h_matches_the_float64_resampler(lib, dev, case):
 # ------------------------------------------------------------------ raw u8 / i16: warp_rigid_raw
 
 
-def _raw_movie(t, h, w, dtype, seed):
-    """test_rigid_routes._raw_movie's recipe without a drift: a static texture in [10, 50) + noise, rounded to the
-    detector's integers (i16: scaled and offset so that negative counts occur)."""
-    g = torch.Generator().manual_seed(seed)
-    base = torch.rand(h, w, generator=g) * 40 + 10
-    raw = torch.empty((t, h, w), dtype=dtype)
-    for f in range(t):
-        v = base + 2 * torch.randn(h, w, generator=g)
-        raw[f] = (v * 8 - 100).round().clamp(-32768, 32767).to(dtype) if dtype == torch.int16 else \
-            v.round().clamp(0, 255).to(dtype)
-    return raw
-
-
-def _gain(h, w, seed=9):
-    """A gain reference with a large dynamic range, log-uniform in [0.25, 4]: a wrong gain row or column (a cache
-    offset error) changes the output by a factor, which a constant or near-constant gain would hide."""
-    g = torch.Generator().manual_seed(seed + h * 7 + w)
-    gain = 4.0 ** (2 * torch.rand(h, w, generator=g) - 1)
-    assert float(gain.min()) >= 0.25 and float(gain.max()) <= 4.0 and float(gain.max() / gain.min()) > 8
-    return gain
-
-
-def _raw_setup(dev, t, h, w, dtype, with_gain, seed):
-    from torch_motion_correction_amd import engine
-
-    raw = _raw_movie(t, h, w, dtype, seed)
-    gain = _gain(h, w) if with_gain else None
-    rm = engine.RawMovie(raw.to(dev), None if gain is None else gain.to(dev))  # kind, mu; ones for no gain
-    torch.cuda.synchronize()
-    return raw, gain, rm
-
-
 _RAW_PARAMS = [(case, dtype) for case in KERNEL_CASES["warp_rigid_raw"] for dtype in (torch.uint8, torch.int16)
                if not (dtype == torch.int16 and case[1] == 4096)]  # 4096^2: u8 only
 
@@ -368,7 +279,7 @@ def test_warp_rigid_raw_matches_the_float64_resampler(lib, dev, case, dtype, wit
     one, against the float64 conditioning + resampler; mu and kind come from engine.RawMovie.  (6, 33, 516) also
     runs the phase split and an unaligned sum."""
     t, h, w = case[:3]
-    raw, gain, rm = _raw_setup(dev, t, h, w, dtype, with_gain, seed=500 + h)
+    raw, gain, rm = raw_setup(dev, t, h, w, dtype, with_gain, seed=500 + h)
     launch = _raw_launcher(lib, rm)
     reference = _raw_reference(raw, gain, rm.mu.cpu().numpy())
     shifts = kernel_case_shifts(*case)
@@ -386,7 +297,7 @@ def test_warp_rigid_raw_gain_cache_recentring(lib, dev, dtype):
     axes at once and return to the start (rigid_reference.RECENTRE_SHIFTS): the gain cache, centred with 8 spare
     rows and columns, is kept, re-centred and re-used.  Gain in [0.25, 4]; one full tile + edge tiles."""
     t, h, w = len(RECENTRE_SHIFTS), 72, 1028
-    raw, gain, rm = _raw_setup(dev, t, h, w, dtype, True, seed=640)
+    raw, gain, rm = raw_setup(dev, t, h, w, dtype, True, seed=640)
     _run_case(lib, _raw_launcher(lib, rm), _raw_reference(raw, gain, rm.mu.cpu().numpy()), (t, h, w),
               RECENTRE_SHIFTS, dev, f"warp_rigid_raw {str(dtype)[6:]} recentring")
 
@@ -394,7 +305,7 @@ def test_warp_rigid_raw_gain_cache_recentring(lib, dev, dtype):
 def test_warp_rigid_raw_at_its_frame_limit(lib, dev):
     """t = 256 = RR_PAR_MAX frames on (256, 64, 512) u8: the last slot of the per-frame parameter table."""
     t, h, w = 256, 64, 512
-    raw, gain, rm = _raw_setup(dev, t, h, w, torch.uint8, True, seed=256)
+    raw, gain, rm = raw_setup(dev, t, h, w, torch.uint8, True, seed=256)
     shifts = kernel_case_shifts(t, h, w, offset=3, n_pool=t - 4)
     assert len(shifts) == t
     _run_case(lib, _raw_launcher(lib, rm), _raw_reference(raw, gain, rm.mu.cpu().numpy()), (t, h, w), shifts, dev,
@@ -409,10 +320,10 @@ def test_raw_route_beyond_the_frame_limit_falls_back(mc, lib, dev):
     from torch_motion_correction_amd._lib import ptr, stream_ptr
 
     t, h, w, ps = 257, 64, 512, 0.83
-    raw, gain, rm = _raw_setup(dev, t, h, w, torch.uint8, True, seed=257)
+    raw, gain, rm = raw_setup(dev, t, h, w, torch.uint8, True, seed=257)
     px = torch.from_numpy(kernel_case_shifts(t, h, w, offset=5, n_pool=t - 4).copy())
     scratch = _scratch(lib, t, h, w, dev)
-    total, _ = _nan_buffer((h, w), dev)
+    total, _ = nan_buffer((h, w), dev)
     rc = lib.mc_warp_rigid_raw(ptr(rm.raw), rm.kind, ptr(rm.gain), ptr(rm.mu), t, h, w, ptr(px.to(dev)), ptr(scratch),
                                None, ptr(total), 0, stream_ptr(dev))
     assert rc == -2 and bool(torch.isnan(total).all())
@@ -422,7 +333,7 @@ def test_raw_route_beyond_the_frame_limit_falls_back(mc, lib, dev):
     sh = engine.frame_lattices(field.to(dev), t, "catmull_rom")[:, :, 0, 0].cpu().numpy() / np.float32(ps)
     ref, bound = _raw_reference(raw, gain, rm.mu.cpu().numpy())(sh.astype(np.float32))
     rf = assert_frames(fr, ref, bound, "motion_correct_sum_raw t=257 frames")
-    rs = _assert_sum(s, ref.sum(0), _sum_bound(ref, bound), "motion_correct_sum_raw t=257 sum")
+    rs = assert_sum(s, ref.sum(0), _sum_bound(ref, bound), "motion_correct_sum_raw t=257 sum")
     print(f"RATIO motion_correct_sum_raw t=257 (fallback): frames {rf:.3f} sum {rs:.3f}")
 
 
@@ -432,7 +343,7 @@ def test_warp_rigid_raw_accumulate_sums_two_chunks(lib, dev, dtype):
     and without frames.  Reference = the sum of both chunks' references; bound = both chunks' sum bounds + one fp32
     add per pixel for the second chunk (the first is added to zero, exactly)."""
     t, h, w, n = 6, 64, 2048, 3
-    raw, gain, rm = _raw_setup(dev, t, h, w, dtype, True, seed=77)
+    raw, gain, rm = raw_setup(dev, t, h, w, dtype, True, seed=77)
     mu = rm.mu.cpu().numpy()
     shifts = kernel_case_shifts(t, h, w, offset=6, n_pool=2)
     want, bound = np.zeros((h, w)), np.zeros((h, w))
@@ -444,17 +355,17 @@ def test_warp_rigid_raw_accumulate_sums_two_chunks(lib, dev, dtype):
         bound += _sum_bound(ref, fb)
     bound += ULP * (np.abs(refs[0][0].sum(0)) + np.abs(refs[1][0].sum(0)) + bound)
     for with_frames in (False, True):
-        total, total_all = _nan_buffer((h, w), dev)
+        total, total_all = nan_buffer((h, w), dev)
         total.zero_()
         for i, a in enumerate((0, n)):
             win = rm.window(a, n)
-            frames, frames_all = _nan_buffer((n, h, w), dev) if with_frames else (None, None)
+            frames, frames_all = nan_buffer((n, h, w), dev) if with_frames else (None, None)
             sd = torch.from_numpy(np.ascontiguousarray(shifts[a:a + n])).to(dev)
             _raw_launcher(lib, win, accumulate=True)(sd, _scratch(lib, n, h, w, dev), frames, total, 0)
             torch.cuda.synchronize()
             if with_frames:
-                _assert_guards(frames, frames_all, "accumulate frames")
+                assert_guards(frames, frames_all, "accumulate frames")
                 assert_frames(frames, refs[i][0], refs[i][1], f"accumulate {dtype} chunk {i} frames")
-        _assert_guards(total, total_all, "accumulate sum")
-        r = _assert_sum(total, want, bound, f"accumulate {dtype} frames={with_frames}")
+        assert_guards(total, total_all, "accumulate sum")
+        r = assert_sum(total, want, bound, f"accumulate {dtype} frames={with_frames}")
         print(f"RATIO mc_warp_rigid_raw_accumulate {str(dtype)[6:]} frames={with_frames}: sum {r:.3f}")

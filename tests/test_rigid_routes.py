@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_harness import drifting_raw_movie, mc, rel_err  # noqa: F401
 from rigid_reference import (FRAME_SPACINGS, LARGE_SHIFTS, PIPELINE_SPACINGS, RAW_SPACINGS, SMALL_SHIFTS,
                              TABLE_SPACINGS, assert_frames as _assert_frames, canonical_shift, coordinate_ulp,
                              neighbour_gradient, rigid_resample_stack)
@@ -16,13 +17,6 @@ from rigid_reference import (FRAME_SPACINGS, LARGE_SHIFTS, PIPELINE_SPACINGS, RA
 pytestmark = pytest.mark.gpu
 
 GRIDS = ("catmull_rom", "bspline")
-
-
-@pytest.fixture(scope="module")
-def mc():
-    import torch_motion_correction_amd as m
-
-    return m
 
 
 def _shift_table(t, values, offset=0):
@@ -222,23 +216,12 @@ def test_single_frame_movie_takes_the_same_route_everywhere(mc, dev, ps, grid):
 # ------------------------------------------------------------------ d. raw movies
 
 
-def _raw_movie(dy, dx, h, w, dtype, seed, pad=64):
-    g = torch.Generator().manual_seed(seed)
-    base = torch.rand(h + 2 * pad, w + 2 * pad, generator=g) * 40 + 10
-    raw = torch.empty((len(dy), h, w), dtype=dtype)
-    for f, (a, b) in enumerate(zip(dy, dx)):
-        v = base[pad - a: pad - a + h, pad - b: pad - b + w] + 2 * torch.randn(h, w, generator=g)
-        raw[f] = (v * 8 - 100).round().clamp(-32768, 32767).to(dtype) if dtype == torch.int16 else \
-            v.round().clamp(0, 255).to(dtype)
-    return raw
-
-
 @pytest.fixture(scope="module")
 def raw_movies(dev):
     dy, dx = _DRIFTS[4]
     out = {}
     for dtype in (torch.uint8, torch.int16):
-        out[dtype] = [_raw_movie(dy, dx, 256, 4096, dtype, seed=500 + i).to(dev) for i in range(3)]
+        out[dtype] = [drifting_raw_movie(dy, dx, 256, 4096, dtype, seed=500 + i).to(dev) for i in range(3)]
     gain = (1.0 + 0.1 * torch.randn(256, 4096, generator=torch.Generator().manual_seed(9))).clamp(0.5, 1.5)
     return out, gain.to(dev)
 
@@ -263,11 +246,6 @@ def test_raw_pipeline_equals_one_call_per_movie(mc, dev, raw_movies, ps, grid, d
         assert torch.equal(r.total, s), i
 
 
-def _rel_err(a, b):
-    a, b = a.detach().cpu().double(), b.detach().cpu().double()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
-
-
 @pytest.mark.parametrize("dtype", [torch.uint8, torch.int16])
 def test_raw_route_equals_conditioning_then_the_fp32_route(mc, dev, raw_movies, dtype):
     """At ps = 0.83 motion_correct_raw (the fused raw warp, and with a dose the rigid shift route of
@@ -286,7 +264,7 @@ def test_raw_route_equals_conditioning_then_the_fp32_route(mc, dev, raw_movies, 
     fa = mc.estimate_global_motion(img, ps)
     sa, fra = mc.motion_correct_sum(img, fa, ps, return_frames=True)
     assert torch.equal(f, fa)
-    assert _rel_err(fr, fra) <= 1e-5 and _rel_err(s, sa) <= 1e-5
+    assert rel_err(fr, fra) <= 1e-5 and rel_err(s, sa) <= 1e-5
     sh = engine.frame_lattices(fa, t, "catmull_rom")[:, :, 0, 0].cpu().numpy() / np.float32(ps)
     p_y, p_x = np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32)
     for i in range(t):
@@ -298,7 +276,7 @@ def test_raw_route_equals_conditioning_then_the_fp32_route(mc, dev, raw_movies, 
     f_d, dw = mc.motion_correct_raw(m, gd, ps, **dose)
     dw_c = mc.motion_correct_sum(img, fa, ps, **dose)
     assert torch.equal(f_d, f)
-    assert _rel_err(dw, dw_c) <= 2e-5, _rel_err(dw, dw_c)
+    assert rel_err(dw, dw_c) <= 2e-5, rel_err(dw, dw_c)
     piped = mc.RawMoviePipeline(gd, dev, ps, return_frames=True).run([m])[0]
     torch.cuda.synchronize()
-    assert _rel_err(dw, mc.dose_weighted_sum(piped.frames, ps, **dose)) <= 2e-5
+    assert rel_err(dw, mc.dose_weighted_sum(piped.frames, ps, **dose)) <= 2e-5

@@ -70,64 +70,13 @@ import torch
 
 import xc_reference as xr
 from global_refine_reference import planted_movie
+from kernel_harness import calls, switches  # noqa: F401
 from rigid_reference import condition_float64, conditioning_error
 
 pytestmark = pytest.mark.gpu
 
 U = xr.U
 STORE_F16, STORE_F32 = 2, 3
-
-
-class _Recorder:
-    """The loaded library with the names (and arguments) of the entry points that are called written down."""
-
-    def __init__(self, lib):
-        self._lib, self.names, self.args = lib, [], {}
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-
-        def call(*a):
-            self.names.append(name)
-            self.args.setdefault(name, []).append(a)
-            return fn(*a)
-
-        return call
-
-    def count(self, name):
-        return self.names.count(name)
-
-    def clear(self):
-        del self.names[:]
-        self.args.clear()
-
-    def ran(self, *want, absent=()):
-        for name in want:
-            assert self.count(name) >= 1, f"{name} did not run ({sorted(set(self.names))})"
-        for name in absent:
-            assert self.count(name) == 0, f"{name} ran ({sorted(set(self.names))})"
-
-
-@pytest.fixture
-def calls(monkeypatch):
-    from torch_motion_correction_amd import _lib
-
-    rec = _Recorder(_lib.load())
-    monkeypatch.setattr(_lib, "load", lambda: rec)
-    return rec
-
-
-@pytest.fixture
-def switches(monkeypatch):
-    """The engine's test switches at their defaults, restored afterwards; plan's line cache cleared around the test."""
-    from torch_motion_correction_amd import engine, plan
-
-    for name in ("FUSED_SEARCH", "USE_ROW_CHORDS", "WORKSPACE_BYTES"):
-        monkeypatch.setattr(engine, name, getattr(engine, name))
-    monkeypatch.setattr(plan, "USE_DIRECT_LINES", plan.USE_DIRECT_LINES)
-    plan._LINES.clear()
-    yield engine, plan
-    plan._LINES.clear()
 
 
 @contextlib.contextmanager
