@@ -631,6 +631,35 @@ int mc_raw_pixel_sums(const void* raw, int is_i16, int t, int h, int w, long lon
 int mc_raw_group_frames(const void* raw, int storage, int t, int h, int w, int group, short* out, int* overflow,
                         void* stream);
 
+/* Detector defects filled from the session's defect map (MotionCor2 -DefectFile / -DefectMap, RELION
+ * --defect_file), in a raw movie and in its gain reference.  map: (h, w) bytes, non-zero = defect.  pixels: the n
+ * defect pixels' linear indices y * w + x in row-major (ascending) order; j is a pixel's place in that list.  reach:
+ * 1 .. 16.  donors: (n, 8 * reach) ints, counts: n ints.  h * w must fit an int.
+ *
+ * mc_defect_donors writes the tables: with the ring at Chebyshev distance r around a defect = the pixels of
+ * max(|dy|, |dx|) == r inside the frame, r_j is the smallest r in 1 .. reach whose ring holds a good pixel;
+ * donors[j][0 .. counts[j]) are the good pixels of that one ring in row-major order and the rest of the row is -1.
+ * counts[j] == 0: no good pixel within reach (the caller's error to report).
+ *
+ * mc_raw_fill_defects fills a contiguous (t, h, w) movie of elem_bytes = 1, 2 or 4 bytes per element IN PLACE:
+ * movie[f][pixels[j]] = movie[f][donors[j][k]], the element's bits untouched, with the pick (uint32, wrapping)
+ *   x = seed ^ (f * 0x9E3779B1) ^ (j * 0x85EBCA77);
+ *   x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16;   k = ((uint64)x * counts[j]) >> 32.
+ * Donors are good pixels and no good pixel is written: nothing else of the movie changes, and the call has no
+ * races.  A row with counts[j] == 0 is left as it is.
+ *
+ * mc_gain_fill_defects: gain[pixels[j]] = (float)(sum_k (double)gain[donors[j][k]] / counts[j]), the sum in table
+ * order, in place; every other gain stays.
+ *
+ * MC_ERR_ARG for null pointers, sizes < 1, reach outside 1 .. 16, elem_bytes not 1, 2 or 4 and a movie or gain
+ * that is not aligned to its element; n == 0 is MC_OK without a launch (the tables may then be null). */
+int mc_defect_donors(const unsigned char* map, int h, int w, const int* pixels, int n, int reach, int* donors,
+                     int* counts, void* stream);
+int mc_raw_fill_defects(void* movie, int elem_bytes, int t, int h, int w, const int* pixels, const int* donors,
+                        const int* counts, int n, int reach, unsigned seed, void* stream);
+int mc_gain_fill_defects(float* gain, int h, int w, const int* pixels, const int* donors, const int* counts, int n,
+                         int reach, void* stream);
+
 /* ---- estimate_local_motion (estimate_motion_optimizer.py:28-439): loss + gradient ------
  * The reference rebuilds, every iteration and for every patch, rfftn(patch * mask), the
  * Fourier shift by the spline-predicted shifts, the band-pass and B-factor filters, the

@@ -14,12 +14,26 @@ pixels / pixel mean``, and a list of dead, hot and stuck pixels from the same st
 
 The finalisation is a handful of (h, w) torch operations once per session, on the device the statistics live on.
 All rules are integer or single float64 operations, so tests/calibration_reference.py restates them bit for bit.
+
+The defect map is then used to REPAIR the movies (MotionCor2 -DefectFile / -DefectMap, RELION --defect_file), as a
+raw movie -> raw movie stage in front of any raw route and a matching gain -> gain step:
+
+  DefectFill                  the plan of a defect map: the defect list and each defect's donor pixels
+  fill_defects_raw            every defect of every frame replaced by one of its donors, chosen by a hash of (seed,
+                              frame, defect): an exact element of the movie's own type with the movie's own noise
+  fill_defects_gain           the defects' gains replaced by the mean gain of their donors
+  defect_map_from_rectangles  MotionCor2 defect-file entries (x, y, width, height) -> a bool map, on the host
+
+csrc/defect_fill.hip holds the kernels, tests/defect_reference.py restates the rule with Python integers.
 """
 
 from __future__ import annotations
 
+import operator
+
 import torch
 
+from . import _lib
 from ._lib import check, device_scope, load, ptr, require_gpu, stream_ptr
 
 RAW_DTYPES = (torch.uint8, torch.int16)
@@ -27,6 +41,8 @@ RAW_DTYPES = (torch.uint8, torch.int16)
 # 2^63 - 1 beyond these frame counts.  add() and merge() refuse the frames that would exceed them.
 MAX_FRAMES = {torch.uint8: (2**63 - 1) // 255**2, torch.int16: (2**63 - 1) // 2**30}
 EXACT_F64 = 2**53  # integers below it convert to float64 exactly
+FILL_DTYPES = (torch.uint8, torch.int16, torch.float16, torch.float32)  # 1, 2, 2 and 4 bytes: the fill copies bits
+MAX_REACH = 16
 
 
 class RawStatistics:
@@ -207,3 +223,182 @@ def estimate_gain_reference(stats_or_movies, defect_map=None, return_defect_map=
     num = torch.full(stats.shape, float(total), dtype=torch.float64, device=s.device)
     gain = torch.where(good, (num / (float(c) * sg.double())).float(), torch.zeros((), device=s.device))
     return (gain, defect) if return_defect_map else gain
+
+
+# ------------------------------------------------------------------ defects filled from the map
+
+
+def _check_defect_map(defect_map, what="defect_map"):
+    if (not isinstance(defect_map, torch.Tensor) or defect_map.dtype != torch.bool or defect_map.dim() != 2
+            or defect_map.numel() < 1):
+        raise ValueError(f"{what} must be a bool (h, w) tensor, got "
+                         f"{getattr(defect_map, 'dtype', type(defect_map).__name__)} "
+                         f"{tuple(getattr(defect_map, 'shape', ()))}")
+    if defect_map.numel() >= 2**31:
+        raise ValueError(f"{what}: frames of 2^31 pixels and more are not supported")
+
+
+def _check_reach(reach):
+    if isinstance(reach, bool) or not isinstance(reach, int) or not 1 <= reach <= MAX_REACH:
+        raise ValueError(f"reach must be an int in 1..{MAX_REACH}, got {reach!r}")
+    return reach
+
+
+class DefectFill:
+    """The fill plan of a bool (h, w) ``defect_map``.  With the defects listed in row-major order (``j`` a defect's
+    place in the list) and the ring at Chebyshev distance r around a defect = the pixels with max(|dy|, |dx|) == r
+    inside the frame, defect j's donors are the good pixels of the FIRST ring r = 1 .. ``reach`` that holds any, in
+    row-major order (at most 8 r of them).
+
+      pixels (n,)             the defects' linear indices y * w + x, int32, ascending
+      donors (n, 8 * reach)   the donors' linear indices, int32, unused entries -1
+      counts (n,)             the number of donors, int32
+      shape, reach, n, device
+
+    The tables live on ``device`` (None: the map's device, the current GPU for a CPU map); mc_defect_donors
+    (csrc/defect_fill.hip) writes them, one thread per defect.  A defect without a good pixel within ``reach`` is a
+    ValueError naming the first such pixel as (y, x) and the reach -- from one device-to-host read of
+    ``counts.min()``, here, before any movie is touched.  A map without defects is valid and fills nothing."""
+
+    def __init__(self, defect_map, reach=4, device=None):
+        _check_defect_map(defect_map)
+        self.reach = _check_reach(reach)
+        h, w = (int(s) for s in defect_map.shape)
+        self.shape = (h, w)
+        dev = require_gpu(device if device is not None else defect_map.device)
+        with device_scope(dev):
+            dmap = defect_map.detach().to(dev).contiguous()
+            # torch.nonzero lists the indices in row-major order
+            self.pixels = torch.nonzero(dmap.reshape(-1)).reshape(-1).to(torch.int32)
+            n = int(self.pixels.numel())
+            self.donors = torch.empty((n, 8 * self.reach), dtype=torch.int32, device=dev)
+            self.counts = torch.empty((n,), dtype=torch.int32, device=dev)
+            if n:
+                check(_lib.load().mc_defect_donors(ptr(dmap.view(torch.uint8)), h, w, ptr(self.pixels), n,
+                                                   self.reach, ptr(self.donors), ptr(self.counts), stream_ptr(dev)),
+                      "mc_defect_donors")
+                if int(self.counts.min()) == 0:
+                    p = int(self.pixels[int(torch.nonzero(self.counts == 0)[0])])
+                    raise ValueError(f"defect pixel (y, x) = ({p // w}, {p % w}) has no good pixel within "
+                                     f"reach={self.reach}: raise reach or mask the region another way")
+        self.n, self.device = n, dev
+
+
+def _check_fill(fill, frame_shape, what):
+    """The argument rules of `fill` (a DefectFill or a bool map) against an (h, w) of a movie or a gain."""
+    if isinstance(fill, DefectFill):
+        shape = fill.shape
+    else:
+        _check_defect_map(fill, "fill (a DefectFill or a defect map)")
+        shape = tuple(int(s) for s in fill.shape)
+    if shape != tuple(int(s) for s in frame_shape):
+        raise ValueError(f"the defect map has shape {shape}, the {what} {tuple(frame_shape)}")
+
+
+def _fill_plan(fill, data, device):
+    """-> the DefectFill of `fill` for `data` (a movie or a gain).  A plan decides the device; a map's plan is built
+    on `device`, else on the data's device."""
+    if isinstance(fill, DefectFill):
+        if device is not None and require_gpu(device) != fill.device:
+            raise ValueError(f"the DefectFill lives on {fill.device}, {torch.device(device)} was asked for")
+        return fill
+    return DefectFill(fill, device=device if device is not None else data.device)
+
+
+def fill_defects_raw(movie, fill, seed=0, in_place=False, device=None):
+    """A (t, h, w) or (h, w) movie of uint8, int16, float16 or float32 with its detector defects filled: for frame f
+    and defect j (``DefectFill``'s list)
+
+      x = seed ^ (f * 0x9E3779B1) ^ (j * 0x85EBCA77)                                  uint32, wrapping
+      x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16
+      out[f, p_j] = movie[f, donors[j, (x * count_j) >> 32]]
+
+    -- a deterministic "random" pick among the nearest good pixels, as MotionCor2 and RELION fill defects.  The value
+    is an exact element of the movie (its bits are copied) with the movie's own noise; a neighbour mean would
+    imprint a low-variance pattern.  Every other element equals ``movie`` bit for bit.  The result has the movie's
+    dtype and shape and is a raw movie for every ``*_raw*`` function, ``condition_movie``, the pipelines and
+    ``RawStatistics``; use it with ``fill_defects_gain`` of the same plan.
+
+    ``fill``: a ``DefectFill``, or a bool (h, w) map from which one is built with the default reach.  ``seed``: an
+    int in 0 .. 2^32 - 1.  ``in_place=True`` needs a contiguous movie that is already on the GPU and returns that
+    tensor; otherwise the movie is copied (the one full pass: the defect list is sparse) and the copy is filled
+    (mc_raw_fill_defects, one thread per frame and defect), and the result comes back on the movie's device.
+    Argument errors are ValueErrors raised before any device is touched."""
+    if not isinstance(movie, torch.Tensor) or movie.dtype not in FILL_DTYPES:
+        raise ValueError("movie must be a uint8, int16, float16 or float32 tensor, got "
+                         f"{getattr(movie, 'dtype', type(movie).__name__)}")
+    if movie.dim() not in (2, 3) or movie.numel() < 1:
+        raise ValueError(f"movie must be (t, h, w) or (h, w) with at least one frame, got {tuple(movie.shape)}")
+    _check_fill(fill, movie.shape[-2:], "movie's frames")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2**32:
+        raise ValueError(f"seed must be an int in 0..2^32-1, got {seed!r}")
+    if in_place and not (movie.is_cuda and movie.is_contiguous()):
+        raise ValueError("in_place=True needs a contiguous movie that is already on the GPU")
+    plan = _fill_plan(fill, movie, movie.device if in_place else device)  # in place: the movie's device
+    dev = plan.device
+    t = 1 if movie.dim() == 2 else int(movie.shape[0])
+    h, w = plan.shape
+    with device_scope(dev):
+        if in_place:
+            out = movie
+        else:
+            out = torch.empty(movie.shape, dtype=movie.dtype, device=dev)
+            out.copy_(movie.detach())
+        if plan.n:
+            check(_lib.load().mc_raw_fill_defects(ptr(out), out.element_size(), t, h, w, ptr(plan.pixels),
+                                                  ptr(plan.donors), ptr(plan.counts), plan.n, plan.reach, seed,
+                                                  stream_ptr(dev)), "mc_raw_fill_defects")
+        return out if in_place else out.to(movie.device)
+
+
+def fill_defects_gain(gain, fill, device=None):
+    """The fp32 (h, w) gain reference for a movie filled by ``fill_defects_raw``: a new tensor with
+
+      gain'[p_j] = float32( sum_k float64(gain[donors[j, k]]) / count_j )     (the sum in table order)
+
+    at the defects and ``gain`` bit for bit elsewhere.  A filled pixel carries a donor's raw value, so it needs a
+    gain of the donors' size: with ``estimate_gain_reference``'s gain (0 at defects, positive on good pixels) every
+    filled pixel gets a positive one.  ``fill`` as in ``fill_defects_raw``; argument errors are ValueErrors raised
+    before any device is touched; the result comes back on the gain's device."""
+    if not isinstance(gain, torch.Tensor) or gain.dtype != torch.float32 or gain.dim() != 2 or gain.numel() < 1:
+        raise ValueError("gain must be a float32 (h, w) tensor, got "
+                         f"{getattr(gain, 'dtype', type(gain).__name__)} {tuple(getattr(gain, 'shape', ()))}")
+    _check_fill(fill, gain.shape, "gain")
+    plan = _fill_plan(fill, gain, device)
+    dev = plan.device
+    h, w = plan.shape
+    with device_scope(dev):
+        out = torch.empty((h, w), dtype=torch.float32, device=dev)
+        out.copy_(gain.detach())
+        if plan.n:
+            check(_lib.load().mc_gain_fill_defects(ptr(out), h, w, ptr(plan.pixels), ptr(plan.donors),
+                                                   ptr(plan.counts), plan.n, plan.reach, stream_ptr(dev)),
+                  "mc_gain_fill_defects")
+        return out.to(gain.device)
+
+
+def defect_map_from_rectangles(shape, rectangles):
+    """bool (h, w) CPU map from MotionCor2 defect-file entries: ``rectangles`` is an iterable of (x, y, width,
+    height) in pixels, x along the rows' direction (columns x .. x + width - 1, rows y .. y + height - 1 are
+    defects).  ``shape`` is the frame size (h, w).  ValueError for an entry that is not four integers, for an empty
+    rectangle (width or height < 1) and for one that leaves the frame.  Host only."""
+    try:
+        h, w = (operator.index(s) for s in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"shape must be the frame size (h, w), got {shape!r}") from None
+    if h < 1 or w < 1:
+        raise ValueError(f"shape must be the frame size (h, w), got {shape!r}")
+    out = torch.zeros((h, w), dtype=torch.bool)
+    for i, rect in enumerate(rectangles):
+        try:
+            if any(isinstance(v, bool) for v in rect):
+                raise TypeError
+            x, y, rw, rh = (operator.index(v) for v in rect)
+        except (TypeError, ValueError):
+            raise ValueError(f"rectangle {i} must be four integers (x, y, width, height), got {rect!r}") from None
+        if rw < 1 or rh < 1:
+            raise ValueError(f"rectangle {i} is empty: (x, y, width, height) = {(x, y, rw, rh)}")
+        if x < 0 or y < 0 or x + rw > w or y + rh > h:
+            raise ValueError(f"rectangle {i} leaves the {(h, w)} frame: (x, y, width, height) = {(x, y, rw, rh)}")
+        out[y:y + rh, x:x + rw] = True
+    return out
