@@ -660,6 +660,26 @@ int mc_raw_fill_defects(void* movie, int elem_bytes, int t, int h, int w, const 
 int mc_gain_fill_defects(float* gain, int h, int w, const int* pixels, const int* donors, const int* counts, int n,
                          int reach, void* stream);
 
+/* EER event movies (Falcon 4 / 4i) rendered into a raw u8 movie: out (n_frames / group, up h, up w) bytes, frame k =
+ * the per-pixel event count of the input frames k group .. k group + group - 1 (the trailing n_frames % group frames
+ * are decoded and checked but fill no output frame).  data: the device buffer that holds the strips, data_bytes long;
+ * offsets / nbytes: HOST arrays of n_frames entries, frame f's strip is data[offsets[f] .. offsets[f] + nbytes[f]).
+ * The codec rule (7-bit runs, 4-bit sub-pixel codes; csrc/eer.h) places an event of the h x w detector at (y, x) for
+ * upsampling 1 and at (2 y + ((s >> 3) & 1), 2 x + ((s >> 1) & 1)) for upsampling 2.  A count is at most group <= 255:
+ * nothing saturates.  final_n, events: n_frames ints each (device): the pixel count n at which frame f's decoding
+ * stopped (== h * w for a well-formed stream, anything else is the caller's error to report) and its events.
+ * seg_bytes: the segment size of the parallel parse, 64, 128 or 256.  scratch (device, 8-byte aligned) must hold
+ *   scratch_bytes >= 24 * n_frames + 52 * sum_f ceil(nbytes[f] / seg_bytes).
+ * No kernel reads a byte outside a frame's own strip, whatever the bits say.  The call zeroes out on the stream,
+ * copies the frame table to the device (it returns after that copy) and launches three kernels.
+ * Before anything is launched: MC_ERR_ARG for null pointers, sizes < 1, group < 1, n_frames < group, a strip outside
+ * the buffer, misaligned out / final_n / events / scratch, a scratch that is too small, and an rle_bits or upsampling
+ * that names no format; MC_ERR_UNSUPPORTED for rle_bits 8 (compression 65000), upsampling 4, group > 255, h * w >=
+ * 2^31, a strip of 2^28 bytes or more, 2^31 segments or more, up w % 4 != 0 and any other seg_bytes. */
+int mc_eer_render(const unsigned char* data, long long data_bytes, const long long* offsets, const long long* nbytes,
+                  int n_frames, int h, int w, int rle_bits, int upsampling, int group, int seg_bytes,
+                  unsigned char* out, int* final_n, int* events, void* scratch, long long scratch_bytes, void* stream);
+
 /* ---- estimate_local_motion (estimate_motion_optimizer.py:28-439): loss + gradient ------
  * The reference rebuilds, every iteration and for every patch, rfftn(patch * mask), the
  * Fourier shift by the spline-predicted shifts, the band-pass and B-factor filters, the

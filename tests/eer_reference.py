@@ -1,0 +1,198 @@
+"""Test-side restatement of the EER codec rule (csrc/eer.h) in numpy and Python integers: an encoder, the sequential
+decoder, a renderer, and a minimal writer for the TIFF and BigTIFF containers.  Nothing here is imported by the
+package; scripts/eer_render_time.py reuses the encoder.
+
+The rule.  A frame of a detector with N = h * w pixels is a little-endian bit stream (bit k of the stream is bit
+k & 7 of byte k >> 3).  With bit = 0, n = 0:
+
+    loop:  p = 7 bits at `bit`;  bit += 7;  n += p
+           if n >= N: stop
+           if p == 127: continue
+           s = 4 bits at `bit`;  bit += 4;  event at linear position n with sub-pixel code s;  n += 1
+
+and decoding also stops when the next symbol would begin at or after bit 8 * nbytes; bits beyond the strip read as
+zero.  A well-formed stream stops with n == N."""
+
+import struct
+
+import numpy as np
+
+RUN_MAX = 127
+
+
+def encode_frame(positions, subs, n_pixels):
+    """The stream of one frame: `positions` strictly increasing linear positions < n_pixels, `subs` their 4-bit codes
+    -> bytes.  Before each event, gap // 127 skips and a run of gap % 127; after the last one, the runs that bring n
+    to n_pixels (skips, then the rest if any), which is one run of 0 when the last event sits on the last pixel.
+    Vectorised: symbol lengths -> cumsum -> bit scatter."""
+    pos = np.asarray(positions, dtype=np.int64)
+    sub = np.asarray(subs, dtype=np.int64)
+    assert pos.shape == sub.shape and pos.ndim == 1
+    assert pos.size == 0 or (pos[0] >= 0 and pos[-1] < n_pixels and np.all(np.diff(pos) > 0))
+    prev_end = np.concatenate(([0], pos[:-1] + 1)) if pos.size else pos
+    gap = pos - prev_end
+    skips = gap // RUN_MAX
+    count = skips + 1  # symbols per event: its skips and its run + code
+    last = np.cumsum(count) - 1
+    vals = np.full(int(count.sum()), RUN_MAX, dtype=np.int64)
+    lens = np.full(vals.size, 7, dtype=np.int64)
+    vals[last] = (gap % RUN_MAX) | (sub << 7)
+    lens[last] = 11
+    rest = n_pixels - (int(pos[-1]) + 1 if pos.size else 0)
+    tail = [RUN_MAX] * (rest // RUN_MAX) + ([rest % RUN_MAX] if rest % RUN_MAX or rest == 0 else [])
+    vals = np.concatenate((vals, np.asarray(tail, dtype=np.int64)))
+    lens = np.concatenate((lens, np.full(len(tail), 7, dtype=np.int64)))
+    starts = np.cumsum(lens) - lens
+    bits = np.zeros(int(lens.sum()), dtype=np.uint8)
+    for b in range(11):
+        m = lens > b
+        bits[starts[m] + b] = (vals[m] >> b) & 1
+    return np.packbits(bits, bitorder="little").tobytes()
+
+
+def decode_frame(strip, n_pixels):
+    """The sequential decoder of the rule -> (positions, subs, final n): an int.from_bytes walk.  Positions at and
+    beyond n_pixels never occur: decoding stops first."""
+    v = int.from_bytes(bytes(strip), "little")
+    end = 8 * len(strip)
+    bit = n = 0
+    positions, subs = [], []
+    while bit < end:
+        p = (v >> bit) & 127
+        bit += 7
+        n += p
+        if n >= n_pixels:
+            break
+        if p == RUN_MAX:
+            continue
+        subs.append((v >> bit) & 15)
+        bit += 4
+        positions.append(n)
+        n += 1
+    return positions, subs, n
+
+
+def entry_offsets(strip, n_pixels, segment_bytes):
+    """The offsets, within their segments, of the first symbol of every segment after the first (unstopped parse)."""
+    v = int.from_bytes(bytes(strip), "little")
+    end = 8 * len(strip)
+    bit, seen, seg = 0, set(), 0
+    while bit < end:
+        if bit // (8 * segment_bytes) != seg:
+            seg = bit // (8 * segment_bytes)
+            seen.add(bit - seg * 8 * segment_bytes)
+        p = (v >> bit) & 127
+        bit += 7 if p == RUN_MAX else 11
+    return seen
+
+
+def render(strips, shape, group, upsampling=1):
+    """(t_out, up h, up w) uint8 from the frames' strips (np.add.at), the (n_frames,) final n and event counts."""
+    h, w = shape
+    up = upsampling
+    t_out = len(strips) // group
+    out = np.zeros((t_out, up * h, up * w), dtype=np.int64)
+    final_n, counts = [], []
+    for f, strip in enumerate(strips):
+        positions, subs, n = decode_frame(strip, h * w)
+        final_n.append(n)
+        counts.append(len(positions))
+        if f // group >= t_out:
+            continue
+        pos, s = np.asarray(positions, dtype=np.int64), np.asarray(subs, dtype=np.int64)
+        y, x = pos // w, pos % w
+        if up == 2:
+            y, x = 2 * y + ((s >> 3) & 1), 2 * x + ((s >> 1) & 1)
+        np.add.at(out[f // group], (y, x), 1)
+    assert out.max(initial=0) <= 255
+    return out.astype(np.uint8), np.asarray(final_n, dtype=np.int32), np.asarray(counts, dtype=np.int32)
+
+
+def random_frame(rng, n_pixels, density):
+    """One `random(N) < d` mask, then `integers(0, 16)` codes -> (positions, subs)."""
+    positions = np.nonzero(rng.random(n_pixels) < density)[0]
+    return positions, rng.integers(0, 16, size=positions.size)
+
+
+def lay_out(strips, order, lead=1, gap=3, odd=True):
+    """The strips laid into one buffer in `order`, `gap` bytes of 0xff between them, every strip at an odd offset when
+    `odd` -> (bytes, offsets, nbytes) with offsets / nbytes in frame order."""
+    buf = bytearray(b"\xff" * lead)
+    offsets = [0] * len(strips)
+    for i in order:
+        buf += b"\xff" * gap
+        if odd and len(buf) % 2 == 0:
+            buf += b"\xff"
+        offsets[i] = len(buf)
+        buf += strips[i]
+    buf += b"\xff" * gap
+    return bytes(buf), offsets, [len(s) for s in strips]
+
+
+# ------------------------------------------------------------------ containers
+
+_SIZES = {1: 1, 3: 2, 4: 4, 16: 8}
+_CODES = {1: "B", 3: "H", 4: "I", 16: "Q"}
+
+
+def write_tiff(path, strips, shape, big=False, compression=65001, order=None, overrides=None, byte_order="<"):
+    """A minimal TIFF (magic 42) or BigTIFF (magic 43): one IFD and one strip per frame.  The strips are written in
+    `order` (default: reversed), each at an odd offset, each followed by the IFD of the same frame, so that IFD
+    bytes lie between strips and the IFD chain jumps back and forth.  `overrides[frame][tag]` = (type, count, value)
+    replaces or adds an entry, None drops it.  Returns (offsets, nbytes) in frame order."""
+    h, w = shape
+    n = len(strips)
+    order = list(reversed(range(n))) if order is None else list(order)
+    overrides = overrides or {}
+    off_type = 16 if big else 4
+    fsz = 8 if big else 4  # the value field
+
+    def entries(i, strip_offset):
+        e = {256: (4, 1, w), 257: (4, 1, h), 259: (3, 1, compression), 273: (off_type, 1, strip_offset),
+             279: (4, 1, len(strips[i]))}
+        for tag, val in overrides.get(i, {}).items():
+            if val is None:
+                e.pop(tag, None)
+            else:
+                e[tag] = val
+        return sorted(e.items())
+
+    def ifd_size(i):
+        k = len(entries(i, 0))
+        return (8 + 20 * k + 8) if big else (2 + 12 * k + 4)
+
+    at = 16 if big else 8
+    strip_at, ifd_at = [0] * n, [0] * n
+    for i in order:
+        at += 1 - at % 2  # an odd offset
+        strip_at[i] = at
+        at += len(strips[i])
+        at += at % 2  # IFDs on word boundaries
+        ifd_at[i] = at
+        at += ifd_size(i)
+    out = bytearray(b"\xee" * at)
+    bo = byte_order
+    out[:2] = b"II" if bo == "<" else b"MM"
+    if big:
+        struct.pack_into(bo + "HHHQ", out, 2, 43, 8, 0, ifd_at[0] if n else 0)
+    else:
+        struct.pack_into(bo + "HI", out, 2, 42, ifd_at[0] if n else 0)
+    for i in range(n):
+        out[strip_at[i]:strip_at[i] + len(strips[i])] = strips[i]
+        ents = entries(i, strip_at[i])
+        p = ifd_at[i]
+        struct.pack_into(bo + ("Q" if big else "H"), out, p, len(ents))
+        p += 8 if big else 2
+        for tag, (typ, count, value) in ents:
+            struct.pack_into(bo + "HH" + ("Q" if big else "I"), out, p, tag, typ, count)
+            field = bytearray(fsz)
+            if typ in _SIZES and _SIZES[typ] * count <= fsz and count == 1:
+                struct.pack_into(bo + _CODES[typ], field, 0, value)
+            else:  # an offset to the values (never followed by the reader under test)
+                struct.pack_into(bo + ("Q" if big else "I"), field, 0, value)
+            out[p + 4 + fsz:p + 4 + 2 * fsz] = field
+            p += 4 + 2 * fsz
+        struct.pack_into(bo + ("Q" if big else "I"), out, p, ifd_at[i + 1] if i + 1 < n else 0)
+    with open(path, "wb") as fh:
+        fh.write(out)
+    return strip_at, [len(s) for s in strips]
