@@ -197,7 +197,7 @@ def transform_cost(h, w, layout):
       row_major  csrc/full_fft.hip, full_sums.hip: rows as a packed complex line of w / 2 points plus the pack / unpack
                  butterfly (one more level, eta), columns of h points; powers of two cost log2 levels
                  (Higham), the K3 lengths their smooth_radix_list.
-      pruned     xc_rows_fwd.hip, xc_cols.hip / xcg_*.hip: the same for native power-of-two lines; otherwise plan.line_plan's
+      pruned     xc_rows_fwd*.hip, xc_cols.hip / xcg_*.hip: the same for native power-of-two lines; otherwise plan.line_plan's
                  line of row_line_length(w) points (packed for even w, unpacked for odd w) and of h points,
                  forward with the output pruning the engine asks for.
       polyphase  polyphase.hip: the pruned engine on (h, w / 2) and one radix-2 butterfly each way.

@@ -361,6 +361,192 @@ def test_field_warp_entry_points_reject_in_a_fixed_order():
         assert warp_raw(7, entry=acc) == -1 and warp_raw(7, entry=acc, out_sum=OUT) == -2
 
 
+def test_rows_forward_entry_points_reject_in_a_fixed_order():
+    """The return code of every early return that the entry points of K1 (forward row pass of the cross-correlation
+    estimate, xc_rows_fwd.hip) reach before their first HIP call, with pointers that are never dereferenced: no
+    case gets as far as a launch.  Inputs that fail two checks at once pin the ORDER: the storage tag comes before
+    the geometry, the geometry before the pointers, the pointers before the shape and alignment rules of the
+    1024-sample engine; mc_xc_provisional_mean_t alone looks at its pointers before the tag.  The route between
+    the wave-per-row and the workgroup-per-row engine shows through a 4096-column geometry whose staging tile
+    does not fit a CU's LDS: the workgroup engine refuses it (MC_ERR_ARG) before any HIP call, so every input that
+    must NOT take the wave engine (a misaligned pointer, a row pitch that is no whole 16-byte unit, per-job
+    exponents, no mask, mc_xc_row_engine(1)) comes back as -1.  The expected codes were taken by running this test
+    against the library as it was when all three engines and the entry points were one source file: it passed
+    there unchanged."""
+    lib = _lib.load()
+    fake = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+    ARG, UNS, OK = -1, -2, 0
+    U8, I16, F16, F32 = 0, 1, 2, 3
+    SRC, OFF, EXA, EXB, MASK, MR, T1, T1B, TW, GAIN, SUB = (0x10000 * (i + 1) for i in range(11))
+
+    def geom(W=64, H=64, nkx=9, kyp=5, kyn=4, y0=0, ny=None, x0=0, x1=None, RG=16):
+        return _lib.XcGeom(W=W, H=H, nkx=nkx, kyp=kyp, kyn=kyn, y0=y0, ny=H if ny is None else ny, x0=x0,
+                           x1=W if x1 is None else x1, RG=RG)
+
+    small = geom()
+    patch = geom(W=1024, H=1024, nkx=100, kyp=10, kyn=10, RG=8)  # rows the 1024-sample engine takes
+    # 4096-sample rows the wave engine takes; the workgroup engine's LDS would be 8 (2 * 2177 + 512 * 33) bytes
+    big = geom(W=4096, H=4096, nkx=512, kyp=10, kyn=10, RG=32)
+    assert 8 * (2 * 2177 + 512 * 33) > 160 * 1024
+    # geom_from's own checks, in its order (sizes before counts), shared by every entry that converts a geometry
+    bad_geoms = [(None, ARG), (geom(W=100), UNS), (geom(W=16, nkx=5), UNS), (geom(W=16384), UNS), (geom(H=1), UNS),
+                 (geom(H=8200, RG=8), UNS), (geom(W=100, nkx=0), UNS), (geom(nkx=0), ARG), (geom(nkx=34), ARG),
+                 (geom(kyp=0, kyn=0), ARG), (geom(kyp=60, kyn=5), ARG), (geom(RG=0), ARG), (geom(ny=60), ARG),
+                 (geom(RG=2), ARG), (geom(y0=16), ARG), (geom(y0=-16, ny=16), ARG), (geom(x1=0), ARG),
+                 (geom(x1=66), ARG), (geom(x0=1), ARG), (geom(x1=63), ARG)]
+
+    # ---- mc_xc_rows_lds_bytes
+    assert lib.mc_xc_rows_lds_bytes(small) == 8 * (4 * 2 * 35 + 9 * 17)  # four sub-groups of 32-point lines
+    assert lib.mc_xc_rows_lds_bytes(big) == 8 * (2 * 2177 + 512 * 33)
+    for q, code in bad_geoms:
+        assert lib.mc_xc_rows_lds_bytes(q) == code, q and [getattr(q, n) for n, _ in q._fields_]
+
+    # ---- mc_xc_rows_forward
+    def fwd(src=SRC, off=OFF, stride=None, expo=0, mask=MASK, mr=MR, t1=T1, tw=TW, n=2, q=small):
+        stride = q.W if stride is None and q else stride or 64
+        return lib.mc_xc_rows_forward(fake(src), fake(off), stride, fake(expo), fake(mask), fake(mr), fake(t1), fake(tw),
+                                      n, q, None)
+
+    for q, code in bad_geoms:  # the geometry before the pointers
+        assert fwd(q=q) == code and fwd(q=q, src=0, off=0, t1=0, tw=0, n=0) == code
+    for null in ("src", "off", "t1", "tw", "n"):
+        assert fwd(**{null: 0}) == ARG and fwd(q=big, **{null: 0}) == ARG, null
+    assert fwd(n=-1) == ARG
+    # the route: none of these may take the wave engine
+    for wg in (dict(src=SRC + 4), dict(src=SRC + 8), dict(mask=MASK + 4), dict(mask=MASK + 8), dict(mask=0),
+               dict(expo=EXA), dict(stride=4098), dict(stride=4097), dict(mr=0, mask=0)):
+        assert fwd(q=big, **wg) == ARG, wg
+    for q in (geom(W=4096, H=4096, nkx=600, kyp=10, kyn=10, RG=32),                 # more than 512 kept bins
+              geom(W=4096, H=4096, nkx=512, kyp=10, kyn=10, ny=4092, RG=44),        # no whole rounds of 8 rows
+              geom(W=2048, H=4096, nkx=512, kyp=10, kyn=10, RG=64),
+              geom(W=8192, H=4096, nkx=512, kyp=10, kyn=10, RG=32)):
+        assert fwd(q=q) == ARG, [getattr(q, n) for n, _ in q._fields_]
+
+    # ---- mc_xc_row_engine
+    assert lib.mc_xc_row_engine(-1) == ARG and lib.mc_xc_row_engine(2) == ARG
+    try:
+        assert lib.mc_xc_row_engine(1) == OK
+        assert lib.mc_xc_row_engine(7) == ARG  # ... and the mode stays 1:
+        assert fwd(q=big) == ARG               # rows the wave engine would take go to the workgroup engine
+    finally:
+        assert lib.mc_xc_row_engine(0) == OK
+
+    # ---- mc_xc_rows_forward_raw
+    def fwd_raw(storage, raw=SRC, gain=GAIN, off=OFF, stride=None, mask=MASK, sub=SUB, mr=MR, t1=T1, tw=TW, n=2, q=small):
+        stride = q.W if stride is None and q else stride or 64
+        return lib.mc_xc_rows_forward_raw(fake(raw), storage, fake(gain), fake(off), stride, fake(mask), fake(sub),
+                                          fake(mr), fake(t1), fake(tw), n, q, None, None)
+
+    raw_nulls = ("raw", "gain", "off", "mask", "sub", "mr", "t1", "tw", "n")
+    for tag in (F16, F32, 7, -1):  # a bad storage tag wins over everything
+        assert fwd_raw(tag) == UNS and fwd_raw(tag, q=None) == UNS and fwd_raw(tag, q=geom(nkx=0), raw=0, n=0) == UNS
+    for storage in (U8, I16):
+        for q, code in bad_geoms:
+            assert fwd_raw(storage, q=q) == code and fwd_raw(storage, q=q, raw=0, gain=0, n=0) == code
+        for null in raw_nulls:
+            assert fwd_raw(storage, **{null: 0}) == ARG and fwd_raw(storage, q=big, **{null: 0}) == ARG, null
+        # the route: 16-byte raw, gain and mask and a pitch of whole 8-sample units, or the workgroup engine
+        for wg in (dict(raw=SRC + 8), dict(raw=SRC + 1), dict(gain=GAIN + 8), dict(gain=GAIN + 4), dict(mask=MASK + 8),
+                   dict(stride=4100), dict(stride=4098)):
+            assert fwd_raw(storage, q=big, **wg) == ARG, (storage, wg)
+        assert fwd_raw(storage, q=geom(W=8192, H=4096, nkx=512, kyp=10, kyn=10, RG=32)) == ARG
+
+    # ---- mc_xc_rows_forward_dual_t
+    def dual(storage, src=SRC, off=OFF, stride=1024, exa=EXA, exb=EXB, mask=MASK, mr=MR, t1a=T1, t1b=T1B, tw=TW, n=2,
+             q=patch):
+        return lib.mc_xc_rows_forward_dual_t(fake(src), storage, fake(off), stride, fake(exa), fake(exb), fake(mask),
+                                             fake(mr), fake(t1a), fake(t1b), fake(tw), n, q, None, None)
+
+    not_patch_rows = [small, big, geom(W=512, H=1024, nkx=100, kyp=10, kyn=10, RG=8),
+                      geom(W=2048, H=1024, nkx=100, kyp=10, kyn=10, RG=8),
+                      geom(W=1024, H=1024, nkx=129, kyp=10, kyn=10, RG=8),
+                      geom(W=1024, H=1024, nkx=100, kyp=10, kyn=10, ny=1020, RG=4)]
+    dual_nulls = ("src", "off", "exa", "mask", "t1a", "tw", "n")
+    for tag in (U8, I16, 7, -1):
+        assert dual(tag) == UNS and dual(tag, q=None) == UNS and dual(tag, q=geom(nkx=0), src=0, n=0) == UNS
+    for storage in (F16, F32):
+        for q, code in bad_geoms:
+            assert dual(storage, q=q) == code and dual(storage, q=q, src=0, mask=0, n=0) == code
+        for null in dual_nulls:
+            assert dual(storage, **{null: 0}) == ARG, null
+            for q in not_patch_rows:  # a null pointer wins over a shape the engine does not take
+                assert dual(storage, q=q, **{null: 0}) == ARG, null
+            assert dual(storage, mask=MASK + 4, **({null: 0} if null != "mask" else {"src": 0})) == ARG
+        assert dual(storage, t1b=0) == ARG and dual(storage, t1b=0, q=small) == ARG  # a second exponent without its T1
+        assert dual(storage, n=-3) == ARG
+        for q in not_patch_rows:
+            assert dual(storage, q=q) == UNS and dual(storage, q=q, exb=0, t1b=0) == UNS
+        assert dual(storage, mask=MASK + 4) == UNS and dual(storage, mask=MASK + 12) == UNS
+
+    # ---- mc_xc_rows_forward_dual_raw
+    def dual_raw(storage, raw=SRC, gain=GAIN, area=1 << 20, off=OFF, stride=1024, exa=EXA, exb=EXB, mask=MASK, sub=SUB,
+                 mr=MR, t1a=T1, t1b=T1B, tw=TW, n=2, q=patch):
+        return lib.mc_xc_rows_forward_dual_raw(fake(raw), storage, fake(gain), area, fake(off), stride, fake(exa),
+                                               fake(exb), fake(mask), fake(sub), fake(mr), fake(t1a), fake(t1b),
+                                               fake(tw), n, q, None, None)
+
+    dual_raw_bad = [dict(raw=0), dict(gain=0), dict(off=0), dict(exa=0), dict(mask=0), dict(sub=0), dict(mr=0),
+                    dict(t1a=0), dict(tw=0), dict(n=0), dict(t1b=0), dict(area=0), dict(stride=0), dict(stride=-1024)]
+    for tag in (F16, F32, 7, -1):
+        assert dual_raw(tag) == UNS and dual_raw(tag, q=None) == UNS and dual_raw(tag, q=geom(nkx=0), raw=0) == UNS
+    for storage in (U8, I16):
+        for q, code in bad_geoms:
+            assert dual_raw(storage, q=q) == code and dual_raw(storage, q=q, raw=0, gain=0, area=0) == code
+        for bad in dual_raw_bad:
+            assert dual_raw(storage, **bad) == ARG, bad
+            for q in not_patch_rows:
+                assert dual_raw(storage, q=q, **bad) == ARG, bad
+            if "gain" not in bad:  # ... and over the raw entry's own alignment rules
+                assert dual_raw(storage, **{"gain": GAIN + 2, **bad}) == ARG, bad
+        for q in not_patch_rows:
+            assert dual_raw(storage, q=q) == UNS and dual_raw(storage, q=q, exb=0, t1b=0) == UNS
+        assert dual_raw(storage, mask=MASK + 4) == UNS
+        assert dual_raw(storage, gain=GAIN + 2) == UNS and dual_raw(storage, gain=GAIN + 1) == UNS
+    assert dual_raw(I16, raw=SRC + 1) == UNS and dual_raw(I16, raw=SRC + 1, tw=0) == ARG  # (u8 rows may start anywhere)
+
+    # ---- mc_xc_rows_forward_stats_t: the storage tag, the pointers it reads itself, then the box (it clears the
+    # accumulators before it looks at anything else)
+    def stats(storage, m0=MR, acc=SUB, fix=GAIN, out3=T1B, q=small, hl=16, hu=48, wl=16, wu=48):
+        return lib.mc_xc_rows_forward_stats_t(fake(SRC), storage, fake(OFF), 64, fake(MASK), fake(m0), fake(T1), fake(TW),
+                                              2, q, hl, hu, wl, wu, fake(acc), fake(fix), fake(out3), None, None)
+
+    windowed = geom(y0=16, ny=32, x0=16, x1=48)
+    boxes = [dict(hl=0), dict(hu=64), dict(wl=0), dict(wl=14), dict(wu=64), dict(wu=50), dict(wl=17), dict(wu=47),
+             dict(hl=48), dict(hl=40, hu=32), dict(wl=48), dict(wl=40, wu=32)]
+    for tag in (U8, I16, 7, -1):
+        assert stats(tag) == UNS and stats(tag, m0=0, acc=0, q=None) == UNS and stats(tag, q=windowed, hl=0) == UNS
+    for storage in (F16, F32):
+        for null in ("m0", "acc", "fix", "out3"):
+            assert stats(storage, **{null: 0}) == ARG and stats(storage, q=windowed, hl=0, **{null: 0}) == ARG, null
+        assert stats(storage, q=None) == ARG
+        for box in boxes:  # the box must lie inside the region K1 reads, on even columns, and hold something
+            assert stats(storage, q=windowed, **box) == ARG, box
+        assert stats(storage, q=geom(W=100, y0=16, ny=32, x0=16, x1=48), hl=0) == ARG  # the box before the geometry
+
+    # ---- mc_xc_provisional_mean_t: the pointers and the count before the tag
+    def pmean(storage, x=SRC, n=16, m0=MR):
+        return lib.mc_xc_provisional_mean_t(fake(x), storage, n, fake(m0), None)
+
+    for tag in (U8, I16, 7, -1):
+        assert pmean(tag) == UNS
+        assert pmean(tag, x=0) == ARG and pmean(tag, m0=0) == ARG and pmean(tag, n=0) == ARG and pmean(tag, n=-1) == ARG
+    for storage in (F16, F32):
+        assert pmean(storage, x=0) == ARG and pmean(storage, m0=0) == ARG and pmean(storage, n=0) == ARG
+
+    # ---- mc_xc_rows_hot_correct
+    def hot(keys=SRC, rv=OFF, n=0, frame0=0, njobs=2, h=64, w=64, mask=MASK, mr=MR, t1=T1, q=small):
+        return lib.mc_xc_rows_hot_correct(fake(keys), fake(rv), n, frame0, njobs, h, w, fake(mask), fake(mr), fake(t1), q,
+                                          None)
+
+    assert hot() == OK and hot(mask=0) == OK  # an empty list is no work, and no error; the mask is optional
+    for bad in (dict(keys=0), dict(rv=0), dict(mr=0), dict(t1=0), dict(q=None), dict(n=-1), dict(frame0=-1),
+                dict(njobs=0), dict(h=0), dict(w=0), dict(w=128), dict(q=geom(W=128)), dict(q=geom(nkx=0)),
+                dict(q=geom(ny=0)), dict(q=geom(y0=-16)), dict(q=geom(y0=16)), dict(h=32), dict(n=1 << 31)):
+        assert hot(**bad) == ARG, bad  # ... but every argument is checked before the list is found empty
+        if "n" not in bad:
+            assert hot(n=5, **bad) == ARG, bad
+
+
 def test_full_spectrum_and_generic_length_entry_points_reject_in_a_fixed_order():
     """The return code of every early return of the row-major full-spectrum entry points (full_fft.hip,
     full_sums.hip), of mc_xcg_rows_forward_raw and of the geometry and line checks of the generic-length engine

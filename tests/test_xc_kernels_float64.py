@@ -432,6 +432,30 @@ def test_patch_jobs_dual_wave_kernel(dev, calls, switches, half):
         print(f"RATIO patch jobs 1024 dual wave kernel {'fp16' if half else 'fp32'} {tag}: L2 {r[0]:.3f} bin {r[1]:.3f}")
 
 
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
+def test_patch_jobs_single_wave_kernel(dev, calls, switches, half):
+    """The same 1024-px jobs with ONE exponent per job (the middle-frame strategy's call of
+    mc_xc_rows_forward_dual_t: no second exponent list, no second T1), fp32 and fp16: the single-spectrum form of
+    the wave-per-patch-row kernel, against the bounds of the dual form's first spectrum."""
+    engine, plan = switches
+    p = 1024
+    pa = xr.args(p, p)
+    x, off, W = _patch_input(p, dev, half)
+    ea = [1, 2, 3, 1]
+    mean, std = xr.box_stats64(x)
+    pl = _plan(pa, dev)
+    calls.clear()
+    S = engine._forward_spectra(x.to(dev), off, W, torch.tensor(ea, dtype=torch.int32, device=dev), pl,
+                                _stats_tensor(mean, std, dev), min_expo=1)
+    torch.cuda.synchronize()
+    calls.ran("mc_xc_rows_forward_dual_t", "mc_xc_cols_forward", absent=("mc_xc_rows_forward",))
+    a = calls.args["mc_xc_rows_forward_dual_t"]
+    assert len(a) == 1 and a[0][1] == (STORE_F16 if half else STORE_F32) and a[0][5] is None and a[0][9] is None
+    parts = xr.spectra_parts(x, pa, PATCH_JOBS, ea, (mean, std))
+    r = xr.check_spectra(S, parts, [xr.spectra_bounds(pa, mean, std, expo=e) for e in ea], f"single half={half}")
+    print(f"RATIO patch jobs 1024 single wave kernel {'fp16' if half else 'fp32'}: L2 {r[0]:.3f} bin {r[1]:.3f}")
+
+
 @pytest.mark.parametrize("p", [1024, 48, 63, 80])
 def test_patch_jobs_two_ordinary_passes(dev, calls, switches, p):
     """The same jobs where the engine has no fused kernel (no host-known minimum exponent for 1024, any other patch

@@ -20,8 +20,10 @@ LIB_PATH = os.path.join(PKG_DIR, "libmcorr.so")
 # one kernel family each: its 101 kernels took five minutes as one translation unit, 75 s each side by side
 SOURCES = [("xcg_rows_inv.hip", "xcg_rows_inv", []), ("xcg_cols_inv.hip", "xcg_cols_inv", []),
            ("xcg_rows_fwd.hip", "xcg_rows_fwd", []), ("xcg_cols_fwd.hip", "xcg_cols_fwd", []),
-           # the power-of-two engine, one object per pass family (K1 / K2-K3 / K4-K6)
-           ("xc_rows_fwd.hip", "xc_rows_fwd", []),
+           # the power-of-two engine, one object per pass family (K2-K3 / K4-K6); K1 is four objects over xc_rows_fwd.h:
+           # the workgroup and the wave engine here (12 s and 11 s), the patch-row engine and the entry points (3 s and
+           # 2 s) further down
+           ("xc_rows_fwd_wg.hip", "xc_rows_fwd_wg", []), ("xc_rows_fwd_wave.hip", "xc_rows_fwd_wave", []),
            # row-major full spectra over full_common.h: per-frame transforms / fused sums and the raw row pass
            ("full_fft.hip", "full_fft", []), ("full_sums.hip", "full_sums", []), ("fourier_crop.hip", "fourier_crop", []),
            ("xc_cols.hip", "xc_cols", []), ("xc_search.hip", "xc_search", []),
@@ -36,6 +38,7 @@ SOURCES = [("xcg_rows_inv.hip", "xcg_rows_inv", []), ("xcg_cols_inv.hip", "xcg_c
            ("field_tables.hip", "field_tables", ["-fno-slp-vectorize"]),
            # conditioning, statistics and hot pixels of raw movies over cond_common.h; the plan's tables
            ("hot_pixels.hip", "hot_pixels", []), ("condition.hip", "condition", []),
+           ("xc_rows_fwd_wave512.hip", "xc_rows_fwd_wave512", []), ("xc_rows_fwd.hip", "xc_rows_fwd", []),
            ("field_post.hip", "field_post", []), ("local_motion.hip", "local_motion", []),
            ("polyphase.hip", "polyphase", []), ("plan_tables.hip", "plan_tables", []), ("xc_refine.hip", "xc_refine", []),
            ("xc_refine_patches.hip", "xc_refine_patches", []), ("raw_accumulate.hip", "raw_accumulate", []),

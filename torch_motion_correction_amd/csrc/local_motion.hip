@@ -4,7 +4,7 @@
 //
 // What does not change between iterations is hoisted out of the loop: the masked, filtered
 // patch spectra  P[b][f][k] = rfft2(patch_b,f * mask)[k] * bandpass[k] * b_envelope[k]  are
-// computed ONCE (the pruned K1/K2 transforms of xc_rows_fwd.hip / xc_cols.hip: only bins inside the band are
+// computed ONCE (the pruned K1/K2 transforms of xc_rows_fwd*.hip / xc_cols.hip: only bins inside the band are
 // kept, everything else is multiplied by zero in the reference).  An iteration is then
 //     G_f[k] = P[b][f][k] exp(-2 pi i (fy[k] sy_f + fx[k] sx_f))         (Fourier shift)
 //     S[k]   = sum_f G_f[k]

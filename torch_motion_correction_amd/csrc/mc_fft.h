@@ -193,7 +193,7 @@ __device__ __forceinline__ void fft_pass2(int lt, const FftTwiddles<N>& T, Load 
 // reads through `load(i, it, m)` (it, m = position of element i in this thread's
 // first-pass registers); the last pass writes through `store(i, v)` when
 // LAST_TO_FUNCTOR, else to LDS.  Returns the index of the line that was read or written
-// last; the next transform of a loop must start at (that ^ 1) -- see xc_rows_fwd.hip.
+// last; the next transform of a loop must start at (that ^ 1) -- see xc_rows_fwd_wg.hip.
 template <int N, int DIR, bool LAST_TO_FUNCTOR, int PASS, typename Load, typename Store>
 __device__ __forceinline__ int fft_pp_rec(cfloat* l0, cfloat* l1, int s, int lt,
                                           const FftTwiddles<N>& T, Load load, Store store) {

@@ -1,5 +1,5 @@
 // Types and host helpers shared by the pruned, separable 2-D real FFT engines of the cross-correlation shift
-// search (reference: estimate_motion_xc.py:76-123 for whole frames, :338-355 for patches): xc_rows_fwd.hip,
+// search (reference: estimate_motion_xc.py:76-123 for whole frames, :338-355 for patches): xc_rows_fwd*.hip,
 // xc_cols.hip and xc_search.hip (power-of-two lengths) and xcg_*.hip over xcg_common.h (any other length: mixed radix /
 // chirp-z).
 //
@@ -10,6 +10,8 @@
 //
 //   K1 xc_rows_fwd   rows:  gather + (x-mean)*rstd*mask^e -> real FFT(W) -> first nkx bins
 //                           -> T1[job][kx][ysupport]            (transposed via LDS)      xc_rows_fwd.hip
+//                           (entry points and route rules over xc_rows_fwd.h; one object per engine:
+//                           xc_rows_fwd_wg.hip, xc_rows_fwd_wave.hip, xc_rows_fwd_wave512.hip)
 //   K2 xc_cols_fwd   cols:  T1 column -> FFT(H) -> kept ky rows * filter -> S[job][kx][kyi]   xc_cols.hip
 //   K3 xc_cols_inv   cols:  conj(S_ref)*S_cur -> inverse FFT(H) -> T2[pair][kx][y]            xc_cols.hip
 //   K4 xc_rows_inv   rows:  T2 rows -> inverse real FFT(W) -> fused arg-max | store           xc_search.hip

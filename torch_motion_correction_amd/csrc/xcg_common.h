@@ -1,7 +1,7 @@
 // The generic-length engine: the pruned, separable 2-D real FFT for transform lengths that are not powers of
 // two -- the xcg_* kernels (direct mixed-radix lines for the K3 formats, Bluestein chirp-z for everything else)
 // with the same pruning, layouts (T1, S, T2) and fused prologues / epilogues as the power-of-two engine
-// (xc_rows_fwd.hip, xc_cols.hip, xc_search.hip; map of the passes in xc_common.h).  One source file per kernel
+// (xc_rows_fwd*.hip, xc_cols.hip, xc_search.hip; map of the passes in xc_common.h).  One source file per kernel
 // family, compiled side by side (75 s each instead of five minutes as one translation unit):
 //   xcg_rows_fwd.hip  rows forward (+ from raw bytes) and the peak neighbourhood
 //   xcg_cols_fwd.hip  columns forward

@@ -112,7 +112,8 @@ def _k2(lib, g, dev, T1, filt, S, tw_col, n, st):
 
 
 def _wave_rows_geometry(g):
-    """The geometry of the wave-per-row patch kernels (mc_xc_rows_forward_dual*): rows of 1024 samples."""
+    """The geometry of the wave-per-row patch kernels (mc_xc_rows_forward_dual*): rows of 1024 samples.
+    A shortcut: the authority is wave512_shape (csrc/xc_rows_fwd.hip)."""
     return g.W == 1024 and g.nkx <= 128 and g.ny % 8 == 0
 
 
@@ -264,7 +265,8 @@ def _global_spectra(img, pl, after_k1=None):
     statistics gathered inside K1 whenever the central box lies in the region K1 reads
     (always for near-square frames); otherwise a separate statistics pass.  `after_k1()`, if
     given, is called right after K1 has been enqueued on the fused path (the movie pipeline
-    records an event there); the other path never calls it."""
+    records an event there); the other path never calls it.
+    `half_ok` is a shortcut: the authority on the rows the wave-per-row K1 takes is k1_route (csrc/xc_rows_fwd.hip)."""
     lib = _lib.load()
     t, h, w = img.shape
     dev, g = img.device, pl.geom
