@@ -27,12 +27,13 @@ __device__ __forceinline__ void wf_pin(int& v, float dep) { asm volatile("" : "+
 // engines do): the table of all fifteen was 15 KiB, and with it a workgroup's 51 KB of LDS allowed three
 // workgroups per CU; 40 KB allow four.  The kernel is bound by how many waves are there to issue (49 %
 // VALU, 37 % LDS, 62 % of the HBM ceiling; a wave issues at most one VALU instruction per ~6 cycles,
-// scripts/ubench/pk_rate.hip), so the fourth wave per SIMD is worth more than the 44 extra instructions
-// per row.
+// scripts/ubench/pk_rate.hip), so LDS must never be what keeps a workgroup out of a CU: that is worth more than
+// the 44 extra instructions per row.  What the kernel runs is two waves per SIMD -- its 198-235 VGPRs admit two
+// workgroups of four waves per CU (WF_MIN_WG), whatever the LDS would allow.
 #define WF_TWA (4 * 128)
 #define WF_TWB (4 * 15 * 2)
 constexpr int WF_ROWS_PER_WG = 32;  // rounds of 8 rows: a wave takes rows 2 wv and 2 wv + 1 of every round (16: the prologue is 22 % of a wave's life; 32: K1 445 -> 430 us)
-constexpr int WF_MIN_WG = 2;  // workgroups per CU the register allocation aims at (2: 256 VGPRs per lane, 3: 168)
+constexpr int WF_MIN_WG = 2;  // workgroups per CU the register allocation aims at = waves per SIMD (2: up to 256 VGPRs per lane, none of the 20 variants spills; 3: 168, 416 B of scratch)
 
 // N1LO / N1HI: only the 256-sample chunks [N1LO, N1HI) of a row can touch the mask support,
 // the others are zero and are not loaded.  CLAMP_ALL = false: the chunks strictly between
@@ -163,21 +164,35 @@ __device__ __forceinline__ void wf_row(float4 (&px)[16], float4 (&mk)[16], const
     half_row(std::integral_constant<int, 8>{});
   }
   if (RAW == 0) wf_load_mask<N1LO, N1HI>(mrow, t, mk);
-  auto condition = [&](auto in_box) {
-    constexpr bool INBOX = decltype(in_box)::value;
-    wf2 acc_s = {0.f, 0.f}, acc_q = {0.f, 0.f};
+  if constexpr (STATS && RAW == 0) {
+    // The statistics of a row of the box (wave-uniform) are taken from px under the mask loads' latency, in a
+    // side block of their own: the conditioning below is then the same straight-line code as without STATS.
+    // As one block per kind of row, each with its own copy of the conditioning, the compiler kept both copies'
+    // 64 results apart and the full-width variants went to scratch.  The centred samples are formed twice on
+    // these rows, by the same subtraction, so every sum keeps its bits.
+    if (box_hi > box_lo) {
+      wf2 acc_s = {0.f, 0.f}, acc_q = {0.f, 0.f};
+#pragma unroll
+      for (int n1 = N1LO; n1 < N1HI; ++n1) {
+        const wf2 a01 = (HALF ? wf_unpack_h2(px[n1].x) : wf2{px[n1].x, px[n1].y}) - mean;
+        const wf2 a23 = (HALF ? wf_unpack_h2(px[n1].y) : wf2{px[n1].z, px[n1].w}) - mean;
+        // chunk weight 1 inside the box, 0 outside (scalar): no branch per chunk
+        const float cw = (n1 >= box_lo && n1 < box_hi) ? 1.f : 0.f;
+        const wf2 sa = a01 + a23;
+        const wf2 sq = __builtin_elementwise_fma(a01, a01, a23 * a23);
+        acc_s = __builtin_elementwise_fma(sa, wf2{cw, cw}, acc_s);
+        acc_q = __builtin_elementwise_fma(sq, wf2{cw, cw}, acc_q);
+      }
+      st_s += acc_s.x + acc_s.y;
+      st_q += acc_q.x + acc_q.y;
+    }
+  }
+  if constexpr (RAW == 0) {
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) {
       if (n1 >= N1LO && n1 < N1HI) {
         const wf2 a01 = (HALF ? wf_unpack_h2(px[n1].x) : wf2{px[n1].x, px[n1].y}) - mean;
         const wf2 a23 = (HALF ? wf_unpack_h2(px[n1].y) : wf2{px[n1].z, px[n1].w}) - mean;
-        if (INBOX) {  // chunk weight 1 inside the box, 0 outside (scalar): no branch per chunk
-          const float cw = (n1 >= box_lo && n1 < box_hi) ? 1.f : 0.f;
-          const wf2 sa = a01 + a23;
-          const wf2 sq = __builtin_elementwise_fma(a01, a01, a23 * a23);
-          acc_s = __builtin_elementwise_fma(sa, wf2{cw, cw}, acc_s);
-          acc_q = __builtin_elementwise_fma(sq, wf2{cw, cw}, acc_q);
-        }
         A0[n1] = (a01 * rstd) * wf2{mk[n1].x, mk[n1].y};
         A1[n1] = (a23 * rstd) * wf2{mk[n1].z, mk[n1].w};
       } else {
@@ -185,14 +200,6 @@ __device__ __forceinline__ void wf_row(float4 (&px)[16], float4 (&mk)[16], const
         A1[n1] = wf2{0.f, 0.f};
       }
     }
-    if (INBOX) {
-      st_s += acc_s.x + acc_s.y;
-      st_q += acc_q.x + acc_q.y;
-    }
-  };
-  if constexpr (RAW == 0) {
-    if (STATS && box_hi > box_lo) condition(std::true_type{});  // wave-uniform: a row of the box
-    else condition(std::false_type{});
   }
   int tl = t;  // lane index as the tables see it (re-pinned before each table)
   wf_pin(tl, A0[N1HI - 1].x);
@@ -391,7 +398,10 @@ __global__ __launch_bounds__(256, WF_MIN_WG) void xc_rows_fwd_wave(
         } else {
           const int r8 = r16 + (rr >> 1) * 8;
           // 4 lanes = the 64 bytes of one kx; nkx <= 256 KEEP, so at most 4 KEEP pieces per thread: all the
-          // LDS reads first, then the stores (one LDS latency per round instead of one per piece)
+          // LDS reads first, then the stores (one LDS latency per round instead of one per piece).  The reads are
+          // unconditional (j < 2048: always inside slabs[][]; only the store is guarded): read under `j < 4 nkx`
+          // the 16 values were undefined on the other path and the compiler kept them alive round the whole row
+          // loop -- 16 VGPRs in every variant, and the scratch of the statistics variants at the 256 limit
           typedef float f4 __attribute__((ext_vector_type(4)));
 #pragma unroll
           for (int half = 0; half < KEEP; ++half) {  // four pieces (16 registers) at a time
@@ -399,7 +409,7 @@ __global__ __launch_bounds__(256, WF_MIN_WG) void xc_rows_fwd_wave(
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
               const int j = tj + 256 * (4 * half + it);
-              if (j < 4 * g.nkx) pv[it] = parked[(j & 3) * (WF_SLAB / 2) + (j >> 2)];
+              pv[it] = parked[(j & 3) * (WF_SLAB / 2) + (j >> 2)];
             }
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
