@@ -7,6 +7,7 @@ caller gets an exception.  Nothing here touches the oracle.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 
 import torch
@@ -207,8 +208,6 @@ def normalize_frame_index(reference_frame, t: int) -> int:
     (estimate_motion_xc.py:101, :306): Python semantics, negative values count from the end and
     anything outside [-t, t) raises IndexError.  Returns the wrapped index; no raw user value
     ever reaches a device-side table."""
-    import operator
-
     r = operator.index(reference_frame)
     if not -t <= r < t:
         raise IndexError(f"index {r} is out of bounds for dimension 0 with size {t}")
