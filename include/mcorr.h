@@ -61,12 +61,9 @@ int mc_xc_filter(float* filt, const mc_xc_geom* geom, float low, float high, flo
 #define MC_STORE_F32 3
 
 /* ---- a2: normalize_image statistics (utils.py:49-84) ---------------------------- */
-/* mean and unbiased std of stack[:, hl:hu, wl:wu] over all t frames jointly.
+/* mean and unbiased std of stack[:, hl:hu, wl:wu] over all t frames jointly, the frames in their storage
+ * type (MC_STORE_F32 / MC_STORE_F16: statistics of the fp32 up-cast, read straight from the fp16 bytes).
  * acc: 2 doubles of scratch; out3 = {mean, 1/std, std} as floats. */
-int mc_central_box_stats(const float* stack, int t, int h, int w, int hl, int hu, int wl, int wu,
-                         double* acc, float* out3, void* stream);
-/* The same over frames in their storage type (MC_STORE_F32 / MC_STORE_F16): statistics of the
- * fp32 up-cast, read straight from the fp16 bytes. */
 int mc_central_box_stats_t(const void* stack, int storage, int t, int h, int w, int hl, int hu, int wl,
                            int wu, double* acc, float* out3, void* stream);
 /* dst = (src - mean) * (1/std), n elements (normalize_image's elementwise pass). */
@@ -163,15 +160,10 @@ int mc_dose_accumulate(const void* S, int nframes, int frame0, int total_frames,
  * expo_b != NULL the same samples are transformed twice, with mask^expo_a[j] into T1a and
  * mask^expo_b[j] into T1b -- the U and V spectra of the mean-except-current reference
  * (estimate_motion_xc.py:315-346) from one read of the patch rows.  Layouts as
- * mc_xc_rows_forward. */
-int mc_xc_rows_forward_dual(const float* src, const int64_t* job_off, int64_t row_stride,
-                            const int* expo_a, const int* expo_b, const float* mask,
-                            const float* mean_rstd, void* T1a, void* T1b, const void* tw_row,
-                            int njobs, const mc_xc_geom* geom, const int* row_chord /* NULL or as in
-                            mc_xc_rows_forward_stats */, void* stream);
-/* The same reading the samples in their storage type (MC_STORE_F32 or MC_STORE_F16; job_off and
- * row_stride in elements): an fp16 movie is transformed without an fp32 copy of it.  Results are
- * those of the fp32 up-cast (the reference cannot run Half on the CPU at all). */
+ * mc_xc_rows_forward; row_chord: NULL or as in mc_xc_rows_forward_stats_t.  The samples are read in their
+ * storage type (MC_STORE_F32 or MC_STORE_F16; job_off and row_stride in elements): an fp16 movie is
+ * transformed without an fp32 copy of it.  Results are those of the fp32 up-cast (the reference cannot run
+ * Half on the CPU at all). */
 int mc_xc_rows_forward_dual_t(const void* src, int storage, const int64_t* job_off, int64_t row_stride,
                               const int* expo_a, const int* expo_b, const float* mask,
                               const float* mean_rstd, void* T1a, void* T1b, const void* tw_row,
@@ -189,9 +181,8 @@ int mc_xc_col_engine(int mode);
  * 1 = always one workgroup per row.  Process-wide; results agree to fp32 rounding. */
 int mc_xc_row_engine(int mode);
 
-/* m0 = {mean of the n floats at x, 1, 1}: the provisional mean mc_xc_rows_forward_stats takes
- * (one small workgroup; any value near the true mean serves). */
-int mc_xc_provisional_mean(const float* x, int n, float* m0, void* stream);
+/* m0 = {mean of the n samples at x (MC_STORE_F32 / MC_STORE_F16), 1, 1}: the provisional mean
+ * mc_xc_rows_forward_stats_t takes (one small workgroup; any value near the true mean serves). */
 int mc_xc_provisional_mean_t(const void* x, int storage, int n, float* m0, void* stream);
 
 /* K1 with the normalisation statistics fused in (whole-frame jobs only): samples become
@@ -204,15 +195,10 @@ int mc_xc_provisional_mean_t(const void* x, int storage, int n, float* m0, void*
  * row_chord (NULL, or H x 2 ints per WINDOW row y: first and last 4-aligned column whose quad
  * holds a non-zero mask value): samples outside a row's chord of the mask disk are not fetched
  * (they are multiplied by the mask's exact zero) -- 21 % of the support box of a circular mask.
- * The statistics box must lie inside the chords (the caller checks; plan.row_chords). */
-int mc_xc_rows_forward_stats(const float* src, const int64_t* job_off, int64_t row_stride,
-                             const float* mask, const float* m0, void* T1, const void* tw_row,
-                             int njobs, const mc_xc_geom* geom, int hl, int hu, int wl, int wu,
-                             double* acc, float* fix, float* out3, const int* row_chord,
-                             void* stream);
-/* The same reading the frames in their storage type (MC_STORE_F32 / MC_STORE_F16; job_off and row_stride
- * in samples): fp16 frames are read as they are by the wavefront-per-row kernel (4096-column frames;
- * MC_ERR_UNSUPPORTED otherwise: widen the stack and call mc_xc_rows_forward_stats). */
+ * The statistics box must lie inside the chords (the caller checks; plan.row_chords).
+ * The frames are read in their storage type (MC_STORE_F32 / MC_STORE_F16; job_off and row_stride in
+ * samples): fp16 frames are read as they are by the wavefront-per-row kernel (4096-column frames;
+ * MC_ERR_UNSUPPORTED otherwise: widen the stack and call again with MC_STORE_F32). */
 int mc_xc_rows_forward_stats_t(const void* src, int storage, const int64_t* job_off, int64_t row_stride,
                                const float* mask, const float* m0, void* T1, const void* tw_row,
                                int njobs, const mc_xc_geom* q, int hl, int hu, int wl, int wu,
@@ -390,22 +376,19 @@ int mc_spline_points(const float* data, int c, int nt, int nh, int nw, const int
  * pixel + shift/pixel_spacing with zero outside (_correct_frame + sample_image_2d,
  * correct_motion.py:81-129).  scratch: mc_warp_scratch_bytes() bytes, 16-byte aligned.
  * out_frames (nframes*h*w) and/or out_sum (h*w, OVERWRITTEN with the sum over the frames: the
- * caller need not clear it) may be NULL (not both). */
+ * caller need not clear it) may be NULL (not both).
+ * The frames come in their storage type (MC_STORE_F32 / MC_STORE_F16; outputs stay fp32).  fp16 frames are
+ * resampled straight from the fp16 bytes (half the HBM read) when w % 8 == 0, the frames are 16-byte aligned
+ * and the lattice is sparse (32 pixel rows span <= 1.5 lattice cells); otherwise MC_ERR_UNSUPPORTED: widen
+ * the stack and call again with MC_STORE_F32. */
 int mc_warp_scratch_bytes(int nframes, int h, int w, int GH, int GW, int64_t* bytes /*host*/);
-int mc_warp_frames(const float* frames, int nframes, int h, int w, const float* lattice, int GH,
-                   int GW, float pixel_spacing, float* scratch, float* out_frames, float* out_sum,
-                   void* stream);
-/* The same with the frames in their storage type (MC_STORE_F32 / MC_STORE_F16; outputs stay fp32).
- * fp16 frames are resampled straight from the fp16 bytes (half the HBM read) when w % 8 == 0, the
- * frames are 16-byte aligned and the lattice is sparse (32 pixel rows span <= 1.5 lattice cells);
- * otherwise MC_ERR_UNSUPPORTED: widen the stack and call mc_warp_frames. */
 int mc_warp_frames_t(const void* frames, int storage, int nframes, int h, int w, const float* lattice,
                      int GH, int GW, float pixel_spacing, float* scratch, float* out_frames, float* out_sum,
                      void* stream);
 
 /* N2: mc_warp_frames_t fed from the RAW movie: every sample is conditioned as raw * gain - mu[f] (gain (h,w)
  * fp32, mu from mc_raw_movie_stats) on its way into the resampler's window, so the outputs (fp32, same contract)
- * equal mc_warp_frames on the output of mc_condition_movie; outside the frame the result is the conditioned
+ * equal mc_warp_frames_t on the output of mc_condition_movie; outside the frame the result is the conditioned
  * domain's zero.  storage: MC_STORE_U8 (w % 16 == 0) or MC_STORE_I16 (w % 8 == 0); 16-byte aligned raw, the
  * sparse lattice of mc_warp_frames_t's fp16 path and h * w < 2^31; anything else is MC_ERR_UNSUPPORTED. */
 int mc_warp_frames_raw(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h, int w,
@@ -424,9 +407,9 @@ int mc_warp_frames_raw_accumulate(const void* raw, int storage, const float* gai
 
 /* N2: the rigid warp (correct_motion for a (2,t,1,1) field, correct_motion.py:18-78) fed from the RAW movie:
  * every sample is conditioned as raw * gain - mu[f] on its way to the resampler (examples/ttMotion.py:90-121,
- * 180-199), so the result equals mc_warp_rigid on the output of mc_condition_movie without that fp32 movie.
+ * 180-199), so the result equals mc_warp_rigid_phase_t on the output of mc_condition_movie without that fp32 movie.
  * storage: MC_STORE_U8 or MC_STORE_I16; gain (h,w) fp32; mu from mc_raw_movie_stats; scratch / phase as
- * mc_warp_rigid_phase.  w % 4 == 0 and 16-byte aligned buffers, else MC_ERR_UNSUPPORTED. */
+ * mc_warp_rigid_phase_t.  w % 4 == 0 and 16-byte aligned buffers, else MC_ERR_UNSUPPORTED. */
 int mc_warp_rigid_raw(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h, int w,
                       const float* shifts_px, float* scratch, float* out_frames, float* out_sum, int phase,
                       void* stream);
@@ -442,28 +425,23 @@ int mc_warp_rigid_raw_accumulate(const void* raw, int storage, const float* gain
 /* The tail of the rigid movie pipeline in two launches: integer-peak shifts (t,2) px of estimate_global_motion ->
  * field (2,t) Angstrom (image_shifts_to_deformation_field, deformation_field_utils.py:129-162), the per-frame
  * shifts the corrector uses (the field's spline at the frame times, correct_motion.py:57-72, lattice point
- * (0,0), / pixel_spacing) and the weight tables of mc_warp_rigid_phase(phase 1) in `scratch`.  Results are
- * bit for bit those of mc_spline_lattice + mc_warp_rigid_phase. */
+ * (0,0), / pixel_spacing) and the weight tables of mc_warp_rigid_phase_t(phase 1) in `scratch`.  Results are
+ * bit for bit those of mc_spline_lattice + mc_warp_rigid_phase_t. */
 int mc_rigid_tables_from_shifts(const float* shifts, float pixel_spacing, const int* idx_t, const float* w_t,
                                 const float* w_y, const float* w_x, int nframes, int h, int w, float* field,
                                 float* shifts_px, float* scratch, void* stream);
 
-/* Rigid special case of mc_warp_frames: a (2,nt,1,1) field gives each frame ONE shift,
+/* Rigid special case of mc_warp_frames_t: a (2,nt,1,1) field gives each frame ONE shift,
  * shifts_px[f] = (sy, sx) in pixels (device).  The coordinate chain is then separable
  * and the resample is a regular 5x5 separable correlation (see warp_rigid.hip).  Same
- * outputs/contract as mc_warp_frames.  scratch: mc_warp_rigid_scratch_bytes(). */
+ * outputs/contract as mc_warp_frames_t.  scratch: mc_warp_rigid_scratch_bytes().
+ * phase 0 does it all; for callers that want to time or schedule the resampling kernel on its own, phase 1
+ * fills the per-frame weight tables in `scratch` and phase 2 (same arguments) resamples.
+ * The frames come in their storage type (MC_STORE_F32 / MC_STORE_F16; outputs stay fp32): fp16 frames are
+ * DMA'd to LDS as they are and widened on the way to the registers (half the read bytes).  fp16 needs
+ * w % 8 == 0 and 16-byte aligned frames / out_frames, else MC_ERR_UNSUPPORTED (widen and call again with
+ * MC_STORE_F32). */
 int mc_warp_rigid_scratch_bytes(int nframes, int h, int w, int64_t* bytes /*host*/);
-int mc_warp_rigid(const float* frames, int nframes, int h, int w, const float* shifts_px,
-                  float* scratch, float* out_frames, float* out_sum, void* stream);
-/* The same in two steps, for callers that want to time or schedule the resampling kernel on its
- * own: phase 1 fills the per-frame weight tables in `scratch`, phase 2 (same arguments) resamples;
- * phase 0 = mc_warp_rigid. */
-int mc_warp_rigid_phase(const float* frames, int nframes, int h, int w, const float* shifts_px,
-                        float* scratch, float* out_frames, float* out_sum, int phase, void* stream);
-/* The same with the frames in their storage type (MC_STORE_F32 / MC_STORE_F16; outputs stay fp32): fp16
- * frames are DMA'd to LDS as they are and widened on the way to the registers (half the read bytes).
- * fp16 needs w % 8 == 0 and 16-byte aligned frames / out_frames, else MC_ERR_UNSUPPORTED (widen and
- * call mc_warp_rigid). */
 int mc_warp_rigid_phase_t(const void* frames, int storage, int nframes, int h, int w, const float* shifts_px,
                           float* scratch, float* out_frames, float* out_sum, int phase, void* stream);
 

@@ -25,12 +25,13 @@ def stage1():  # K1 (+ provisional mean)
     st = stream_ptr(dev)
     acc = torch.empty(128, dtype=torch.float64, device=dev)
     m0 = torch.ones(3, dtype=torch.float32, device=dev)
-    check(lib.mc_central_box_stats(ptr(stack), 1, h, w, hl, hl + 1, wl, wu, ptr(acc), ptr(m0), st), "m0")
+    check(lib.mc_central_box_stats_t(ptr(stack), engine.STORE_F32, 1, h, w, hl, hl + 1, wl, wu, ptr(acc), ptr(m0), st), "m0")
     m0[1:].fill_(1.0)
     fix = torch.empty(2, device=dev); out3 = torch.empty(3, device=dev)
     T1 = torch.empty((t, g.nkx, g.ny, 2), device=dev)
-    check(lib.mc_xc_rows_forward_stats(ptr(stack), ptr(job_off), w, ptr(pl.mask), ptr(m0), ptr(T1), ptr(pl.tw_row), t, g,
-                                       hl, hu, wl, wu, ptr(acc), ptr(fix), ptr(out3), ptr(pl.chord), st), "k1")
+    check(lib.mc_xc_rows_forward_stats_t(ptr(stack), engine.STORE_F32, ptr(job_off), w, ptr(pl.mask), ptr(m0), ptr(T1),
+                                         ptr(pl.tw_row), t, g, hl, hu, wl, wu, ptr(acc), ptr(fix), ptr(out3), ptr(pl.chord),
+                                         st), "k1")
     return T1, fix
 
 def stage2(T1, fix):  # K2 .. K5

@@ -1,4 +1,4 @@
-"""A float64 reference of the deformation-field warp (mc_warp_frames: csrc/warp_field.hip with warp_field_plan,
+"""A float64 reference of the deformation-field warp (mc_warp_frames_t: csrc/warp_field.hip with warp_field_plan,
 warp_field3, warp_field_slow and the route rule; csrc/warp_field_fallback.hip with warp_main, warp_field2; the
 tables of csrc/field_tables.hip) driven with a hand-made (t, 2, GH, GW) Angstrom lattice, the cases the
 GPU tests run (tests/test_field_kernels_float64.py) and the host emulation of the documented dispatch rules

@@ -704,10 +704,10 @@ def test_wave_row_engine_matches_workgroup_engine(dev, h, fr):
             acc = torch.empty(128, dtype=torch.float64, device=dev)
             fix = torch.empty(2, device=dev)
             out3 = torch.empty(3, device=dev)
-            check(lib.mc_xc_rows_forward_stats(ptr(img), ptr(off), w, ptr(pl.mask), ptr(m0), ptr(T1),
-                                               ptr(pl.tw_row), t, gm, hl, hu, wl, wu, ptr(acc), ptr(fix),
-                                               ptr(out3), ptr(pl.chord) if mode == 0 else None,
-                                               stream_ptr(dev)), "rows_forward_stats")
+            check(lib.mc_xc_rows_forward_stats_t(ptr(img), engine.STORE_F32, ptr(off), w, ptr(pl.mask), ptr(m0), ptr(T1),
+                                                 ptr(pl.tw_row), t, gm, hl, hu, wl, wu, ptr(acc), ptr(fix),
+                                                 ptr(out3), ptr(pl.chord) if mode == 0 else None,
+                                                 stream_ptr(dev)), "rows_forward_stats")
             plain = torch.zeros_like(T1)
             st = torch.tensor([11.0, 0.5], device=dev)
             check(lib.mc_xc_rows_forward(ptr(img), ptr(off), w, None, ptr(pl.mask), ptr(st), ptr(plain),
@@ -862,7 +862,7 @@ def test_motion_correct_sum_dose_weighting_streams_chunks(mc, dev, switches, rig
 
 
 def test_wave512_patch_rows_match_workgroup_engine(dev):
-    """mc_xc_rows_forward_dual (one wavefront per 1024-sample row, U and V from one read)
+    """mc_xc_rows_forward_dual_t (one wavefront per 1024-sample row, U and V from one read)
     against the workgroup-per-row K1 run twice, on patch jobs at odd and even offsets."""
     from torch_motion_correction_amd import _lib, plan
     from torch_motion_correction_amd._lib import check, ptr, stream_ptr
@@ -882,10 +882,10 @@ def test_wave512_patch_rows_match_workgroup_engine(dev):
     stats = torch.tensor([4.0, 0.7], device=dev)
     st = stream_ptr(dev)
     Ua, Ub, Ra, Rb, Sa = (torch.zeros((n, gm.nkx, gm.ny, 2), device=dev) for _ in range(5))
-    check(lib.mc_xc_rows_forward_dual(ptr(img), ptr(off), w, ptr(ea), ptr(eb), ptr(pl.mask), ptr(stats), ptr(Ua),
-                                      ptr(Ub), ptr(pl.tw_row), n, gm, ptr(pl.chord), st), "dual")  # chord-clamped loads
-    check(lib.mc_xc_rows_forward_dual(ptr(img), ptr(off), w, ptr(ea), None, ptr(pl.mask), ptr(stats), ptr(Sa), None,
-                                      ptr(pl.tw_row), n, gm, None, st), "single")  # box-clamped loads
+    check(lib.mc_xc_rows_forward_dual_t(ptr(img), 3, ptr(off), w, ptr(ea), ptr(eb), ptr(pl.mask), ptr(stats), ptr(Ua),
+                                        ptr(Ub), ptr(pl.tw_row), n, gm, ptr(pl.chord), st), "dual")  # chord-clamped loads
+    check(lib.mc_xc_rows_forward_dual_t(ptr(img), 3, ptr(off), w, ptr(ea), None, ptr(pl.mask), ptr(stats), ptr(Sa), None,
+                                        ptr(pl.tw_row), n, gm, None, st), "single")  # box-clamped loads
     check(lib.mc_xc_rows_forward(ptr(img), ptr(off), w, ptr(ea), ptr(pl.mask), ptr(stats), ptr(Ra), ptr(pl.tw_row),
                                  n, gm, st), "wg a")
     check(lib.mc_xc_rows_forward(ptr(img), ptr(off), w, ptr(eb), ptr(pl.mask), ptr(stats), ptr(Rb), ptr(pl.tw_row),
@@ -1638,9 +1638,9 @@ _FP16_NATIVE = {((3, 416, 520), (2, 2)), ((3, 200, 264), (1, 2))}
 def test_fp16_frames_through_the_field_warp(mc, dev, shape, grid, ps, monkeypatch):
     """The deformation-field warp on fp16 frames == the warp of the fp32 up-cast, frames and sum, bit for bit.
     native: the shape is one warp_field3<HALF> reads (window DMA'd as fp16, widened in LDS; borders, edge tiles,
-    non-unit spacing) -- the widening fallback entry mc_warp_frames is never called; the other shapes (a dense
-    lattice for the frame height, a row length that is not a multiple of 8) pin that fallback: every fp16 warp goes
-    through it.  (The fp16 kernel against an independent float64 reference: tests/test_field_kernels_float64.py.)"""
+    non-unit spacing) -- the widening fallback (a second mc_warp_frames_t call, tagged fp32) never happens; the
+    other shapes (a dense lattice for the frame height, a row length that is not a multiple of 8) pin that fallback:
+    every fp16 warp goes through it.  (The fp16 kernel against an independent float64 reference: tests/test_field_kernels_float64.py.)"""
     from field_reference import route_of, tile_plan
     from torch_motion_correction_amd import _lib, engine
 
@@ -1648,23 +1648,25 @@ def test_fp16_frames_through_the_field_warp(mc, dev, shape, grid, ps, monkeypatc
     native = (shape, grid) in _FP16_NATIVE
     assert (route_of(h, w, 10 * grid[0], "f16") == "warp_field3") == native
     lib = _lib.load()
-    fallback = lib.mc_warp_frames
-    calls = []
+    entry = lib.mc_warp_frames_t
+    calls = []  # the storage tag of every call
+    F16, F32 = engine.STORE_F16, engine.STORE_F32
+    fp16_calls = [F16] if native else [F16, F32]  # refused as fp16, then widened
 
     def counted(*a):
-        calls.append(a)
-        return fallback(*a)
+        calls.append(a[1])
+        return entry(*a)
 
-    monkeypatch.setattr(lib, "mc_warp_frames", counted)
+    monkeypatch.setattr(lib, "mc_warp_frames_t", counted)
     g = torch.Generator().manual_seed(h + w)
     st16 = (torch.randn(t, h, w, generator=g) * 2 + 1).half().to(dev)
     field = (torch.randn(2, t, *grid, generator=g) * 1.5).to(dev)
     for gt in ("bspline", "catmull_rom"):
         n = len(calls)
         sa, fa = mc.motion_correct_sum(st16, field, ps, grid_type=gt, return_frames=True)
-        assert len(calls) - n == (0 if native else 1)
+        assert calls[n:] == fp16_calls
         sb, fb = mc.motion_correct_sum(st16.float(), field, ps, grid_type=gt, return_frames=True)
-        assert len(calls) - n == (0 if native else 1)  # fp32 stacks never take the fallback entry
+        assert calls[n:] == fp16_calls + [F32]  # fp32 stacks: one call, no fallback
         assert fa.dtype == torch.float32 and torch.equal(fa, fb) and torch.equal(sa, sb)
     # rough field: some tile-frames fail the regularity test and take the generic kernel (native shapes: a field on
     # the shape's own grid, so that the lattice stays sparse and warp_field_slow<HALF> runs -- asserted from the
@@ -1679,7 +1681,7 @@ def test_fp16_frames_through_the_field_warp(mc, dev, shape, grid, ps, monkeypatc
         assert irregular.any() and not irregular.all()
     n = len(calls)
     fa = mc.correct_motion(st16, rough, ps, grid_type="bspline")
-    assert len(calls) - n == (0 if native else 1)
+    assert calls[n:] == fp16_calls
     fb = mc.correct_motion(st16.float(), rough, ps, grid_type="bspline")
     assert torch.equal(fa, fb)
     # and against the oracle on the up-cast

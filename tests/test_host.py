@@ -224,7 +224,7 @@ def test_abi_rejects_bad_arguments_without_touching_the_gpu():
     assert lib.mc_warp_scratch_bytes(4, 64, 64, 10, 10, ctypes.byref(n)) == 0 and n.value > 0
     assert lib.mc_warp_rigid_scratch_bytes(4, 64, 64, ctypes.byref(n)) == 0 and n.value > 0
     assert lib.mc_circle_mask(None, None, 64, 64, 16.0, 8.0, None) == -1  # MC_ERR_ARG
-    assert lib.mc_warp_frames(None, 1, 64, 64, None, 10, 10, 1.0, None, None, None, None) == -1
+    assert lib.mc_warp_frames_t(None, 3, 1, 64, 64, None, 10, 10, 1.0, None, None, None, None) == -1
 
 
 def test_full_spectrum_and_storage_entry_points_check_arguments_on_the_host():

@@ -1,9 +1,10 @@
-"""The statistics variants of the wave-per-row K1 (xc_rows_fwd_wave<KEEP, STATS = true, ...>) keep no state in
-scratch memory, and still compute what they computed.
+"""The variants of the wave-per-row K1 (xc_rows_fwd_wave<KEEP, STATS, ...>) keep no state in scratch memory, and
+still compute what they computed.
 
 Host: csrc/xc_rows_fwd_wave.hip compiled for gfx950 with the library's flags; every instantiation's scratch size and
-VGPR count read from the code object's metadata notes (nothing is disassembled).  Every STATS = true instantiation
-has 0 bytes of scratch, every instantiation at most 256 VGPRs and at most 40 KiB of LDS (four workgroups per CU).
+VGPR count read from the code object's metadata notes (nothing is disassembled).  There are 16 instantiations, the
+ones an entry point can launch: 8 with statistics, 8 without.  Every one has 0 bytes of scratch, at most 256 VGPRs
+and at most 40 KiB of LDS (four workgroups per CU).
 
 GPU: mc_xc_rows_forward_stats_t called directly at the smallest shape the wave engine takes -- rows of 4096 samples,
 64 rows (two rounds of WF_ROWS_PER_WG = 32 rows: the running sums are carried from round to round), 2 frames -- on a
@@ -23,6 +24,17 @@ Judged against float64, with the bounds of tests/test_xc_kernels_float64.py for 
               the same fp32 mask values, so the table's own error drops out), the row transform costs
               line_costs(g)['rows_fwd'].  No column pass, no filter.  A bin's error scales with its own row's norm;
               the rows of these masks have the same norm to 2 %, so the per-bin statement uses their rms.
+
+The eight variants without statistics (fp32 with all 16 chunks or the 14 inner ones, u8 and i16, each with KEEP 1 and
+2): five run on 4096-column rows with 64 or more support rows in other tests -- fp32 all-16 with KEEP 1 and 2 in
+test_xc_kernels_float64.py::test_wave_per_row_k1 ((2, 512, 4096), bands 20 and 10), fp32 inner with KEEP 2 in
+test_gpu_parity.py::test_wave_row_engine_matches_workgroup_engine (h = 4096), u8 and i16 with KEEP 2 in
+test_xc_kernels_float64.py::test_raw_movies ((2, 512, 4096)).  The other three run here, at the shapes above: fp32
+inner with KEEP 1 through mc_xc_rows_forward, u8 and i16 with KEEP 1 through mc_xc_rows_forward_raw (gain in
+[0.8, 1.2], an offset per frame).  Same judgement: check_spectra with (5 + |mean| / std) u for the normalisation
+with supplied statistics (the `norm` term of xc_reference.spectra_bounds; raw input: mean 0), u for the mask product,
+line_costs(g)['rows_fwd'], and for raw input the conditioning's rounding (rigid_reference.conditioning_error in L2
+over the masked job, as tests/test_xc_kernels_float64.py::test_raw_movies adds it).
 """
 
 import ctypes as C
@@ -37,6 +49,7 @@ import pytest
 import torch
 
 import xc_reference as xr
+from rigid_reference import condition_float64, conditioning_error
 from kernel_harness import assert_guards, calls, nan_buffer  # noqa: F401
 
 U = xr.U
@@ -77,12 +90,11 @@ def test_statistics_variants_use_no_scratch(tmp_path):
             kernels[name.group(1)] = (name.group(3) == "1", field("private_segment_fixed_size"), field("vgpr_count"),
                                       field("group_segment_fixed_size"))
     stats = {k: v for k, v in kernels.items() if v[0]}
-    assert len(kernels) == 20 and len(stats) == 8, sorted(kernels)
+    assert len(kernels) == 16 and len(stats) == 8, sorted(kernels)
     for name, (st, scratch, vgpr, lds) in sorted(kernels.items()):
         print(f"{name[:52]} scratch {scratch} vgpr {vgpr} lds {lds}")
         assert vgpr <= 256 and lds <= 40960, f"{name}: {vgpr} VGPRs, {lds} bytes of LDS"
-        if st:
-            assert scratch == 0, f"{name}: {scratch} bytes of scratch per lane"
+        assert scratch == 0, f"{name}: {scratch} bytes of scratch per lane"
 
 
 # ------------------------------------------------------------------ GPU: the eight variants against float64
@@ -205,3 +217,80 @@ def test_last_workgroup_with_fewer_rows(dev, calls, route):
     rows instead of four -- every wave transforms one pair of rows there, and no sum of a round that did not run
     enters the statistics."""
     _check(dev, calls, 2, route, 1000.0, 30.0, y0=8, ny=40, box_rows=(16, 44))
+
+
+# ------------------------------------------------------------------ GPU: the variants without statistics
+
+
+def _check_plain(dev, calls, kind, y0=0, ny=H):
+    """KEEP = 1 without statistics.  kind 'f32': the 14 inner chunks through mc_xc_rows_forward; 'u8' / 'i16': all 16
+    chunks through mc_xc_rows_forward_raw."""
+    from torch_motion_correction_amd import plan
+    from torch_motion_correction_amd._lib import check, ptr, stream_ptr
+
+    raw = kind != "f32"
+    x0, x1 = (0, 4096) if raw else (300, 3800)
+    g = _geometry(NKX[1], x0, x1, y0, ny)
+    mask = _mask(x0, x1, False)
+    maskd = mask.to(dev)
+    tw = plan.get_twiddles(W, dev)
+    off = (torch.arange(T, dtype=torch.int64) * (H * W)).to(dev)
+    st = stream_ptr(dev)
+    T1, flat = nan_buffer((T, g.nkx, g.ny, 2), dev)
+    what = f"KEEP 1 {kind} without statistics rows {y0}+{ny}"
+    m64 = mask.double().numpy()[None]
+    norm = lambda a: np.array([np.linalg.norm(a[f, y0:y0 + ny]) for f in range(T)])  # noqa: E731
+    calls.clear()
+    if raw:
+        gen = torch.Generator().manual_seed(11 + (kind == "u8"))
+        if kind == "u8":
+            x = torch.clamp(torch.round(torch.randn(T, H, W, generator=gen) * 6 + 40), 0, 255).to(torch.uint8)
+        else:
+            x = torch.round(torch.randn(T, H, W, generator=gen) * 30 + 1000).to(torch.int16)
+        gain = (0.8 + 0.4 * torch.rand(H, W, generator=gen)).float()
+        v = x.double() * gain.double()
+        sub = v.mean(dim=(1, 2)).float()  # an offset per frame
+        stats = torch.tensor([0.0, 1.0 / float(v.std())], dtype=torch.float32)
+        xd, gaind, subd, statsd = x.to(dev), gain.to(dev), sub.to(dev), stats.to(dev)
+        check(calls.mc_xc_rows_forward_raw(ptr(xd), 0 if kind == "u8" else 1, ptr(gaind), ptr(off), W, ptr(maskd),  # MC_STORE_U8 / _I16
+                                           ptr(subd), ptr(statsd), ptr(T1), ptr(tw), T, g, None, st),
+              "mc_xc_rows_forward_raw")
+        torch.cuda.synchronize()
+        calls.ran("mc_xc_rows_forward_raw")
+        c = condition_float64(x.numpy(), gain.numpy(), sub.numpy())
+        xn = c * float(stats[1]) * m64
+        cond = norm(conditioning_error(x.numpy(), gain.numpy(), sub.numpy()) * m64) / norm(c * m64)
+        d = 0.0
+    else:
+        x = xr.noise(T, H, W, mean=5.0, std=2.0, seed=3)
+        mean, std = float(x.double().mean()), float(x.double().std())
+        stats = torch.tensor([mean, 1.0 / std], dtype=torch.float32)
+        xd, statsd = x.to(dev), stats.to(dev)
+        check(calls.mc_xc_rows_forward(ptr(xd), ptr(off), W, None, ptr(maskd), ptr(statsd), ptr(T1), ptr(tw), T, g, st),
+              "mc_xc_rows_forward")
+        torch.cuda.synchronize()
+        calls.ran("mc_xc_rows_forward")
+        xn = (x.double().numpy() - mean) / std * m64
+        cond = np.zeros(T)
+        d = abs(mean) / std
+    assert_guards(T1, flat, "T1")
+    ref = np.ascontiguousarray(np.fft.rfft(xn[:, y0:y0 + ny], axis=2)[:, :, :g.nkx].transpose(0, 2, 1))
+    parts = {"S": ref, "filt": np.ones(ref.shape[1:]), "rms": norm(xn) / math.sqrt(ny)}
+    rel = (5 + d) * U + U + xr.line_costs(g)["rows_fwd"]
+    bounds = [{"rel": rel + float(cond[f]), "fix_l2": 0.0, "fix_bin": 0.0} for f in range(T)]
+    r = xr.check_spectra(T1.cpu(), parts, bounds, what)
+    print(f"RATIO K1 variant {what}: L2 {r[0]:.3f} bin {r[1]:.3f}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["f32", "u8", "i16"])
+def test_variants_without_statistics_against_float64(dev, calls, kind):
+    """The three instantiations without statistics that no other test launches on 4096-column rows (module
+    docstring), on 64 rows = two workgroups of four store rounds."""
+    _check_plain(dev, calls, kind)
+
+
+@pytest.mark.gpu
+def test_last_workgroup_with_fewer_rows_without_statistics(dev, calls):
+    """40 support rows from row 8, u8 samples: the second workgroup runs one round of 8 rows instead of four."""
+    _check_plain(dev, calls, "u8", y0=8, ny=40)

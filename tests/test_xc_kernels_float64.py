@@ -132,7 +132,7 @@ def _box_stats(x, box):
 def _fused_route(engine, img, pl, box):
     """The fused-statistics route of engine._global_spectra, launch for launch, with the statistics box given -- for
     the one case the engine cannot be steered to: a box OFF the 256-sample chunk grid on 4096-column rows, where the
-    statistics stay on the workgroup form of mc_xc_rows_forward_stats (every box the engine forms on such rows is on
+    statistics stay on the workgroup form of mc_xc_rows_forward_stats_t (every box the engine forms on such rows is on
     the grid).  Everything else goes through the engine's own seams."""
     import ctypes as C
 
@@ -150,14 +150,14 @@ def _fused_route(engine, img, pl, box):
     acc = torch.empty(128, dtype=torch.float64, device=dev)
     m0 = torch.empty(3, dtype=torch.float32, device=dev)
     check(lib.mc_xc_provisional_mean_t(C.c_void_p(img.data_ptr() + img.element_size() * (hl * w + wl)),
-                                       engine.storage_of(img), wu - wl, ptr(m0), st), "mc_xc_provisional_mean")
+                                       engine.storage_of(img), wu - wl, ptr(m0), st), "mc_xc_provisional_mean_t")
     fix = torch.empty(2, dtype=torch.float32, device=dev)
     out3 = torch.empty(3, dtype=torch.float32, device=dev)
     T1 = torch.empty((t, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
     S = torch.empty((t, g.nkx, g.nky, 2), dtype=torch.float32, device=dev)
     check(lib.mc_xc_rows_forward_stats_t(ptr(img), engine.storage_of(img), ptr(off), w, ptr(pl.mask), ptr(m0), ptr(T1),
                                          ptr(pl.tw_row), t, g, hl, hu, wl, wu, ptr(acc), ptr(fix), ptr(out3),
-                                         ptr(engine._box_chords(pl, hl, hu, wl, wu)), st), "mc_xc_rows_forward_stats")
+                                         ptr(engine._box_chords(pl, hl, hu, wl, wu)), st), "mc_xc_rows_forward_stats_t")
     check(lib.mc_xc_cols_forward_fix(ptr(T1), ptr(pl.filt), ptr(S), ptr(pl.tw_col), t, g, ptr(fix), ptr(mhat), st),
           "mc_xc_cols_forward_fix")
     torch.cuda.synchronize()
@@ -315,7 +315,7 @@ FUSED_BOXES = {(1, 4096, 4096): None,                    # the engine's own rout
 @pytest.mark.parametrize("shape", list(FUSED_BOXES), ids=lambda s: "x".join(map(str, s)))
 @pytest.mark.parametrize("mean,std", xr.STAT_INPUTS)
 def test_fused_statistics_and_fix_up(dev, calls, switches, shape, mean, std):
-    """mc_xc_rows_forward_stats + mc_xc_cols_forward_fix on N(0, 1), N(40, 2.5^2) and counts-like N(1000, 30^2): the
+    """mc_xc_rows_forward_stats_t + mc_xc_cols_forward_fix on N(0, 1), N(40, 2.5^2) and counts-like N(1000, 30^2): the
     provisional mean keeps d = |mean - m0| / std small, so the fix-up's term stays small and the bound barely moves --
     a route that subtracted nothing would need d = 33 on the last input.  The statistics the kernel returns are
     within their roundings of the float64 ones."""

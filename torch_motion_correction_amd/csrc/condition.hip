@@ -407,11 +407,6 @@ int mc_raw_movie_stats(const void* raw, int kind, const float* gain, int nframes
   return mc_check_launch();
 }
 
-int mc_central_box_stats(const float* stack, int t, int h, int w, int hl, int hu, int wl, int wu,
-                         double* acc, float* out3, void* stream) {
-  return mc_central_box_stats_t(stack, MC_STORE_F32, t, h, w, hl, hu, wl, wu, acc, out3, stream);
-}
-
 int mc_central_box_stats_t(const void* stack, int storage, int t, int h, int w, int hl, int hu, int wl,
                            int wu, double* acc, float* out3, void* stream) {
   if (!stack || !acc || !out3 || t < 1 || hl < 0 || hu > h || wl < 0 || wu > w || hl >= hu ||

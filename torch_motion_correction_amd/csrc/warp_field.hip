@@ -1,6 +1,6 @@
 // The production deformation-field warp: bicubic frame resample along a cubic-spline shift lattice
 // (+ optional fused frame sum) for fp32, fp16 and raw u8 / i16 frames -- warp_field_plan, warp_field3 and
-// warp_field_slow -- and the entry points mc_warp_frames*, which pick a route (field_route below).  The
+// warp_field_slow -- and the entry points mc_warp_frames_*, which pick a route (field_route below).  The
 // lattice tables come from field_tables.hip, the two fallback kernels live in warp_field_fallback.hip.
 //
 // No FMA contraction in this object: warp_field_common.h says why.
@@ -698,13 +698,6 @@ int mc_warp_frames_t(const void* frames, int storage, int nframes, int h, int w,
     mc_pick(pixel_spacing == 1.0f, [&](auto U) { field_slow_launch<U.value, false, 0>(fa, s); });
   }
   return mc_check_launch();
-}
-
-int mc_warp_frames(const float* frames, int nframes, int h, int w, const float* lattice, int GH,
-                   int GW, float pixel_spacing, float* scratch, float* out_frames, float* out_sum,
-                   void* stream) {
-  return mc_warp_frames_t(frames, MC_STORE_F32, nframes, h, w, lattice, GH, GW, pixel_spacing, scratch,
-                          out_frames, out_sum, stream);
 }
 
 int mc_warp_frames_raw(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h, int w,

@@ -703,10 +703,12 @@ void mc_rigid_tables_launch(const float* shifts_px, int nframes, int h, int w, c
                      (const int*)t.S, t.Wy, t.Wx);
 }
 
-// phase 0: weight tables + resampling (mc_warp_rigid); 1: tables only; 2: resampling only, the
+extern "C" {
+
+// phase 0: weight tables + resampling; 1: tables only; 2: resampling only, the
 // tables of an earlier phase-1 call with the same arguments are in `scratch`
-static int warp_rigid_impl(const void* frames_any, int storage, int nframes, int h, int w, const float* shifts_px,
-                           float* scratch, float* out_frames, float* out_sum, int phase, void* stream) {
+int mc_warp_rigid_phase_t(const void* frames_any, int storage, int nframes, int h, int w, const float* shifts_px,
+                          float* scratch, float* out_frames, float* out_sum, int phase, void* stream) {
   const float* frames = static_cast<const float*>(frames_any);
   if (storage != MC_STORE_F32 && storage != MC_STORE_F16) return MC_ERR_UNSUPPORTED;
   // fp16 frames: only the LDS-DMA kernel's 512 x 32 geometry, rows of whole 8-sample units
@@ -753,32 +755,15 @@ static int warp_rigid_impl(const void* frames_any, int storage, int nframes, int
   return mc_check_launch();
 }
 
-extern "C" {
-
 int mc_warp_rigid_scratch_bytes(int nframes, int h, int w, int64_t* bytes) {
   if (!bytes || nframes < 1 || h < 2 || w < 2) return MC_ERR_ARG;
   *bytes = rigid_tables_layout(nullptr, nframes, h, w).bytes;
   return MC_OK;
 }
 
-int mc_warp_rigid_phase(const float* frames, int nframes, int h, int w, const float* shifts_px,
-                        float* scratch, float* out_frames, float* out_sum, int phase, void* stream) {
-  return warp_rigid_impl(frames, MC_STORE_F32, nframes, h, w, shifts_px, scratch, out_frames, out_sum, phase, stream);
-}
-
-int mc_warp_rigid_phase_t(const void* frames, int storage, int nframes, int h, int w, const float* shifts_px,
-                          float* scratch, float* out_frames, float* out_sum, int phase, void* stream) {
-  return warp_rigid_impl(frames, storage, nframes, h, w, shifts_px, scratch, out_frames, out_sum, phase, stream);
-}
-
-int mc_warp_rigid(const float* frames, int nframes, int h, int w, const float* shifts_px,
-                  float* scratch, float* out_frames, float* out_sum, void* stream) {
-  return warp_rigid_impl(frames, MC_STORE_F32, nframes, h, w, shifts_px, scratch, out_frames, out_sum, 0, stream);
-}
-
 // The movie pipeline's tail in two launches (rigid_tail + rigid_weights): integer-peak shifts (t,2) px ->
 // field (2,t) Angstrom, the warp's shifts_px (t,2) and its weight tables in `scratch` (the layout of
-// mc_warp_rigid_phase, phase 1).  idx_t / w_t: the 4 time taps per frame of the field's spline
+// mc_warp_rigid_phase_t, phase 1).  idx_t / w_t: the 4 time taps per frame of the field's spline
 // (spline.axis_taps(t, linspace(0,1,t))), w_y / w_x: the taps of lattice point 0 on a 1-sample axis.
 int mc_rigid_tables_from_shifts(const float* shifts, float pixel_spacing, const int* idx_t, const float* w_t,
                                 const float* w_y, const float* w_x, int nframes, int h, int w, float* field,

@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256) void warp_rigid_hot_taps(const long long* __re
 }
 
 // N2: the rigid warp straight from a raw u8 / i16 movie + gain reference (warp_rigid_raw); phase as in
-// mc_warp_rigid_phase.  Shapes it has no kernel for (w % 4, unaligned buffers): MC_ERR_UNSUPPORTED -- the
+// mc_warp_rigid_phase_t.  Shapes it has no kernel for (w % 4, unaligned buffers): MC_ERR_UNSUPPORTED -- the
 // caller conditions the movie into an fp32 copy first.
 static int warp_rigid_raw_impl(const void* raw, int storage, const float* gain, const float* mu, int nframes, int h,
                                int w, const float* shifts_px, float* scratch, float* out_frames, float* out_sum,

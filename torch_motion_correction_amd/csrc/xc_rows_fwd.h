@@ -11,8 +11,8 @@
 enum K1WaveLoads {
   K1_LOADS_ALL,          // all 16 chunks, each clamped to the support box, or to the row's chord given a table
   K1_LOADS_INNER,        // chunks 1 .. 14; only the first and the last of them clamped, to the support box
-  K1_LOADS_INNER_CHORD,  // chunks 1 .. 14, each clamped to the row's chord
-  K1_LOADS_HALF,         // fp16 samples: as K1_LOADS_ALL
+  K1_LOADS_INNER_CHORD,  // chunks 1 .. 14, each clamped to the row's chord (with statistics only)
+  K1_LOADS_HALF,         // fp16 samples: as K1_LOADS_ALL (with statistics only)
 };
 struct K1WaveVariant {
   bool keep1;
@@ -29,7 +29,8 @@ __attribute__((visibility("hidden"))) int k1_wg_launch(int raw, const void* src,
                                                        const float* mean_rstd, void* T1, const void* tw_row, int njobs,
                                                        const XcGeom& g, const XcBox& b, double* stats_acc,
                                                        const float* gain, const float* job_sub, void* stream);
-// xc_rows_fwd_wave.hip; raw samples run K1_LOADS_ALL without statistics
+// xc_rows_fwd_wave.hip; raw samples run K1_LOADS_ALL without statistics; MC_ERR_UNSUPPORTED for a statistics-only
+// variant without statistics
 __attribute__((visibility("hidden"))) int k1_wave_launch(K1WaveVariant v, int raw, const void* src,
                                                          const int64_t* job_off, int64_t row_stride, const float* mask,
                                                          const float* mean_rstd, void* T1, const void* tw_row,

@@ -166,14 +166,6 @@ static int rows_forward_impl(const float* src, const int64_t* job_off, int64_t r
   }
 }
 
-int mc_xc_rows_forward_dual(const float* src, const int64_t* job_off, int64_t row_stride,
-                            const int* expo_a, const int* expo_b, const float* mask,
-                            const float* mean_rstd, void* T1a, void* T1b, const void* tw_row,
-                            int njobs, const mc_xc_geom* q, const int* row_chord, void* stream) {
-  return mc_xc_rows_forward_dual_t(src, MC_STORE_F32, job_off, row_stride, expo_a, expo_b, mask, mean_rstd,
-                                   T1a, T1b, tw_row, njobs, q, row_chord, stream);
-}
-
 int mc_xc_rows_forward_dual_t(const void* src, int storage, const int64_t* job_off, int64_t row_stride,
                               const int* expo_a, const int* expo_b, const float* mask,
                               const float* mean_rstd, void* T1a, void* T1b, const void* tw_row,
@@ -217,27 +209,16 @@ int mc_xc_rows_forward(const float* src, const int64_t* job_off, int64_t row_str
                            nullptr, nullptr, stream);
 }
 
-int mc_xc_provisional_mean(const float* x, int n, float* m0, void* stream) {
-  if (!x || !m0 || n < 1) return MC_ERR_ARG;
-  hipLaunchKernelGGL(xc_provisional_mean_kernel<float>, dim3(1), dim3(256), 0, (hipStream_t)stream, x, n, m0);
-  return mc_check_launch();
-}
-
 int mc_xc_provisional_mean_t(const void* x, int storage, int n, float* m0, void* stream) {
   if (!x || !m0 || n < 1) return MC_ERR_ARG;
-  if (storage == MC_STORE_F32) return mc_xc_provisional_mean(static_cast<const float*>(x), n, m0, stream);
-  if (storage != MC_STORE_F16) return MC_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(xc_provisional_mean_kernel<_Float16>, dim3(1), dim3(256), 0, (hipStream_t)stream,
-                     static_cast<const _Float16*>(x), n, m0);
+  if (storage != MC_STORE_F32 && storage != MC_STORE_F16) return MC_ERR_UNSUPPORTED;
+  if (storage == MC_STORE_F32)
+    hipLaunchKernelGGL(xc_provisional_mean_kernel<float>, dim3(1), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const float*>(x), n, m0);
+  else
+    hipLaunchKernelGGL(xc_provisional_mean_kernel<_Float16>, dim3(1), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const _Float16*>(x), n, m0);
   return mc_check_launch();
-}
-
-int mc_xc_rows_forward_stats(const float* src, const int64_t* job_off, int64_t row_stride,
-                             const float* mask, const float* m0, void* T1, const void* tw_row,
-                             int njobs, const mc_xc_geom* q, int hl, int hu, int wl, int wu,
-                             double* acc, float* fix, float* out3, const int* row_chord, void* stream) {
-  return mc_xc_rows_forward_stats_t(src, MC_STORE_F32, job_off, row_stride, mask, m0, T1, tw_row, njobs, q, hl, hu,
-                                    wl, wu, acc, fix, out3, row_chord, stream);
 }
 
 int mc_xc_rows_forward_stats_t(const void* src_any, int storage, const int64_t* job_off, int64_t row_stride,

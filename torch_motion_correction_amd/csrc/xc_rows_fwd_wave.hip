@@ -1,6 +1,7 @@
 // K1 of the pruned cross-correlation engine (xc_common.h has the map of the passes), the wave-per-row engine:
 // a wavefront per 4096-sample row of a whole frame, fp32 / fp16 / u8 / i16 samples, with or without the fused
-// frame statistics.  xc_rows_fwd.hip has the entry points and the rules that route a job here and choose its variant.
+// frame statistics (16 kernels: k1_wave_launch instantiates what an entry point can ask for and no more).
+// xc_rows_fwd.hip has the entry points and the rules that route a job here and choose its variant.
 #include "xc_rows_fwd.h"
 
 // ------------------------------------------------------------------ K1, wave per row
@@ -33,7 +34,7 @@ __device__ __forceinline__ void wf_pin(int& v, float dep) { asm volatile("" : "+
 #define WF_TWA (4 * 128)
 #define WF_TWB (4 * 15 * 2)
 constexpr int WF_ROWS_PER_WG = 32;  // rounds of 8 rows: a wave takes rows 2 wv and 2 wv + 1 of every round (16: the prologue is 22 % of a wave's life; 32: K1 445 -> 430 us)
-constexpr int WF_MIN_WG = 2;  // workgroups per CU the register allocation aims at = waves per SIMD (2: up to 256 VGPRs per lane, none of the 20 variants spills; 3: 168, 416 B of scratch)
+constexpr int WF_MIN_WG = 2;  // workgroups per CU the register allocation aims at = waves per SIMD (2: up to 256 VGPRs per lane, none of the 16 variants spills; 3: 168, 416 B of scratch)
 
 // N1LO / N1HI: only the 256-sample chunks [N1LO, N1HI) of a row can touch the mask support,
 // the others are zero and are not loaded.  CLAMP_ALL = false: the chunks strictly between
@@ -283,9 +284,7 @@ __global__ __launch_bounds__(256, WF_MIN_WG) void xc_rows_fwd_wave(
     const void* __restrict__ src, const int64_t* __restrict__ job_off, int64_t row_stride,
     const float* __restrict__ mask, const float* __restrict__ mean_rstd, cfloat* __restrict__ T1,
     const cfloat* __restrict__ tw_row, XcGeom g, XcBox box, double* __restrict__ stats_acc,
-    const int2* __restrict__ chord, int lines16, const float* __restrict__ gain,
-    const float* __restrict__ job_sub) {
-  extern __shared__ __attribute__((aligned(16))) float4 park0[];  // lines16: [4 waves][nkx]
+    const int2* __restrict__ chord, const float* __restrict__ gain, const float* __restrict__ job_sub) {
   __shared__ __attribute__((aligned(16))) cfloat slabs[4][WF_SLAB];
   __shared__ __attribute__((aligned(16))) cfloat tab[WF_TWA + WF_TWB + 256];
   const cfloat* twA = tab;
@@ -372,11 +371,7 @@ __global__ __launch_bounds__(256, WF_MIN_WG) void xc_rows_fwd_wave(
       int ts = t;
       wf_pin(ts, X[0][0].x);  // addresses: computed here, not carried across rows
       const WfLane L = wf_lane(ts);
-      // lines16: the first round's bins wait in their own LDS area (park0, dynamic) until the second
-      // round is done, and T1[job][kx][16 rows] goes out as whole 128-byte lines (two 64-byte halves
-      // written 10 us apart merged in L2 only most of the time: 0.55 GB written for a 0.40 GB T1)
-      const bool hold = lines16 && nrows == 4 && rr == 1;
-      float4* park = hold ? park0 + wv * g.nkx : reinterpret_cast<float4*>(slab);  // [kx] = {even row, odd row}
+      float4* park = reinterpret_cast<float4*>(slab);  // [kx] = {even row, odd row}
 #pragma unroll
       for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -384,47 +379,37 @@ __global__ __launch_bounds__(256, WF_MIN_WG) void xc_rows_fwd_wave(
           const int k = L.kbin[s] + 256 * k3;
           if (k < g.nkx) park[k] = make_float4(Xe[s][k3].x, Xe[s][k3].y, X[s][k3].x, X[s][k3].y);
         }
-      if (!hold) {  // workgroup-uniform
-        __syncthreads();
-        int tj = threadIdx.x;
-        wf_pin(tj, X[0][0].y);
-        const float4* parked = reinterpret_cast<const float4*>(&slabs[0][0]);
-        if (lines16 && nrows == 4) {
-          for (int j = tj; j < 8 * g.nkx; j += 256) {  // 8 lanes = the 128 bytes of one kx
-            const int kx = j >> 3, pc = j & 7, w = pc & 3;
-            const float4 v = (pc >> 2) ? parked[w * (WF_SLAB / 2) + kx] : park0[w * g.nkx + kx];
-            *reinterpret_cast<float4*>(out + (int64_t)kx * g.ny + r16 + 2 * pc) = v;
-          }
-        } else {
-          const int r8 = r16 + (rr >> 1) * 8;
-          // 4 lanes = the 64 bytes of one kx; nkx <= 256 KEEP, so at most 4 KEEP pieces per thread: all the
-          // LDS reads first, then the stores (one LDS latency per round instead of one per piece).  The reads are
-          // unconditional (j < 2048: always inside slabs[][]; only the store is guarded): read under `j < 4 nkx`
-          // the 16 values were undefined on the other path and the compiler kept them alive round the whole row
-          // loop -- 16 VGPRs in every variant, and the scratch of the statistics variants at the 256 limit
-          typedef float f4 __attribute__((ext_vector_type(4)));
+      __syncthreads();
+      int tj = threadIdx.x;
+      wf_pin(tj, X[0][0].y);
+      const float4* parked = reinterpret_cast<const float4*>(&slabs[0][0]);
+      const int r8 = r16 + (rr >> 1) * 8;
+      // 4 lanes = the 64 bytes of one kx; nkx <= 256 KEEP, so at most 4 KEEP pieces per thread: all the
+      // LDS reads first, then the stores (one LDS latency per round instead of one per piece).  The reads are
+      // unconditional (j < 2048: always inside slabs[][]; only the store is guarded): read under `j < 4 nkx`
+      // the 16 values were undefined on the other path and the compiler kept them alive round the whole row
+      // loop -- 16 VGPRs in every variant, and the scratch of the statistics variants at the 256 limit
+      typedef float f4 __attribute__((ext_vector_type(4)));
 #pragma unroll
-          for (int half = 0; half < KEEP; ++half) {  // four pieces (16 registers) at a time
-            float4 pv[4];
+      for (int half = 0; half < KEEP; ++half) {  // four pieces (16 registers) at a time
+        float4 pv[4];
 #pragma unroll
-            for (int it = 0; it < 4; ++it) {
-              const int j = tj + 256 * (4 * half + it);
-              pv[it] = parked[(j & 3) * (WF_SLAB / 2) + (j >> 2)];
-            }
+        for (int it = 0; it < 4; ++it) {
+          const int j = tj + 256 * (4 * half + it);
+          pv[it] = parked[(j & 3) * (WF_SLAB / 2) + (j >> 2)];
+        }
 #pragma unroll
-            for (int it = 0; it < 4; ++it) {
-              const int j = tj + 256 * (4 * half + it);
-              if (j < 4 * g.nkx) {
-                const int kx = j >> 2, w = j & 3;
-                // T1 is written once here and read once by K2, 0.4 GB later: non-temporal (K1 0.465 -> 0.455 ms)
-                const f4 v = {pv[it].x, pv[it].y, pv[it].z, pv[it].w};
-                __builtin_nontemporal_store(v, reinterpret_cast<f4*>(out + (int64_t)kx * g.ny + r8 + 2 * w));
-              }
-            }
+        for (int it = 0; it < 4; ++it) {
+          const int j = tj + 256 * (4 * half + it);
+          if (j < 4 * g.nkx) {
+            const int kx = j >> 2, w = j & 3;
+            // T1 is written once here and read once by K2, 0.4 GB later: non-temporal (K1 0.465 -> 0.455 ms)
+            const f4 v = {pv[it].x, pv[it].y, pv[it].z, pv[it].w};
+            __builtin_nontemporal_store(v, reinterpret_cast<f4*>(out + (int64_t)kx * g.ny + r8 + 2 * w));
           }
         }
-        __syncthreads();
       }
+      __syncthreads();
     } else {
 #pragma unroll
       for (int s = 0; s < 4; ++s)
@@ -466,21 +451,13 @@ int k1_wave_launch(K1WaveVariant v, int raw, const void* src, const int64_t* job
                    const float* mask, const float* mean_rstd, void* T1, const void* tw_row, int njobs, const XcGeom& g,
                    const XcBox& b, double* stats_acc, const int* row_chord, const float* gain, const float* job_sub,
                    void* stream) {
-  // Whole 128-byte lines of T1 (16 rows per kx) when the first round's bins fit next to the slabs with two
-  // workgroups per CU still resident, and every 16-row piece is line-aligned.  OFF: it saves the 0.15 GB of
-  // write amplification (one stream: 2.00 -> 1.97 ms per 40 x 4096^2 step) but its 26 KB of extra LDS per
-  // workgroup keeps the warp's tiles of the other stream out of the CU: 1.74 -> 1.84 ms per step under the
-  // two-stream overlap.  It also needs WF_ROWS_PER_WG == 16.
-  constexpr bool K1_LINES16 = false;
-  const size_t park_bytes = (size_t)4 * g.nkx * 16;
-  const int lines16 = !raw && K1_LINES16 && WF_ROWS_PER_WG == 16 && (g.ny % 16) == 0 && park_bytes <= 27 * 1024 &&
-                      (reinterpret_cast<uintptr_t>(T1) & 127) == 0;
-  const size_t dyn = lines16 ? park_bytes : 0;
+  // fp16 samples and chord-clamped inner chunks come with statistics only (mc_xc_rows_forward takes neither fp16
+  // samples nor a chord table): without statistics there is no such kernel
+  if (!raw && !stats_acc && (v.loads == K1_LOADS_HALF || v.loads == K1_LOADS_INNER_CHORD)) return MC_ERR_UNSUPPORTED;
   auto launch = [&](auto kernel) {
-    if (dyn) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    hipLaunchKernelGGL(kernel, wave_rows_grid(g, njobs), dim3(256), dyn, (hipStream_t)stream, src, job_off, row_stride,
+    hipLaunchKernelGGL(kernel, wave_rows_grid(g, njobs), dim3(256), 0, (hipStream_t)stream, src, job_off, row_stride,
                        mask, mean_rstd, (cfloat*)T1, (const cfloat*)tw_row, g, b, stats_acc, (const int2*)row_chord,
-                       lines16, gain, job_sub);
+                       gain, job_sub);
   };
   mc_pick(v.keep1, [&](auto keep1) {
     constexpr int KEEP = decltype(keep1)::value ? 1 : 2;
@@ -493,8 +470,12 @@ int k1_wave_launch(K1WaveVariant v, int raw, const void* src, const int64_t* job
     mc_pick(stats_acc != nullptr, [&](auto stats) {
       constexpr bool ST = decltype(stats)::value;
       switch (v.loads) {
-        case K1_LOADS_HALF: launch(xc_rows_fwd_wave<KEEP, ST, 0, 16, true, true>); break;
-        case K1_LOADS_INNER_CHORD: launch(xc_rows_fwd_wave<KEEP, ST, 1, 15, true>); break;
+        case K1_LOADS_HALF:
+          if constexpr (ST) launch(xc_rows_fwd_wave<KEEP, ST, 0, 16, true, true>);
+          break;
+        case K1_LOADS_INNER_CHORD:
+          if constexpr (ST) launch(xc_rows_fwd_wave<KEEP, ST, 1, 15, true>);
+          break;
         case K1_LOADS_INNER: launch(xc_rows_fwd_wave<KEEP, ST, 1, 15, false>); break;
         default: launch(xc_rows_fwd_wave<KEEP, ST, 0, 16, true>); break;
       }

@@ -109,7 +109,7 @@ def central_box_stats(img: torch.Tensor, frac_low=0.25, frac_high=0.75) -> torch
     acc = torch.empty(2, dtype=torch.float64, device=img.device)
     out3 = torch.empty(3, dtype=torch.float32, device=img.device)
     check(lib.mc_central_box_stats_t(ptr(img), storage_of(img), t, h, w, hl, hu, wl, wu, ptr(acc), ptr(out3),
-                                     stream_ptr(img.device)), "mc_central_box_stats")
+                                     stream_ptr(img.device)), "mc_central_box_stats_t")
     return out3
 
 

@@ -117,7 +117,7 @@ def rigid_tables(img, lattices, pixel_spacing):
     # phase 1 never touches the frames (only their geometry matters): tagged fp32 so that fp16 stacks of
     # any row length get their tables here, whichever kernel resamples them later
     check(lib.mc_warp_rigid_phase_t(ptr(img), E.STORE_F32, t, h, w, ptr(shifts_px), ptr(scratch), None, None, 1,
-                                    stream_ptr(dev)), "mc_warp_rigid_phase")
+                                    stream_ptr(dev)), "mc_warp_rigid_phase_t")
     return shifts_px, scratch
 
 
@@ -164,11 +164,11 @@ def warp(img, lattices, pixel_spacing, want_frames=True, want_sum=False, rigid=F
             shifts_px = rigid_shifts_px(lattices, pixel_spacing)
             scratch = _rigid_scratch(lib, t, h, w, dev)
             args = (ptr(img), E.storage_of(img), t, h, w, ptr(shifts_px), ptr(scratch), ptr(frames), ptr(total))
-            check(lib.mc_warp_rigid_phase_t(*args, 0, stream_ptr(dev)), "mc_warp_rigid")
+            check(lib.mc_warp_rigid_phase_t(*args, 0, stream_ptr(dev)), "mc_warp_rigid_phase_t")
             return frames, total
         shifts_px, scratch = tables
         args = (ptr(img), E.storage_of(img), t, h, w, ptr(shifts_px), ptr(scratch), ptr(frames), ptr(total))
-        run = lambda: check(lib.mc_warp_rigid_phase_t(*args, 2, stream_ptr(dev)), "mc_warp_rigid_phase")
+        run = lambda: check(lib.mc_warp_rigid_phase_t(*args, 2, stream_ptr(dev)), "mc_warp_rigid_phase_t")
         if E.RIGID_KERNEL_HOOK is None:
             run()
         else:  # instrumentation: the hook brackets the resampling kernel alone (bench.py)
@@ -181,9 +181,9 @@ def warp(img, lattices, pixel_spacing, want_frames=True, want_sum=False, rigid=F
     if rc == -2 and img.dtype != torch.float32:
         # fp16 frames outside the LDS-staged kernel's shapes (row length not a multiple of 8, dense
         # lattice): widen once and take the fp32 kernels
-        rc = lib.mc_warp_frames(ptr(img.float()), t, h, w, ptr(lattices), GH, GW, float(pixel_spacing),
-                                ptr(scratch), ptr(frames), ptr(total), stream_ptr(dev))
-    check(rc, "mc_warp_frames")
+        rc = lib.mc_warp_frames_t(ptr(img.float()), E.STORE_F32, t, h, w, ptr(lattices), GH, GW, float(pixel_spacing),
+                                  ptr(scratch), ptr(frames), ptr(total), stream_ptr(dev))
+    check(rc, "mc_warp_frames_t")
     return frames, total
 
 

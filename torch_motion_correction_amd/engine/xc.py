@@ -31,13 +31,13 @@ def _k2(lib, g, dev, T1, filt, S, tw_col, n, st):
 
 
 def _wave_rows_geometry(g):
-    """The geometry of the wave-per-row patch kernels (mc_xc_rows_forward_dual*): rows of 1024 samples.
+    """The geometry of the wave-per-row patch kernels (mc_xc_rows_forward_dual_*): rows of 1024 samples.
     A shortcut: the authority is wave512_shape (csrc/xc_rows_fwd.hip)."""
     return g.W == 1024 and g.nkx <= 128 and g.ny % 8 == 0
 
 
 def _wave512_ok(g, job_expo, use_mask, min_expo):
-    """Patch rows of 1024 samples can take the wave-per-row K1 (mc_xc_rows_forward_dual):
+    """Patch rows of 1024 samples can take the wave-per-row K1 (mc_xc_rows_forward_dual_t):
     needs the mask and per-job exponents that are all >= 1 (`min_expo`, known on the host)."""
     return (_wave_rows_geometry(g) and use_mask and job_expo is not None
             and min_expo is not None and min_expo >= 1)
@@ -88,7 +88,7 @@ def _forward_spectra(src, job_off, row_stride, job_expo, pl, stats, use_mask=Tru
                                                 ptr(expo_b), ptr(pl.mask), ptr(stats), ptr(T1), ptr(T1b),
                                                 ptr(pl.tw_row), n, g,
                                                 ptr(pl.chord) if E.USE_ROW_CHORDS else None, st),
-                  "mc_xc_rows_forward_dual")
+                  "mc_xc_rows_forward_dual_t")
         else:
             check(_k1(lib, g, dev, src, off, row_stride, expo, pl.mask if use_mask else None, stats, T1,
                       pl.tw_row, n, st), "xc rows forward")
@@ -208,7 +208,7 @@ def _global_spectra(img, pl, after_k1=None):
     acc = torch.empty(128, dtype=torch.float64, device=dev)  # 64 x {sum, sumsq}
     m0 = torch.empty(3, dtype=torch.float32, device=dev)
     check(lib.mc_xc_provisional_mean_t(C.c_void_p(img.data_ptr() + img.element_size() * (hl * w + wl)),
-                                       E.storage_of(img), wu - wl, ptr(m0), st), "mc_xc_provisional_mean")
+                                       E.storage_of(img), wu - wl, ptr(m0), st), "mc_xc_provisional_mean_t")
     fix = torch.empty(2, dtype=torch.float32, device=dev)
     out3 = torch.empty(3, dtype=torch.float32, device=dev)
     T1 = torch.empty((t, g.nkx, g.ny, 2), dtype=torch.float32, device=dev)
@@ -217,7 +217,7 @@ def _global_spectra(img, pl, after_k1=None):
         check(lib.mc_xc_rows_forward_stats_t(ptr(img), E.storage_of(img), ptr(job_off), w, ptr(pl.mask), ptr(m0),
                                              ptr(T1), ptr(pl.tw_row), t, g, hl, hu, wl, wu, ptr(acc), ptr(fix),
                                              ptr(out3), ptr(_box_chords(pl, hl, hu, wl, wu)), st),
-              "mc_xc_rows_forward_stats")
+              "mc_xc_rows_forward_stats_t")
     except _lib.McorrUnsupported:
         # the C side decides which shapes read fp16 natively (row engine, alignment, geometry); the
         # predicate above is only a shortcut -- on disagreement widen once, as the warps do
