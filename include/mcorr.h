@@ -703,6 +703,24 @@ int mc_polyphase_dose_accumulate(const void* S, int nframes, int frame0, int tot
                                  float dose_per_frame, float voltage, int first, int last,
                                  void* stream);
 
+/* TIFF strips -> a raw movie: the strips of a multi-page TIFF, LZW-coded (compression 5, TIFF 6.0: MSB-first codes,
+ * early change; the rule is stated in csrc/tiff_lzw.h) or stored (compression 1), decoded into the contiguous
+ * (n_frames, h, row_bytes) bytes of `out`; row_bytes = w * bytes per sample, the sample type is the caller's view.
+ * data: the buffer that holds every strip (device), data_bytes its size.  offsets, nbytes (host): n_frames *
+ * strips_per_frame entries each, frame-major: strip k of frame f covers rows k * rows_per_strip .. of that frame and
+ * lies at offsets[f * strips_per_frame + k]; strips may lie anywhere in the buffer, in any order.  produced (device):
+ * one int per strip, the bytes written for it; anything but the size of its rows means a strip that ended early
+ * (cut short, malformed), the caller's error to report.  A strip reads its own bytes and writes its own rows only,
+ * whatever its bits say; bytes a strip holds beyond its rows are ignored.  scratch: 16 bytes per strip (device,
+ * 8-byte aligned).  One wavefront per strip.
+ * Before anything is launched: MC_ERR_ARG for null pointers, sizes < 1, rows_per_strip > h, a strips_per_frame other
+ * than ceil(h / rows_per_strip), a strip outside the buffer, a misaligned produced / scratch and a scratch that is
+ * too small; MC_ERR_UNSUPPORTED for any other compression, a strip whose decoded size is 2^31 bytes or more and 2^31
+ * strips or more. */
+int mc_tiff_decode(const unsigned char* data, long long data_bytes, const long long* offsets, const long long* nbytes,
+                   int n_frames, int strips_per_frame, int h, int row_bytes, int rows_per_strip, int compression,
+                   unsigned char* out, int* produced, void* scratch, long long scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,9 @@ SOURCES = [("xcg_rows_inv.hip", "xcg_rows_inv", []), ("xcg_cols_inv.hip", "xcg_c
            ("xc_refine_patches.hip", "xc_refine_patches", []), ("raw_accumulate.hip", "raw_accumulate", []),
            ("raw_group.hip", "raw_group", []), ("defect_fill.hip", "defect_fill", []),
            # EER event movies -> raw u8 movies, over eer.h
-           ("eer_render.hip", "eer_render", [])]
+           ("eer_render.hip", "eer_render", []),
+           # LZW / stored TIFF strips -> raw movies, over tiff_lzw.h
+           ("tiff_decode.hip", "tiff_decode", [])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 

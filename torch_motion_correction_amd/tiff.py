@@ -1,0 +1,318 @@
+"""LZW-compressed TIFF movies (K3 / K2 counting detectors) decoded into raw movies on the device.
+
+Counting detectors that do not write ``.eer`` write multi-page TIFF: one IFD per frame, strips of a few rows each,
+LZW compression (TIFF compression 5), typically 8-bit counts; the gain reference (``.gain``) is a float32 TIFF of the
+same container.  This module gives such a file a device route to the ``(t, h, w)`` tensor every raw route starts from:
+
+  read_tiff        a pure-Python walk of the file's IFD chain -> ``TiffMovie`` (the bytes and each frame's strips)
+  decode_tiff_raw  the strips decoded on the GPU, one wavefront per strip (mc_tiff_decode): the contiguous (t, h, w)
+                   movie of the file's sample type
+
+The result is a raw movie for every ``*_raw*`` function, ``RawStatistics`` and the pipelines, as the output of
+``render_eer_raw`` is.  The codec rule (TIFF 6.0 LZW: MSB-first codes, early change) is stated once, in
+csrc/tiff_lzw.h, and is pinned to files written by libtiff (tests/golden/tiff_lzw_libtiff.npz).
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import operator
+import os
+import struct
+from dataclasses import dataclass
+
+import torch
+
+from ._lib import check, device_scope, load, ptr, require_gpu, stream_ptr
+
+# the file's sample type -> (bytes per sample, the dtype of the decoded movie)
+_DTYPES = {torch.uint8: (1, torch.uint8), torch.int16: (2, torch.int16), torch.uint16: (2, torch.int16),
+           torch.float32: (4, torch.float32)}
+# (BitsPerSample, SampleFormat) -> the file's sample type
+_SAMPLES = {(8, 1): torch.uint8, (16, 2): torch.int16, (16, 1): torch.uint16, (32, 3): torch.float32}
+
+_TAG_NAMES = {256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: "Compression", 266: "FillOrder",
+              273: "StripOffsets", 277: "SamplesPerPixel", 278: "RowsPerStrip", 279: "StripByteCounts",
+              317: "Predictor", 322: "TileWidth", 323: "TileLength", 324: "TileOffsets", 325: "TileByteCounts",
+              339: "SampleFormat"}
+_INT_TYPES = {1: "B", 3: "H", 4: "I", 16: "Q"}  # TIFF types BYTE, SHORT, LONG, LONG8
+_ARRAY_TYPES = {3: "H", 4: "I", 16: "Q"}        # StripOffsets / StripByteCounts: SHORT, LONG, LONG8
+
+
+def _int(value, what, lo):
+    if isinstance(value, bool):
+        raise ValueError(f"{what} must be an int >= {lo}, got {value!r}")
+    try:
+        v = operator.index(value)
+    except TypeError:
+        raise ValueError(f"{what} must be an int >= {lo}, got {value!r}") from None
+    if v < lo:
+        raise ValueError(f"{what} must be an int >= {lo}, got {value!r}")
+    return v
+
+
+def _check_decode_args(data, offsets, nbytes, shape, rows_per_strip, compression, dtype):
+    """Every argument rule of decode_tiff_raw -> (flat offsets, flat nbytes, t, strips per frame, h, w, rows per strip)
+    as Python ints; ValueError otherwise."""
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError("data must be a 1-D uint8 tensor, got "
+                         f"{getattr(data, 'dtype', type(data).__name__)} {tuple(getattr(data, 'shape', ()))}")
+    try:
+        h, w = (operator.index(s) for s in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"shape must be the frames' (h, w), got {shape!r}") from None
+    if h < 1 or w < 1:
+        raise ValueError(f"shape must be the frames' (h, w), got {shape!r}")
+    if dtype not in _DTYPES:
+        raise ValueError(f"dtype must be torch.uint8, int16, uint16 (decoded to int16) or float32, got {dtype!r}")
+    if isinstance(compression, bool) or compression not in (1, 5):
+        raise ValueError(f"compression must be 5 (LZW) or 1 (none), got {compression!r}: deflate (8, 32946), JPEG "
+                         "(7) and the EER codes (65000 - 65002, see read_eer) are not decoded")
+    rps = min(_int(rows_per_strip, "rows_per_strip", 1), h)  # TIFF writers give 2^32 - 1 for "the whole frame"
+    row_bytes = w * _DTYPES[dtype][0]
+    if rps * row_bytes >= 2**31:
+        raise ValueError(f"rows_per_strip={rps} of {row_bytes} bytes: strips that decode to 2^31 bytes and more are "
+                         "not supported")
+    spf = (h + rps - 1) // rps
+    try:
+        offsets = [[_int(o, "an offset", 0) for o in f] for f in offsets]
+        nbytes = [[_int(n, "a byte count", 0) for n in f] for f in nbytes]
+    except TypeError:
+        raise ValueError("offsets and nbytes must be sequences, one per frame, of sequences of ints, one per "
+                         "strip") from None
+    if len(offsets) != len(nbytes) or not offsets:
+        raise ValueError(f"offsets and nbytes must name the same frames, at least one: got {len(offsets)} and "
+                         f"{len(nbytes)}")
+    if len(offsets) * spf >= 2**31:
+        raise ValueError(f"{len(offsets)} frames of {spf} strips: 2^31 strips and more are not supported")
+    total = int(data.numel())
+    for i, (fo, fn) in enumerate(zip(offsets, nbytes)):
+        if len(fo) != spf or len(fn) != spf:
+            raise ValueError(f"frame {i}: {len(fo)} offsets and {len(fn)} byte counts, but {h} rows in strips of "
+                             f"{rps} are {spf} strips")
+        for k, (o, n) in enumerate(zip(fo, fn)):
+            if o + n > total:
+                raise ValueError(f"frame {i}, strip {k}: offset {o}, {n} bytes leaves the {total} bytes of data")
+    flat_o = [o for f in offsets for o in f]
+    flat_n = [n for f in nbytes for n in f]
+    return flat_o, flat_n, len(offsets), spf, h, w, rps
+
+
+def _decode_strips(data, flat_o, flat_n, t, spf, h, row_bytes, rps, compression, device, out=None):
+    """The checked arguments decoded -> (the (t * h * row_bytes,) uint8 output, the per-strip bytes produced), both on
+    the device.  `out`: a buffer to decode into (the tests' guarded buffers)."""
+    dev = require_gpu(device if device is not None else data.device)
+    n = t * spf
+    with device_scope(dev):
+        buf = data.detach().to(dev).contiguous()
+        if buf.numel() == 0:  # strips without bytes: a pointer the library can take
+            buf = torch.zeros(8, dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(t * h * row_bytes, dtype=torch.uint8, device=dev)
+        assert out.dtype == torch.uint8 and out.numel() == t * h * row_bytes and out.device == dev
+        scratch = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        produced = torch.empty(n, dtype=torch.int32, device=dev)
+        off_c, nb_c = (C.c_int64 * n)(*flat_o), (C.c_int64 * n)(*flat_n)
+        check(load().mc_tiff_decode(ptr(buf), int(data.numel()), off_c, nb_c, t, spf, h, row_bytes, rps, compression,
+                                    ptr(out), ptr(produced), ptr(scratch), 8 * scratch.numel(), stream_ptr(dev)),
+              "mc_tiff_decode")
+    return out, produced
+
+
+def _expected(spf, h, row_bytes, rps):
+    """the bytes of each strip of one frame"""
+    return [min(rps, h - k * rps) * row_bytes for k in range(spf)]
+
+
+def decode_tiff_raw(data, offsets, nbytes, shape, rows_per_strip, compression=5, dtype=torch.uint8, device=None):
+    """TIFF strips decoded into a raw movie: the contiguous ``(t, h, w)`` tensor on the GPU whose frame ``f`` is the
+    strips ``offsets[f]`` put below one another, ``rows_per_strip`` rows each (the last strip of a frame holds the
+    rest).
+
+    ``data``: a 1-D uint8 tensor (CPU or GPU) that holds the strips anywhere in it, in any order, with anything
+    between them -- it may be the whole file.  ``offsets`` / ``nbytes``: one list per frame of one int per strip, the
+    strip's first byte and length in ``data``; every frame has ``ceil(h / rows_per_strip)`` strips (a
+    ``rows_per_strip`` above ``h`` means ``h``).  ``shape``: the frames' ``(h, w)``.  ``compression``: 5, TIFF 6.0
+    LZW (csrc/tiff_lzw.h states the rule), or 1, stored rows.  ``dtype`` names the file's samples: ``torch.uint8``,
+    ``torch.int16``, ``torch.float32`` (little-endian), or ``torch.uint16`` for unsigned 16-bit files, which are
+    returned as ``int16`` -- the raw routes' 16-bit type -- and raise ValueError if a sample is 32768 or more.
+
+    Exact: the decoder moves bytes.  A strip that gives fewer bytes than its rows need (cut short, a malformed code,
+    an early end-of-information) raises ValueError naming the first such frame and strip -- from the one
+    device-to-host read of the per-strip byte counts; bytes a strip holds beyond its rows are ignored, as libtiff
+    ignores them.  Every other argument rule, a strip outside ``data`` included, is a ValueError raised before any
+    device is touched.  The kernel reads no byte outside a strip and writes no byte outside that strip's rows,
+    whatever its bits say.
+
+    ``device``: the GPU to decode on (None: the device of ``data``, the current GPU for a CPU tensor)."""
+    flat_o, flat_n, t, spf, h, w, rps = _check_decode_args(data, offsets, nbytes, shape, rows_per_strip, compression,
+                                                           dtype)
+    size, out_dtype = _DTYPES[dtype]
+    out, produced = _decode_strips(data, flat_o, flat_n, t, spf, h, w * size, rps, compression, device)
+    got = produced.cpu().tolist()
+    want = _expected(spf, h, w * size, rps)
+    for s, g in enumerate(got):
+        if g != want[s % spf]:
+            raise ValueError(f"frame {s // spf}, strip {s % spf}: its {flat_n[s]} bytes decode to {g} of the "
+                             f"{want[s % spf]} bytes of its rows: not a well-formed "
+                             f"{'LZW' if compression == 5 else 'stored'} strip")
+    movie = out.view(out_dtype).view(t, h, w)
+    if dtype == torch.uint16 and bool((movie < 0).any()):
+        raise ValueError("an unsigned 16-bit sample is 32768 or more: the movie does not fit the raw routes' int16")
+    return movie
+
+
+@dataclass
+class TiffMovie:
+    """A TIFF movie as ``read_tiff`` found it: ``data`` (1-D uint8, the whole file), ``offsets`` / ``nbytes`` (one
+    list of ints per frame, one int per strip), ``shape`` (h, w), ``rows_per_strip``, ``compression`` (1 or 5) and
+    ``dtype`` (the file's sample type: torch.uint8, int16, uint16 or float32)."""
+
+    data: torch.Tensor
+    offsets: list
+    nbytes: list
+    shape: tuple
+    rows_per_strip: int
+    compression: int
+    dtype: torch.dtype
+
+    def decode(self, device=None):
+        """``decode_tiff_raw`` of this movie."""
+        return decode_tiff_raw(self.data, self.offsets, self.nbytes, self.shape, self.rows_per_strip,
+                               compression=self.compression, dtype=self.dtype, device=device)
+
+
+def read_tiff(path):
+    """A TIFF movie -> ``TiffMovie``: a walk of the TIFF (magic 42) or BigTIFF (magic 43) IFD chain, in either byte
+    order, in plain Python; no decoder is involved.  Every IFD is one frame of one or more strips and must give
+    ImageWidth, ImageLength, Compression, StripOffsets and StripByteCounts (arrays of SHORT, LONG or LONG8, inline or
+    out of line).  Absent tags mean BitsPerSample 1 (refused), SamplesPerPixel 1, RowsPerStrip = ImageLength,
+    SampleFormat 1, Predictor 1, FillOrder 1.
+
+    Accepted samples: 8-bit unsigned (uint8), 16-bit signed (int16), 16-bit unsigned (uint16: decoded to int16,
+    refused at decode time if a sample is 32768 or more) and 32-bit float (float32, the gain file); multi-byte
+    samples need a little-endian (``II``) file.  Compression 5 (LZW) and 1 (none).  Everything else -- deflate, JPEG,
+    the EER codes, Predictor 2 or 3, FillOrder 2, more than one sample per pixel, tiles, other bit depths, frames that
+    differ from the first, a strip count other than ceil(h / RowsPerStrip), a strip or an IFD that leaves the file, a
+    looping chain, an empty file -- raises ValueError with the frame and the tag named.
+
+    The Orientation tag is ignored: rows are returned in stored order."""
+    with open(path, "rb") as fh:
+        raw = bytearray(os.fstat(fh.fileno()).st_size)  # writable, so that the tensor below shares it
+        size = fh.readinto(raw)
+    if size != len(raw):
+        del raw[size:]
+
+    def fail(msg):
+        raise ValueError(f"{path}: {msg}")
+
+    if size == 0:
+        fail("the file is empty")
+    if size < 8 or raw[:2] not in (b"II", b"MM"):
+        fail("not a TIFF file (byte order mark)")
+    bo = "<" if raw[:2] == b"II" else ">"
+    magic = struct.unpack_from(bo + "H", raw, 2)[0]
+    if magic == 42:
+        entry_size, count_fmt, off_fmt = 12, "H", "I"
+        ifd = struct.unpack_from(bo + "I", raw, 4)[0]
+    elif magic == 43:
+        if size < 16 or struct.unpack_from(bo + "HH", raw, 4) != (8, 0):
+            fail("BigTIFF header with an offset size other than 8")
+        entry_size, count_fmt, off_fmt = 20, "Q", "Q"
+        ifd = struct.unpack_from(bo + "Q", raw, 8)[0]
+    else:
+        fail(f"TIFF magic {magic} is neither 42 (TIFF) nor 43 (BigTIFF)")
+    csz, osz = struct.calcsize(count_fmt), struct.calcsize(off_fmt)
+    frames = []  # (offsets, nbytes) per frame
+
+    def values(tag, typ, count, at, types):
+        """the integers of an IFD entry whose value field starts at `at`"""
+        where = f"frame {len(frames)}: {_TAG_NAMES[tag]}"
+        if typ not in types:
+            fail(f"{where} has TIFF type {typ}, not one of {sorted(types)} (unsigned integers)")
+        if count < 1:
+            fail(f"{where} has no value")
+        width = struct.calcsize(types[typ])
+        if width * count > osz:  # out of line
+            at = struct.unpack_from(bo + off_fmt, raw, at)[0]
+            if at + width * count > size:
+                fail(f"{where}: its {count} values at offset {at} leave the file of {size} bytes")
+        return list(struct.unpack_from(f"{bo}{count}{types[typ]}", raw, at))
+
+    first, seen = None, set()
+    while ifd:
+        i = len(frames)
+        if ifd in seen:
+            fail(f"frame {i}: the IFD chain loops")
+        seen.add(ifd)
+        if ifd + csz > size:
+            fail(f"frame {i}: its IFD lies outside the file")
+        n_entries = struct.unpack_from(bo + count_fmt, raw, ifd)[0]
+        end = ifd + csz + n_entries * entry_size
+        if end + osz > size:
+            fail(f"frame {i}: its IFD lies outside the file")
+        tags = {}
+        for k in range(n_entries):
+            at = ifd + csz + k * entry_size
+            tag, typ = struct.unpack_from(bo + "HH", raw, at)
+            if tag not in _TAG_NAMES:
+                continue  # Orientation among them: rows stay in stored order
+            if 322 <= tag <= 325:
+                fail(f"frame {i}: {_TAG_NAMES[tag]} ({tag}): tiled TIFF is not supported, only strips")
+            count = struct.unpack_from(bo + off_fmt, raw, at + 4)[0]
+            if tag in (273, 279):
+                tags[tag] = values(tag, typ, count, at + 4 + osz, _ARRAY_TYPES)
+            else:
+                v = values(tag, typ, count, at + 4 + osz, _INT_TYPES)
+                if len(v) != 1:
+                    fail(f"frame {i}: {_TAG_NAMES[tag]} has {len(v)} values"
+                         + ("; SamplesPerPixel other than 1 is not supported" if tag in (258, 339) else ""))
+                tags[tag] = v[0]
+        for tag in (256, 257, 259, 273, 279):
+            if tag not in tags:
+                fail(f"frame {i}: {_TAG_NAMES[tag]} is missing")
+        h, w, comp = tags[257], tags[256], tags[259]
+        if h < 1 or w < 1:
+            fail(f"frame {i}: ImageLength x ImageWidth {(h, w)} is empty")
+        if comp not in (1, 5):
+            fail(f"frame {i}: Compression {comp} is not supported: 5 (LZW) and 1 (none) are; 8 / 32946 (deflate), 7 "
+                 "(JPEG) and 65000 - 65002 (EER, see read_eer) are not")
+        if tags.get(317, 1) != 1:
+            fail(f"frame {i}: Predictor {tags[317]} is not supported (only 1, none)")
+        if tags.get(266, 1) != 1:
+            fail(f"frame {i}: FillOrder {tags[266]} is not supported (only 1, MSB first)")
+        if tags.get(277, 1) != 1:
+            fail(f"frame {i}: SamplesPerPixel {tags[277]} is not supported (only 1)")
+        bits, fmt = tags.get(258, 1), tags.get(339, 1)
+        if (bits, fmt) not in _SAMPLES:
+            fail(f"frame {i}: BitsPerSample {bits} with SampleFormat {fmt} is not supported: 8-bit unsigned, 16-bit "
+                 "signed or unsigned and 32-bit float samples are")
+        if bits > 8 and bo == ">":
+            fail(f"frame {i}: BitsPerSample {bits} in a big-endian (MM) file is not supported")
+        rps = min(tags.get(278, h), h)
+        if rps < 1:
+            fail(f"frame {i}: RowsPerStrip {tags[278]}")
+        this = (h, w, comp, _SAMPLES[bits, fmt], rps)
+        if first is None:
+            first = this
+        else:
+            for a, b, name in zip(this, first, ("ImageLength", "ImageWidth", "Compression",
+                                                "BitsPerSample / SampleFormat", "RowsPerStrip")):
+                if a != b:
+                    fail(f"frame {i}: {name} {a} differs from the first frame's {b}")
+        spf = (h + rps - 1) // rps
+        if len(tags[273]) != spf or len(tags[279]) != spf:
+            fail(f"frame {i}: StripOffsets has {len(tags[273])} and StripByteCounts {len(tags[279])} values, but "
+                 f"{h} rows in strips of {rps} are {spf} strips")
+        for k, (o, n) in enumerate(zip(tags[273], tags[279])):
+            if o + n > size:
+                fail(f"frame {i}, strip {k}: StripOffsets + StripByteCounts = {o + n} leaves the file of {size} "
+                     "bytes")
+        frames.append((tags[273], tags[279]))
+        ifd = struct.unpack_from(bo + off_fmt, raw, end)[0]
+    if not frames:
+        fail("the file holds no frame (no IFD)")
+    h, w, comp, dtype, rps = first
+    data = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+    return TiffMovie(data=data, offsets=[f[0] for f in frames], nbytes=[f[1] for f in frames], shape=(h, w),
+                     rows_per_strip=rps, compression=comp, dtype=dtype)
