@@ -721,6 +721,31 @@ int mc_tiff_decode(const unsigned char* data, long long data_bytes, const long l
                    int n_frames, int strips_per_frame, int h, int row_bytes, int rows_per_strip, int compression,
                    unsigned char* out, int* produced, void* scratch, long long scratch_bytes, void* stream);
 
+/* MRC2014 sample rows -> a raw movie: the t * h rows of an MRC file's payload, which starts `offset` bytes into
+ * `data` (device, data_bytes long; the payload has no alignment), decoded into the contiguous (t, h, w) elements of
+ * `out`.  mode 0: 8-bit, copied to uint8 when unsigned_bytes, else widened from signed to int16; modes 1, 6, 12:
+ * 2-byte samples copied as they are (byte-swapped when swap); mode 2: float32 (4-byte swap when swap); mode 101:
+ * 4-bit samples, a row of (w + 1) / 2 bytes, pixel 2k the low and pixel 2k + 1 the high nibble of byte k, to uint8
+ * 0..15 (the rule is stated in csrc/mrc.h).  swap is ignored for 1-byte and 4-bit samples, unsigned_bytes for every
+ * mode but 0.  flip_rows: row r of every output frame is row h - 1 - r of the file's frame.  A row's threads read
+ * the bytes of that row only and write its elements only; rows are cut at the 16-byte boundaries of the source.
+ * Before anything is launched: MC_ERR_ARG for null pointers, data == out, sizes < 1, a negative offset or
+ * data_bytes, offset + t * h * row_bytes > data_bytes, a mode other than 0, 1, 2, 6, 12, 101, a swap, unsigned_bytes
+ * or flip_rows other than 0 or 1 and an `out` misaligned for its element type; MC_ERR_UNSUPPORTED for
+ * h * w >= 2^31. */
+int mc_mrc_decode(const unsigned char* data, long long data_bytes, long long offset, int t, int h, int w, int mode,
+                  int swap, int unsigned_bytes, int flip_rows, void* out, void* stream);
+
+/* Quarter turns and flips of n images: out = numpy.rot90(in, rot90, axes=(-2, -1)) (counter-clockwise), then
+ * flip 1 ("ud": the rows' order reversed) or flip 2 ("lr": every row reversed), flip 0 for neither.  in: (n, h, w)
+ * elements of elem_bytes = 1, 2 or 4 bytes (device); out: (n, h, w) for even rot90, (n, w, h) for odd, the same
+ * element size, a different buffer.  Exact: elements are moved.  Even rot90 is a row copy, odd a tiled transpose
+ * through LDS (128-byte x 128-byte tiles); the flip is folded into the destination index.
+ * Before anything is launched: MC_ERR_ARG for null pointers, in == out, sizes < 1, an elem_bytes other than 1, 2, 4,
+ * rot90 outside 0..3, flip outside 0..2 and an `in` or `out` misaligned for its element size; MC_ERR_UNSUPPORTED for
+ * h * w >= 2^31. */
+int mc_raw_orient(const void* in, int elem_bytes, int n, int h, int w, int rot90, int flip, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,8 @@ SOURCES = [("xcg_rows_inv.hip", "xcg_rows_inv", []), ("xcg_cols_inv.hip", "xcg_c
            ("polyphase.hip", "polyphase", []), ("plan_tables.hip", "plan_tables", []), ("xc_refine.hip", "xc_refine", []),
            ("xc_refine_patches.hip", "xc_refine_patches", []), ("raw_accumulate.hip", "raw_accumulate", []),
            ("raw_group.hip", "raw_group", []), ("defect_fill.hip", "defect_fill", []),
+           # MRC sample rows -> raw movies, over mrc.h; quarter turns and flips of raw images (the gain)
+           ("mrc_decode.hip", "mrc_decode", []), ("raw_orient.hip", "raw_orient", []),
            # EER event movies -> raw u8 movies, over eer.h
            ("eer_render.hip", "eer_render", []),
            # LZW / stored TIFF strips -> raw movies, over tiff_lzw.h

@@ -99,6 +99,8 @@ SIGNATURES = {
     "mc_gain_fill_defects": [vp, i32, i32, vp, vp, vp, i32, i32, vp],
     "mc_eer_render": [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp],
     "mc_tiff_decode": [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp],
+    "mc_mrc_decode": [vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "mc_raw_orient": [vp, i32, i32, i32, i32, i32, i32, vp, vp],
     "mc_condition_movie": [vp, i32, vp, i32, i64, i32, vp, vp, vp],
     "mc_raw_movie_stats": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "mc_xc_rows_forward_raw": [vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, GP, vp, vp],
