@@ -721,6 +721,30 @@ int mc_tiff_decode(const unsigned char* data, long long data_bytes, const long l
                    int n_frames, int strips_per_frame, int h, int row_bytes, int rows_per_strip, int compression,
                    unsigned char* out, int* produced, void* scratch, long long scratch_bytes, void* stream);
 
+/* A raw movie -> TIFF LZW strips (compression 5; the encoder rule -- a leading Clear, greedy longest match, Clear once
+ * the decoder's next code reaches 4093, EOI -- and the size bound are stated in csrc/tiff_lzw_encode.h).
+ * mc_tiff_encode_slot_bytes: *slot_bytes = an upper bound, a multiple of 16, on the stream of a strip of strip_bytes
+ * bytes.  MC_ERR_ARG for a null pointer or a negative size, MC_ERR_UNSUPPORTED for 2^31 bytes or more.
+ * mc_tiff_encode: src (device) is the contiguous (n_frames, h, row_bytes) bytes of the movie; strip k of frame f is
+ * rows k * rows_per_strip .. of that frame (the last strip of a frame holds the rest), and strip s of the frame-major
+ * list is encoded, one wavefront per strip, into slots[s * slot_bytes ..] (device; slots_bytes is the whole buffer's
+ * size) and gives produced[s] (device, 64-bit), the bytes of its stream.  A strip's wavefront reads its rows only and
+ * writes its slot only, never more than slot_bytes of it.  Before anything is launched: MC_ERR_ARG for null pointers,
+ * sizes < 1, rows_per_strip > h, a produced not aligned to 8 or a slots not aligned to 16 bytes, a slot_bytes that is
+ * no multiple of 16 or below mc_tiff_encode_slot_bytes(rows_per_strip * row_bytes), and a slots_bytes below n_frames
+ * * ceil(h / rows_per_strip) * slot_bytes; MC_ERR_UNSUPPORTED for a compression other than 5 (stored strips are the
+ * movie's bytes), a strip of 2^31 bytes or more and 2^31 strips or more.
+ * mc_tiff_pack: payload[offsets[s] .. offsets[s] + produced[s]) = slots[s * slot_bytes ..] for the n_strips strips
+ * (all device; offsets, 64-bit, is the exclusive scan of produced).  Nothing is written outside that range, clipped to
+ * slot_bytes and to payload_bytes, whatever the two arrays hold.  MC_ERR_ARG for null pointers, sizes < 1 and an
+ * offsets or produced not aligned to 8 bytes; MC_ERR_UNSUPPORTED for 2^31 strips or more. */
+int mc_tiff_encode_slot_bytes(long long strip_bytes, long long* slot_bytes /*host*/);
+int mc_tiff_encode(const unsigned char* src, int n_frames, int h, int row_bytes, int rows_per_strip, int compression,
+                   unsigned char* slots, long long slot_bytes, long long slots_bytes, long long* produced,
+                   void* stream);
+int mc_tiff_pack(const unsigned char* slots, long long slot_bytes, const long long* offsets, const long long* produced,
+                 long long n_strips, unsigned char* payload, long long payload_bytes, void* stream);
+
 /* MRC2014 sample rows -> a raw movie: the t * h rows of an MRC file's payload, which starts `offset` bytes into
  * `data` (device, data_bytes long; the payload has no alignment), decoded into the contiguous (t, h, w) elements of
  * `out`.  mode 0: 8-bit, copied to uint8 when unsigned_bytes, else widened from signed to int16; modes 1, 6, 12:

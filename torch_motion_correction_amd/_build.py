@@ -47,8 +47,9 @@ SOURCES = [("xcg_rows_inv.hip", "xcg_rows_inv", []), ("xcg_cols_inv.hip", "xcg_c
            ("mrc_decode.hip", "mrc_decode", []), ("raw_orient.hip", "raw_orient", []),
            # EER event movies -> raw u8 movies, over eer.h
            ("eer_render.hip", "eer_render", []),
-           # LZW / stored TIFF strips -> raw movies, over tiff_lzw.h
-           ("tiff_decode.hip", "tiff_decode", [])]
+           # raw movies -> LZW TIFF strips, over tiff_lzw_encode.h; LZW / stored TIFF strips -> raw movies, over
+           # tiff_lzw.h
+           ("tiff_encode.hip", "tiff_encode", []), ("tiff_decode.hip", "tiff_decode", [])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 

@@ -99,6 +99,9 @@ SIGNATURES = {
     "mc_gain_fill_defects": [vp, i32, i32, vp, vp, vp, i32, i32, vp],
     "mc_eer_render": [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp],
     "mc_tiff_decode": [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp],
+    "mc_tiff_encode_slot_bytes": [i64, C.POINTER(C.c_int64)],
+    "mc_tiff_encode": [vp, i32, i32, i32, i32, i32, vp, i64, i64, vp, vp],
+    "mc_tiff_pack": [vp, i64, vp, vp, i64, vp, i64, vp],
     "mc_mrc_decode": [vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "mc_raw_orient": [vp, i32, i32, i32, i32, i32, i32, vp, vp],
     "mc_condition_movie": [vp, i32, vp, i32, i64, i32, vp, vp, vp],
