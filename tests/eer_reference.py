@@ -1,6 +1,6 @@
 """Test-side restatement of the EER codec rule (csrc/eer.h) in numpy and Python integers: an encoder, the sequential
-decoder, a renderer, and a minimal writer for the TIFF and BigTIFF containers.  Nothing here is imported by the
-package; scripts/eer_render_time.py reuses the encoder.
+decoder, a renderer, and the EER flavour of the container writer (tests/tiff_files.py).  Nothing here is imported by
+the package; scripts/eer_render_time.py reuses the encoder.
 
 The rule.  A frame of a detector with N = h * w pixels is a little-endian bit stream (bit k of the stream is bit
 k & 7 of byte k >> 3).  With bit = 0, n = 0:
@@ -13,9 +13,9 @@ k & 7 of byte k >> 3).  With bit = 0, n = 0:
 and decoding also stops when the next symbol would begin at or after bit 8 * nbytes; bits beyond the strip read as
 zero.  A well-formed stream stops with n == N."""
 
-import struct
-
 import numpy as np
+
+import tiff_files
 
 RUN_MAX = 127
 
@@ -115,84 +115,15 @@ def random_frame(rng, n_pixels, density):
 
 
 def lay_out(strips, order, lead=1, gap=3, odd=True):
-    """The strips laid into one buffer in `order`, `gap` bytes of 0xff between them, every strip at an odd offset when
-    `odd` -> (bytes, offsets, nbytes) with offsets / nbytes in frame order."""
-    buf = bytearray(b"\xff" * lead)
-    offsets = [0] * len(strips)
-    for i in order:
-        buf += b"\xff" * gap
-        if odd and len(buf) % 2 == 0:
-            buf += b"\xff"
-        offsets[i] = len(buf)
-        buf += strips[i]
-    buf += b"\xff" * gap
-    return bytes(buf), offsets, [len(s) for s in strips]
-
-
-# ------------------------------------------------------------------ containers
-
-_SIZES = {1: 1, 3: 2, 4: 4, 16: 8}
-_CODES = {1: "B", 3: "H", 4: "I", 16: "Q"}
+    """tiff_files.lay_out for frames of one strip -> (bytes, offsets, nbytes) with offsets / nbytes in frame order."""
+    buf, offsets, nbytes = tiff_files.lay_out([[s] for s in strips], order, lead, gap, odd)
+    return buf, [o[0] for o in offsets], [n[0] for n in nbytes]
 
 
 def write_tiff(path, strips, shape, big=False, compression=65001, order=None, overrides=None, byte_order="<"):
-    """A minimal TIFF (magic 42) or BigTIFF (magic 43): one IFD and one strip per frame.  The strips are written in
-    `order` (default: reversed), each at an odd offset, each followed by the IFD of the same frame, so that IFD
-    bytes lie between strips and the IFD chain jumps back and forth.  `overrides[frame][tag]` = (type, count, value)
-    replaces or adds an entry, None drops it.  Returns (offsets, nbytes) in frame order."""
-    h, w = shape
-    n = len(strips)
-    order = list(reversed(range(n))) if order is None else list(order)
-    overrides = overrides or {}
-    off_type = 16 if big else 4
-    fsz = 8 if big else 4  # the value field
-
-    def entries(i, strip_offset):
-        e = {256: (4, 1, w), 257: (4, 1, h), 259: (3, 1, compression), 273: (off_type, 1, strip_offset),
-             279: (4, 1, len(strips[i]))}
-        for tag, val in overrides.get(i, {}).items():
-            if val is None:
-                e.pop(tag, None)
-            else:
-                e[tag] = val
-        return sorted(e.items())
-
-    def ifd_size(i):
-        k = len(entries(i, 0))
-        return (8 + 20 * k + 8) if big else (2 + 12 * k + 4)
-
-    at = 16 if big else 8
-    strip_at, ifd_at = [0] * n, [0] * n
-    for i in order:
-        at += 1 - at % 2  # an odd offset
-        strip_at[i] = at
-        at += len(strips[i])
-        at += at % 2  # IFDs on word boundaries
-        ifd_at[i] = at
-        at += ifd_size(i)
-    out = bytearray(b"\xee" * at)
-    bo = byte_order
-    out[:2] = b"II" if bo == "<" else b"MM"
-    if big:
-        struct.pack_into(bo + "HHHQ", out, 2, 43, 8, 0, ifd_at[0] if n else 0)
-    else:
-        struct.pack_into(bo + "HI", out, 2, 42, ifd_at[0] if n else 0)
-    for i in range(n):
-        out[strip_at[i]:strip_at[i] + len(strips[i])] = strips[i]
-        ents = entries(i, strip_at[i])
-        p = ifd_at[i]
-        struct.pack_into(bo + ("Q" if big else "H"), out, p, len(ents))
-        p += 8 if big else 2
-        for tag, (typ, count, value) in ents:
-            struct.pack_into(bo + "HH" + ("Q" if big else "I"), out, p, tag, typ, count)
-            field = bytearray(fsz)
-            if typ in _SIZES and _SIZES[typ] * count <= fsz and count == 1:
-                struct.pack_into(bo + _CODES[typ], field, 0, value)
-            else:  # an offset to the values (never followed by the reader under test)
-                struct.pack_into(bo + ("Q" if big else "I"), field, 0, value)
-            out[p + 4 + fsz:p + 4 + 2 * fsz] = field
-            p += 4 + 2 * fsz
-        struct.pack_into(bo + ("Q" if big else "I"), out, p, ifd_at[i + 1] if i + 1 < n else 0)
-    with open(path, "wb") as fh:
-        fh.write(out)
-    return strip_at, [len(s) for s in strips]
+    """tiff_files.write_tiff with an EER file's tags: one strip per frame, no BitsPerSample, RowsPerStrip or
+    SampleFormat.  Returns (offsets, nbytes) in frame order."""
+    tags = {256: (4, 1, shape[1]), 257: (4, 1, shape[0]), 259: (3, 1, compression)}
+    offsets, nbytes = tiff_files.write_tiff(path, [[s] for s in strips], tags, big=big, byte_order=byte_order,
+                                            order=order, array_types=(16 if big else 4, 4), overrides=overrides)
+    return [o[0] for o in offsets], [n[0] for n in nbytes]

@@ -1,10 +1,15 @@
 """What the float64 kernel tests (tests/test_*_kernels_float64.py and their neighbours) measure with, defined once:
-which entry points of libmcorr ran (Recorder, `calls`), that nothing was written outside an output buffer (nan_buffer,
-assert_guards, nan_empty), the inputs (float_stack, raw_movie, gain, raw_setup), the worst error over bound per
+which entry points of libmcorr ran (Recorder, `calls`) and what the header says of them (header_signature), that nothing
+was written outside an output buffer (nan_buffer, assert_guards, nan_empty; byte_buffer, assert_byte_guards for the
+byte-moving kernels), the inputs (float_stack, raw_movie, gain, raw_setup), the worst error over bound per
 output family (ratios_fixture, worse) and the engine's test switches (`switches`).  tests/test_kernel_harness_host.py
 pins every one of them on the CPU.
 
 A test module takes a fixture with `from kernel_harness import calls  # noqa: F401`."""
+
+import ctypes
+import os
+import re
 
 import numpy as np
 import pytest
@@ -28,6 +33,17 @@ def lib():
     from torch_motion_correction_amd import _lib
 
     return _lib.load()
+
+
+def header_signature(name, header=None):
+    """The ctypes argument types of the entry point `name` as include/mcorr.h declares it (pointer, long long, int),
+    for comparison with _lib.SIGNATURES[name].  `header`: the header's text instead of the file's."""
+    if header is None:
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        with open(os.path.join(root, "include", "mcorr.h")) as fh:
+            header = fh.read()
+    args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
+    return [ctypes.c_void_p if "*" in a else ctypes.c_int64 if "long long" in a else ctypes.c_int for a in args]
 
 
 class Recorder:
@@ -108,6 +124,27 @@ def assert_guards(view, flat, what):
     n, lead = view.numel(), (view.data_ptr() - flat.data_ptr()) // 4
     assert bool(torch.isnan(flat[:lead]).all()) and bool(torch.isnan(flat[lead + n:]).all()), \
         f"{what}: wrote outside its output buffer"
+
+
+def byte_buffer(nbytes, dev, past=0):
+    """`nbytes` bytes that start `past` bytes beyond a 16-byte boundary, inside a larger NaN-filled allocation ->
+    (the uint8 view, the whole allocation as bytes).  The byte tests' sibling of nan_buffer; a typed buffer is
+    ``view.view(dtype).view(shape)``."""
+    lead = 4 * GUARD + past
+    flat = torch.full(((lead + nbytes + 3) // 4 + GUARD,), float("nan"), dtype=torch.float32, device=dev)
+    whole = flat.view(torch.uint8)
+    view = whole[lead:lead + nbytes]
+    assert whole.data_ptr() % 16 == 0 and view.data_ptr() % 16 == past % 16
+    return view, whole
+
+
+def assert_byte_guards(view, whole, what):
+    """No byte of `whole` outside `view` (of any dtype) differs from the NaN words byte_buffer filled it with."""
+    lead, n = view.data_ptr() - whole.data_ptr(), view.numel() * view.element_size()
+    fresh = torch.full((whole.numel() // 4,), float("nan"), dtype=torch.float32).view(torch.uint8)
+    got = whole.cpu()
+    assert torch.equal(got[:lead], fresh[:lead]) and torch.equal(got[lead + n:], fresh[lead + n:]), \
+        f"{what}: wrote outside its buffer"
 
 
 def offset_copy(src, offset):

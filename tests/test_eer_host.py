@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import eer_reference as er
+from kernel_harness import header_signature
 import torch_motion_correction_amd as mc
 from torch_motion_correction_amd import _lib, eer
 
@@ -48,11 +49,9 @@ def test_header_signatures_and_build_agree():
     assert declared == set(_lib.SIGNATURES)
     name = "mc_eer_render"
     assert name in declared and getattr(_lib.load(), name) is not None
-    args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    want = [vp if "*" in a else i64 if "long long" in a else i32 for a in args]
-    assert _lib.SIGNATURES[name] == want == [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64,
-                                             vp]
+    assert _lib.SIGNATURES[name] == header_signature(name) == [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp,
+                                                               vp, vp, vp, i64, vp]
     assert ("eer_render.hip", "eer_render", []) in _build.SOURCES
     assert os.path.exists(os.path.join(_build.CSRC, "eer_render.hip"))
     # the segment size the wrapper asks for is one the header's records hold and the entry point takes

@@ -84,6 +84,56 @@ def test_nan_buffer_alignment_and_guards(offset):
     kh.assert_guards(view, flat, "restored")
 
 
+@pytest.mark.parametrize("past", [0, 1, 3, 6, 12, 16, 17])
+@pytest.mark.parametrize("nbytes", [1, 5, 64, 210])
+def test_byte_buffer_alignment_and_guards(past, nbytes):
+    view, whole = kh.byte_buffer(nbytes, CPU, past)
+    lead = view.data_ptr() - whole.data_ptr()
+    assert view.dtype == whole.dtype == torch.uint8 and view.shape == (nbytes,) and view.is_contiguous()
+    assert whole.data_ptr() % 16 == 0 and view.data_ptr() % 16 == past % 16 and whole.numel() % 4 == 0
+    assert lead >= 4 * kh.GUARD and whole.numel() - lead - nbytes >= 4 * kh.GUARD
+    assert bool(torch.isnan(whole.view(torch.float32)).all())
+    kh.assert_byte_guards(view, whole, "untouched")
+    view.fill_(0)  # writing all of the buffer, and nothing else, passes
+    kh.assert_byte_guards(view, whole, "filled")
+    for at in (lead - 1, lead + nbytes, 0, whole.numel() - 1):  # the bytes next to the view, the allocation's ends
+        saved = int(whole[at])
+        whole[at] = saved ^ 1
+        with pytest.raises(AssertionError, match="one write: wrote outside its buffer"):
+            kh.assert_byte_guards(view, whole, "one write")
+        whole[at] = saved
+    kh.assert_byte_guards(view, whole, "restored")
+
+
+def test_byte_buffer_typed_views():
+    """A typed output is a view of the bytes; the guard check takes it as it is."""
+    for dtype in (torch.int16, torch.float16, torch.float32):
+        size = dtype.itemsize
+        view, whole = kh.byte_buffer(3 * 5 * size, CPU, past=3 * size)
+        out = view.view(dtype).view(3, 5)
+        assert out.data_ptr() == view.data_ptr() and out.data_ptr() % size == 0 and out.data_ptr() % 16 == 3 * size
+        out.fill_(1)
+        kh.assert_byte_guards(out, whole, "typed")
+        whole[out.data_ptr() - whole.data_ptr() + out.numel() * size] ^= 1
+        with pytest.raises(AssertionError, match="wrote outside its buffer"):
+            kh.assert_byte_guards(out, whole, "typed")
+
+
+def test_header_signature():
+    import ctypes
+
+    from torch_motion_correction_amd import _lib
+
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    text = "int mc_other(int a);\nint mc_made_up(const unsigned char* data, long long n,\n    int h, void* stream);\n"
+    assert kh.header_signature("mc_made_up", text) == [vp, i64, i32, vp]
+    assert kh.header_signature("mc_other", text) == [i32]
+    with pytest.raises(AttributeError):
+        kh.header_signature("mc_absent", text)
+    for name in ("mc_eer_render", "mc_tiff_decode", "mc_tiff_encode", "mc_tiff_pack", "mc_mrc_decode", "mc_raw_orient"):
+        assert kh.header_signature(name) == _lib.SIGNATURES[name]  # the committed header
+
+
 def test_nan_and_nan_empty(nan_empty):
     assert bool(torch.isnan(kh.nan((2, 3), CPU)).all()) and kh.nan((2, 3), CPU).dtype == torch.float32
     assert bool(torch.isnan(torch.empty(4, 5)).all()) and bool(torch.isnan(torch.empty((3,), dtype=torch.float64)).all())

@@ -1,6 +1,6 @@
 """MRC decode on the GPU (decode_mrc_raw: mc_mrc_decode, csrc/mrc_decode.hip over csrc/mrc.h) against the numpy decoder
 of tests/mrc_reference.py.  The decoder moves bytes: torch.equal throughout.  Every output lies inside a NaN-guarded
-allocation (kernel_harness.nan_buffer) at an address that is aligned for its element and for nothing more, and
+allocation (kernel_harness.byte_buffer) at an address that is aligned for its element and for nothing more, and
 `data` ends at the payload's last byte, so a write outside the movie shows and a read outside the payload has nothing
 behind it."""
 
@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import mrc_reference as mr
-from kernel_harness import nan_buffer
+from kernel_harness import assert_byte_guards, byte_buffer
 
 pytestmark = pytest.mark.gpu
 
@@ -46,23 +46,12 @@ def pixels_for(mode, shape, seed, unsigned_bytes=False):
 
 
 def guarded(shape, dtype, dev):
-    """A (t, h, w) output of `dtype` inside a NaN-filled allocation, starting an odd number of elements past a 16-byte
-    boundary -> (the view, the whole allocation as bytes, the view's first byte in it)"""
-    size = dtype.itemsize
-    nbytes = int(np.prod(shape)) * size
-    _, flat = nan_buffer(((nbytes + 3) // 4 + 8,), dev)
-    whole = flat.view(torch.uint8)
-    lead = 16 + size * 3
-    view = whole[lead:lead + nbytes].view(dtype).view(*shape)
-    assert view.data_ptr() % size == 0 and view.data_ptr() % 16 != 0
-    return view, whole, lead
-
-
-def assert_guards(whole, lead, nbytes, what):
-    pattern = torch.full((whole.numel() // 4,), float("nan"), dtype=torch.float32).view(torch.uint8)
-    got = whole.cpu()
-    assert torch.equal(got[:lead], pattern[:lead]) and torch.equal(got[lead + nbytes:], pattern[lead + nbytes:]), \
-        f"{what}: wrote outside its output buffer"
+    """An output of `shape` and `dtype` inside a NaN-filled allocation, starting three elements past a 16-byte boundary
+    -> (the view, the whole allocation as bytes)"""
+    view, whole = byte_buffer(int(np.prod(shape)) * dtype.itemsize, dev, past=3 * dtype.itemsize)
+    view = view.view(dtype).view(*shape)
+    assert view.data_ptr() % dtype.itemsize == 0 and view.data_ptr() % 16 != 0
+    return view, whole
 
 
 def same_bits(a, b):
@@ -92,12 +81,12 @@ def test_every_branch_of_a_row(mc, dev, mode, swap, ub):
                     on_dev = data.to(dev)
                     for flip in (False, True):
                         want = torch.from_numpy(mr.decode(payload, (t, h, w), mode, swap, ub, flip))
-                        out, whole, lead = guarded((t, h, w), want.dtype, dev)
+                        out, whole = guarded((t, h, w), want.dtype, dev)
                         got = mrc._decode(on_dev, offset, t, h, w, mode, swap, ub, flip, dev, out=out)
                         torch.cuda.synchronize()
                         what = f"mode {mode} swap {swap} unsigned {ub} {(t, h, w)} offset {offset} flip {flip}"
                         assert got.data_ptr() == out.data_ptr()
-                        assert_guards(whole, lead, out.numel() * out.element_size(), what)
+                        assert_byte_guards(out, whole, what)
                         assert same_bits(got.cpu(), want), what
 
 

@@ -6,7 +6,6 @@ sanitizers (tests/host_mrc.cpp, a stand-alone program started as a child process
 
 import ctypes
 import os
-import re
 import shutil
 import struct
 import subprocess
@@ -16,6 +15,7 @@ import pytest
 import torch
 
 import mrc_reference as mr
+from kernel_harness import header_signature
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = (0, 1, 2, 6, 12, 101)
@@ -66,12 +66,10 @@ def test_sources_signatures_and_header_agree():
     assert stems.index("mrc_decode") < stems.index("eer_render") and stems.index("raw_orient") < stems.index("eer_render")
     for name in ("mrc_decode.hip", "raw_orient.hip", "mrc.h"):
         assert os.path.exists(os.path.join(_build.CSRC, name))
-    header = open(os.path.join(ROOT, "include", "mcorr.h")).read()
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
     for name, want in (("mc_mrc_decode", [vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
                        ("mc_raw_orient", [vp, i32, i32, i32, i32, i32, i32, vp, vp])):
-        args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
-        assert [vp if "*" in a else i64 if "long long" in a else i32 for a in args] == want == _lib.SIGNATURES[name]
+        assert header_signature(name) == want == _lib.SIGNATURES[name]
         assert getattr(_lib.load(), name) is not None
     rule = open(os.path.join(_build.CSRC, "mrc.h")).read()
     assert "NOT been confirmed" in rule  # the 4-bit layout rests on the format descriptions; mrc.h says so

@@ -1,13 +1,13 @@
 """orient_raw on the GPU (mc_raw_orient, csrc/raw_orient.hip) against numpy.rot90 + numpy.flip
 (tests/mrc_reference.py).  Elements are moved: torch.equal on the bits.  Every output lies inside a NaN-guarded
-allocation (kernel_harness.nan_buffer) at an address aligned for its element and for nothing more."""
+allocation (kernel_harness.byte_buffer) at an address aligned for its element and for nothing more."""
 
 import numpy as np
 import pytest
 import torch
 
 import mrc_reference as mr
-from kernel_harness import nan_buffer
+from kernel_harness import assert_byte_guards, byte_buffer
 
 pytestmark = pytest.mark.gpu
 
@@ -37,21 +37,12 @@ def as_bits(x):
 
 
 def guarded(shape, dtype, dev):
-    size = dtype.itemsize
-    nbytes = int(np.prod(shape)) * size
-    _, flat = nan_buffer(((nbytes + 3) // 4 + 8,), dev)
-    whole = flat.view(torch.uint8)
-    lead = 16 + size * 3
-    view = whole[lead:lead + nbytes].view(dtype).view(*shape)
-    assert view.data_ptr() % size == 0 and view.data_ptr() % 16 != 0
-    return view, whole, lead
-
-
-def assert_guards(whole, lead, nbytes, what):
-    pattern = torch.full((whole.numel() // 4,), float("nan"), dtype=torch.float32).view(torch.uint8)
-    got = whole.cpu()
-    assert torch.equal(got[:lead], pattern[:lead]) and torch.equal(got[lead + nbytes:], pattern[lead + nbytes:]), \
-        f"{what}: wrote outside its output buffer"
+    """An output of `shape` and `dtype` inside a NaN-filled allocation, starting three elements past a 16-byte boundary
+    -> (the view, the whole allocation as bytes)"""
+    view, whole = byte_buffer(int(np.prod(shape)) * dtype.itemsize, dev, past=3 * dtype.itemsize)
+    view = view.view(dtype).view(*shape)
+    assert view.data_ptr() % dtype.itemsize == 0 and view.data_ptr() % 16 != 0
+    return view, whole
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=str)
@@ -69,12 +60,12 @@ def test_every_rotation_and_flip(mc, dev, dtype, shape):
             got = mc.orient_raw(on_dev, k, flip)
             assert got.dtype == dtype and got.device == dev and got.is_contiguous() and got.shape == want.shape, what
             assert got.data_ptr() != on_dev.data_ptr() and torch.equal(as_bits(got).cpu(), want), what
-            out, whole, lead = guarded(tuple(want.shape), dtype, dev)
+            out, whole = guarded(tuple(want.shape), dtype, dev)
             kk, ff = mrc._check_orient_args(on_dev, k, flip)
             res = mrc._orient(on_dev, kk, ff, dev, out=out)
             torch.cuda.synchronize()
             assert res.data_ptr() == out.data_ptr()
-            assert_guards(whole, lead, out.numel() * out.element_size(), what)
+            assert_byte_guards(out, whole, what)
             assert torch.equal(as_bits(res).cpu(), want), what
 
 

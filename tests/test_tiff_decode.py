@@ -1,6 +1,6 @@
 """TIFF LZW decode on the GPU (decode_tiff_raw: mc_tiff_decode, csrc/tiff_decode.hip over csrc/tiff_lzw.h) against the
 committed libtiff-written files and the sequential decoder of tests/tiff_reference.py.  The decoder moves bytes:
-torch.equal throughout.  Every output buffer lies inside a guarded allocation (kernel_harness.nan_buffer), so a write
+torch.equal throughout.  Every output buffer lies inside a guarded allocation (kernel_harness.byte_buffer), so a write
 outside the movie shows."""
 
 import os
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import tiff_reference as tr
-from kernel_harness import nan_buffer
+from kernel_harness import assert_byte_guards, byte_buffer
 
 pytestmark = pytest.mark.gpu
 
@@ -31,33 +31,17 @@ def golden():
         return {k: g[k] for k in g.files}
 
 
-def guarded(nbytes, dev):
-    """`nbytes` of output inside a NaN-filled allocation, starting one byte past a word -> (the uint8 view, the
-    whole allocation as bytes, the view's first byte in it)"""
-    _, flat = nan_buffer(((nbytes + 3) // 4 + 1,), dev)
-    whole = flat.view(torch.uint8)
-    lead = (whole.numel() - nbytes) // 2 | 1
-    return whole[lead:lead + nbytes], whole, lead
-
-
-def assert_guards(whole, lead, nbytes, what):
-    pattern = torch.full((whole.numel() // 4,), float("nan"), dtype=torch.float32).view(torch.uint8)
-    got = whole.cpu()
-    assert torch.equal(got[:lead], pattern[:lead]) and torch.equal(got[lead + nbytes:], pattern[lead + nbytes:]), \
-        f"{what}: wrote outside its output buffer"
-
-
 def decode(dev, data, offsets, nbytes, shape, rps, compression=5, dtype=torch.uint8):
     """decode_tiff_raw's own steps with the output in a guarded buffer -> (movie bytes on the CPU, produced)."""
     from torch_motion_correction_amd import tiff
 
     flat_o, flat_n, t, spf, h, w, rps = tiff._check_decode_args(data, offsets, nbytes, shape, rps, compression, dtype)
     row_bytes = w * tiff._DTYPES[dtype][0]
-    out, whole, lead = guarded(t * h * row_bytes, dev)
+    out, whole = byte_buffer(t * h * row_bytes, dev, past=3)  # an odd address, one byte before a word
     got, produced = tiff._decode_strips(data, flat_o, flat_n, t, spf, h, row_bytes, rps, compression, dev, out=out)
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr()
-    assert_guards(whole, lead, out.numel(), "mc_tiff_decode")
+    assert_byte_guards(out, whole, "mc_tiff_decode")
     return got.cpu(), produced.cpu().tolist()
 
 

@@ -1,14 +1,14 @@
 """TIFF LZW encode on the GPU (encode_tiff_raw: mc_tiff_encode and mc_tiff_pack, csrc/tiff_encode.hip over
 csrc/tiff_lzw_encode.h) against the reference encoder of tests/tiff_reference.py, byte for byte, and write_tiff's files
 read back by read_tiff.  The input, the slots and the payload lie inside guarded, NaN-filled allocations
-(kernel_harness.nan_buffer): a write outside a buffer, or into a slot beyond the bytes a strip produced, shows."""
+(kernel_harness.byte_buffer): a write outside a buffer, or into a slot beyond the bytes a strip produced, shows."""
 
 import numpy as np
 import pytest
 import torch
 
 import tiff_reference as tr
-from kernel_harness import nan_buffer
+from kernel_harness import assert_byte_guards, byte_buffer
 
 pytestmark = pytest.mark.gpu
 
@@ -25,21 +25,6 @@ def pattern(nbytes):
     return torch.full(((nbytes + 3) // 4,), float("nan"), dtype=torch.float32).view(torch.uint8)[:nbytes]
 
 
-def guarded(nbytes, dev, odd):
-    """`nbytes` inside a NaN-filled allocation with guard words on both sides: 16-byte aligned, or (`odd`) one byte
-    past a word -> (the uint8 view, the whole allocation as bytes, the view's first byte in it)"""
-    view, flat = nan_buffer(((nbytes + 3) // 4 + 1,), dev)
-    whole = flat.view(torch.uint8)
-    lead = view.data_ptr() - flat.data_ptr() + (1 if odd else 0)
-    return whole[lead:lead + nbytes], whole, lead
-
-
-def assert_guards(whole, lead, nbytes, what):
-    got, want = whole.cpu(), pattern(whole.numel())
-    assert torch.equal(got[:lead], want[:lead]) and torch.equal(got[lead + nbytes:], want[lead + nbytes:]), \
-        f"{what}: wrote outside its buffer"
-
-
 def encode(dev, movie, rps):
     """encode_tiff_raw's own steps with the input, the slots and the payload in guarded buffers -> (the payload's
     bytes, the per-strip sizes)."""
@@ -47,29 +32,29 @@ def encode(dev, movie, rps):
 
     t, h, w, rps, spf, row_bytes = tiff._check_encode_args(movie, rps, 5)
     raw = movie.contiguous().view(torch.uint8).reshape(-1)
-    src, src_whole, src_lead = guarded(raw.numel(), dev, odd=True)
+    src, src_whole = byte_buffer(raw.numel(), dev, past=1)
     src.copy_(raw)
     slot = tiff._slot_bytes(rps * row_bytes)
-    slots, slots_whole, slots_lead = guarded(t * spf * slot, dev, odd=False)
+    slots, slots_whole = byte_buffer(t * spf * slot, dev)
     assert slots.data_ptr() % 16 == 0
     got_slots, got_slot, produced = tiff._encode_strips(src, t, spf, h, row_bytes, rps, dev, slots=slots)
     torch.cuda.synchronize()
     assert got_slots.data_ptr() == slots.data_ptr() and got_slot == slot
     sizes = produced.cpu().tolist()
-    assert_guards(slots_whole, slots_lead, slots.numel(), "mc_tiff_encode")
+    assert_byte_guards(slots, slots_whole, "mc_tiff_encode")
     assert bytes(src.cpu().numpy()) == bytes(raw.numpy())
-    assert_guards(src_whole, src_lead, src.numel(), "mc_tiff_encode (input)")
+    assert_byte_guards(src, src_whole, "mc_tiff_encode (input)")
     # every slot byte past what its strip produced is untouched (slots start on 16-byte boundaries of the pattern)
     image, fresh = slots.cpu().view(t * spf, slot), pattern(slot)
     assert all(0 < n <= slot for n in sizes)
     keep = torch.arange(slot)[None, :] >= torch.tensor(sizes)[:, None]
     assert torch.equal(image[keep], fresh.expand(t * spf, slot)[keep]), "a strip wrote beyond the bytes it produced"
     total = sum(sizes)
-    payload, pay_whole, pay_lead = guarded(total, dev, odd=True)
+    payload, pay_whole = byte_buffer(total, dev, past=1)
     got = tiff._pack_strips(slots, slot, produced, total, dev, payload=payload)
     torch.cuda.synchronize()
     assert got.data_ptr() == payload.data_ptr()
-    assert_guards(pay_whole, pay_lead, total, "mc_tiff_pack")
+    assert_byte_guards(payload, pay_whole, "mc_tiff_pack")
     return bytes(payload.cpu().numpy()), sizes
 
 

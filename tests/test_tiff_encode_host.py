@@ -18,6 +18,8 @@ import pytest
 import torch
 
 import tiff_reference as tr
+from kernel_harness import header_signature
+from tiff_files import walk_ifds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "tiff_lzw_libtiff.npz")
@@ -94,8 +96,7 @@ def test_header_signatures_and_build_agree():
     want = {"mc_tiff_encode": [vp, i32, i32, i32, i32, i32, vp, i64, i64, vp, vp],
             "mc_tiff_pack": [vp, i64, vp, vp, i64, vp, i64, vp]}
     for name, types in want.items():
-        args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
-        assert [vp if "*" in a else i64 if "long long" in a else i32 for a in args] == types == _lib.SIGNATURES[name]
+        assert header_signature(name) == types == _lib.SIGNATURES[name]
         assert getattr(_lib.load(), name) is not None
     assert re.search(r"^int\s+mc_tiff_encode_slot_bytes\s*\(long long strip_bytes, long long\* slot_bytes", header,
                      flags=re.M)
@@ -310,38 +311,6 @@ def test_file_plan_switches_to_bigtiff_when_offsets_need_it():
 
 
 # ------------------------------------------------------------------ write_tiff, stored strips: no device
-
-
-def walk_ifds(raw):
-    """A struct walk of a little-endian TIFF / BigTIFF, independent of read_tiff -> (big, [(IFD offset, [(tag, type,
-    count, values)])])"""
-    assert raw[:2] == b"II"
-    magic = struct.unpack_from("<H", raw, 2)[0]
-    big = magic == 43
-    if big:
-        assert struct.unpack_from("<HH", raw, 4) == (8, 0)
-        ifd = struct.unpack_from("<Q", raw, 8)[0]
-    else:
-        assert magic == 42
-        ifd = struct.unpack_from("<I", raw, 4)[0]
-    word, cnt, entry = ("Q", 8, 20) if big else ("I", 2, 12)
-    sizes = {3: ("H", 2), 4: ("I", 4), 16: ("Q", 8)}
-    out = []
-    while ifd:
-        n = struct.unpack_from("<Q" if big else "<H", raw, ifd)[0]
-        tags = []
-        for k in range(n):
-            at = ifd + cnt + entry * k
-            tag, typ, count = struct.unpack_from("<HH" + word, raw, at)
-            code, size = sizes[typ]
-            field = at + 4 + struct.calcsize(word)
-            if size * count > struct.calcsize(word):
-                field = struct.unpack_from("<" + word, raw, field)[0]
-                assert field % 2 == 0
-            tags.append((tag, typ, count, list(struct.unpack_from(f"<{count}{code}", raw, field))))
-        out.append((ifd, tags))
-        ifd = struct.unpack_from("<" + word, raw, ifd + cnt + entry * n)[0]
-    return big, out
 
 
 @pytest.mark.parametrize("bigtiff", [None, True])

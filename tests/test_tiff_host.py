@@ -17,7 +17,9 @@ import numpy as np
 import pytest
 import torch
 
+import tiff_files
 import tiff_reference as tr
+from kernel_harness import header_signature
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "tiff_lzw_libtiff.npz")
@@ -38,24 +40,12 @@ def mc():
 
 
 def walk(raw):
-    """A minimal walk of a little-endian classic TIFF written by libtiff, independent of read_tiff ->
-    [(strip offsets, strip byte counts, rows per strip, compression)] per frame."""
-    assert raw[:4] == b"II*\x00"
-    frames, ifd = [], struct.unpack_from("<I", raw, 4)[0]
-    while ifd:
-        n = struct.unpack_from("<H", raw, ifd)[0]
-        tags = {}
-        for k in range(n):
-            tag, typ, count = struct.unpack_from("<HHI", raw, ifd + 2 + 12 * k)
-            if typ not in (3, 4):
-                continue
-            code, size = ("H", 2) if typ == 3 else ("I", 4)
-            at = ifd + 2 + 12 * k + 8
-            if size * count > 4:
-                at = struct.unpack_from("<I", raw, at)[0]
-            tags[tag] = list(struct.unpack_from(f"<{count}{code}", raw, at))
-        frames.append((tags[273], tags[279], tags[278][0], tags[259][0]))
-        ifd = struct.unpack_from("<I", raw, ifd + 2 + 12 * n)[0]
+    """The frames of a file libtiff wrote, by tiff_files.walk_ifds: independent of read_tiff -> [(strip offsets, strip
+    byte counts, rows per strip, compression)] per frame."""
+    frames = []
+    for _, tags in tiff_files.walk_ifds(raw)[1]:
+        value = {tag: values for tag, _, _, values in tags}
+        frames.append((value[273], value[279], value[278][0], value[259][0]))
     return frames
 
 
@@ -123,10 +113,9 @@ def test_header_signatures_and_build_agree(mc):
     assert declared == set(_lib.SIGNATURES)
     name = "mc_tiff_decode"
     assert name in declared and getattr(_lib.load(), name) is not None
-    args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    want = [vp if "*" in a else i64 if "long long" in a else i32 for a in args]
-    assert _lib.SIGNATURES[name] == want == [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]
+    assert _lib.SIGNATURES[name] == header_signature(name) == [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp,
+                                                               vp, i64, vp]
     assert _build.SOURCES[-1] == ("tiff_decode.hip", "tiff_decode", [])
     assert os.path.exists(os.path.join(_build.CSRC, "tiff_decode.hip"))
     assert os.path.exists(os.path.join(_build.CSRC, "tiff_lzw.h"))

@@ -1,6 +1,7 @@
 """TIFF 6.0 LZW restated with Python integers: the sequential decoder the device decode (mc_tiff_decode) is compared
-with, an encoder that produces test streams, and a writer of minimal multi-strip TIFF / BigTIFF files.  The rule is
-the one csrc/tiff_lzw.h states; tests/golden/tiff_lzw_libtiff.npz pins it to files libtiff wrote.
+with, an encoder that produces test streams, and the strip-movie flavour of the container writer
+(tests/tiff_files.py).  The rule is the one csrc/tiff_lzw.h states; tests/golden/tiff_lzw_libtiff.npz pins it to files
+libtiff wrote.
 
   codes packed MSB-first; width 9 at the start and after Clear (256); EOI = 257; first free code 258
   the decoder starts cleared whether or not the stream begins with Clear
@@ -11,7 +12,7 @@ the one csrc/tiff_lzw.h states; tests/golden/tiff_lzw_libtiff.npz pins it to fil
   stop at EOI, at the expected size, when fewer than `width` bits are left, at a malformed code
 """
 
-import struct
+import tiff_files
 
 CLEAR, EOI, FIRST, TABLE = 256, 257, 258, 4096
 STOPS = ("eoi", "full", "bits", "malformed")
@@ -154,100 +155,14 @@ def decode_movie(strips, shape, rows_per_strip, row_bytes):
     return bytes(out), produced
 
 
-def lay_out(strips, order=None, lead=1, gap=3, odd=True, fill=None):
-    """Every strip of every frame laid into one buffer in `order` (indices into the flattened frame-major list),
-    `gap` bytes between them (0xff, or bytes drawn from the numpy generator `fill`), every strip at an odd offset
-    when `odd` -> (bytes, offsets, nbytes), the latter two as lists per frame."""
-    flat = [s for f in strips for s in f]
-    order = range(len(flat)) if order is None else order
-
-    def pad(k):
-        return bytes(fill.integers(0, 256, k, dtype="uint8")) if fill is not None else b"\xff" * k
-
-    buf = bytearray(pad(lead))
-    at = [0] * len(flat)
-    for i in order:
-        buf += pad(gap)
-        if odd and len(buf) % 2 == 0:
-            buf += pad(1)
-        at[i] = len(buf)
-        buf += flat[i]
-    buf += pad(gap)
-    offsets, nbytes, i = [], [], 0
-    for f in strips:
-        offsets.append(at[i:i + len(f)])
-        nbytes.append([len(s) for s in f])
-        i += len(f)
-    return bytes(buf), offsets, nbytes
-
-
-# ------------------------------------------------------------------ containers
-
-_SIZES = {1: 1, 3: 2, 4: 4, 16: 8}
-_CODES = {1: "B", 3: "H", 4: "I", 16: "Q"}
+lay_out = tiff_files.lay_out
 
 
 def write_tiff(path, strips, shape, rows_per_strip, big=False, byte_order="<", compression=5, bits=8,
                sample_format=1, array_type=4, overrides=None, loop=False):
-    """A minimal TIFF (magic 42) or BigTIFF (magic 43): one IFD per frame, `strips[f]` its strips, written in
-    reverse order at odd offsets, each frame's IFD and its out-of-line arrays behind its strips.  StripOffsets and
-    StripByteCounts have TIFF type `array_type` (3 SHORT, 4 LONG, 16 LONG8) and go inline when they fit the value
-    field.  `overrides[frame][tag]` = (type, count, value or list) replaces or adds an entry, None drops it.  `loop`:
-    the last IFD points back at the first.  Returns (offsets, nbytes) per frame."""
-    h, w = shape
-    bo, n = byte_order, len(strips)
-    overrides = overrides or {}
-    fsz = 8 if big else 4
-    out = bytearray(16 if big else 8)
-    strip_at = [[0] * len(f) for f in strips]
-    ifd_at = [0] * n
-    blobs = []
-    for i in reversed(range(n)):
-        for k in reversed(range(len(strips[i]))):
-            if len(out) % 2 == 0:
-                out += b"\xee"
-            strip_at[i][k] = len(out)
-            out += strips[i][k]
-        e = {256: (4, 1, w), 257: (4, 1, h), 258: (3, 1, bits), 259: (3, 1, compression),
-             273: (array_type, len(strips[i]), strip_at[i]), 278: (4, 1, rows_per_strip),
-             279: (array_type, len(strips[i]), [len(s) for s in strips[i]]), 339: (3, 1, sample_format)}
-        for tag, val in overrides.get(i, {}).items():
-            if val is None:
-                e.pop(tag, None)
-            else:
-                e[tag] = val
-        fields = []
-        for tag, (typ, count, value) in sorted(e.items()):
-            vals = list(value) if isinstance(value, (list, tuple)) else [value]
-            field = bytearray(fsz)
-            if typ in _SIZES and _SIZES[typ] * count <= fsz and len(vals) == count:
-                struct.pack_into(f"{bo}{count}{_CODES[typ]}", field, 0, *vals)
-            elif typ in _SIZES and len(vals) == count:  # out of line
-                out += b"\xee" * (len(out) % 2)
-                struct.pack_into(bo + ("Q" if big else "I"), field, 0, len(out))
-                out += struct.pack(f"{bo}{count}{_CODES[typ]}", *vals)
-            else:  # a raw value field: an offset the test chose, or a type the reader refuses
-                struct.pack_into(bo + ("Q" if big else "I"), field, 0, vals[0])
-            fields.append((tag, typ, count, field))
-        out += b"\xee" * (len(out) % 2)
-        ifd_at[i] = len(out)
-        out += bytes((8 if big else 2) + (4 + 2 * fsz) * len(fields) + fsz)
-        blobs.append((i, fields))
-    for i, fields in blobs:
-        p = ifd_at[i]
-        struct.pack_into(bo + ("Q" if big else "H"), out, p, len(fields))
-        p += 8 if big else 2
-        for tag, typ, count, field in fields:
-            struct.pack_into(bo + "HH" + ("Q" if big else "I"), out, p, tag, typ, count)
-            out[p + 4 + fsz:p + 4 + 2 * fsz] = field
-            p += 4 + 2 * fsz
-        nxt = ifd_at[i + 1] if i + 1 < n else (ifd_at[0] if loop else 0)
-        struct.pack_into(bo + ("Q" if big else "I"), out, p, nxt)
-    out[:2] = b"II" if bo == "<" else b"MM"
-    if big:
-        struct.pack_into(bo + "HHHQ", out, 2, 43, 8, 0, ifd_at[0] if n else 0)
-    else:
-        struct.pack_into(bo + "HI", out, 2, 42, ifd_at[0] if n else 0)
-    with open(path, "wb") as fh:
-        fh.write(out)
-    return strip_at, [[len(s) for s in f] for f in strips]
+    """tiff_files.write_tiff with a strip movie's tags; StripOffsets and StripByteCounts have TIFF type `array_type`.
+    Returns (offsets, nbytes) per frame."""
+    tags = {256: (4, 1, shape[1]), 257: (4, 1, shape[0]), 258: (3, 1, bits), 259: (3, 1, compression),
+            278: (4, 1, rows_per_strip), 339: (3, 1, sample_format)}
+    return tiff_files.write_tiff(path, strips, tags, big=big, byte_order=byte_order,
+                                 array_types=(array_type, array_type), overrides=overrides, loop=loop)

@@ -18,13 +18,11 @@ from the public description of the format: no vendor-written file has been decod
 from __future__ import annotations
 
 import ctypes as C
-import operator
-import os
-import struct
 from dataclasses import dataclass
 
 import torch
 
+from ._files import _check_data, _int, _positive_ints, read_file, require_tags, walk_ifds
 from ._lib import check, device_scope, load, ptr, require_gpu, stream_ptr
 
 SEGMENT_BYTES = 64   # the segment size of the parallel parse, chosen by measurement among 64, 128, 256
@@ -36,29 +34,10 @@ _TAG_NAMES = {256: "ImageWidth", 257: "ImageLength", 259: "Compression", 273: "S
               65009: "EER vertical sub-pixel bits"}
 
 
-def _int(value, what, lo):
-    if isinstance(value, bool):
-        raise ValueError(f"{what} must be an int >= {lo}, got {value!r}")
-    try:
-        v = operator.index(value)
-    except TypeError:
-        raise ValueError(f"{what} must be an int >= {lo}, got {value!r}") from None
-    if v < lo:
-        raise ValueError(f"{what} must be an int >= {lo}, got {value!r}")
-    return v
-
-
 def _check_render_args(data, offsets, nbytes, shape, group, upsampling, rle_bits):
     """Every argument rule of render_eer_raw -> (offsets, nbytes, h, w, group) as Python ints; ValueError otherwise."""
-    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("data must be a 1-D uint8 tensor, got "
-                         f"{getattr(data, 'dtype', type(data).__name__)} {tuple(getattr(data, 'shape', ()))}")
-    try:
-        h, w = (operator.index(s) for s in shape)
-    except (TypeError, ValueError):
-        raise ValueError(f"shape must be the detector's (h, w), got {shape!r}") from None
-    if h < 1 or w < 1:
-        raise ValueError(f"shape must be the detector's (h, w), got {shape!r}")
+    _check_data(data)
+    h, w = _positive_ints(shape, 2, f"shape must be the detector's (h, w), got {shape!r}")
     if h * w >= 2**31:
         raise ValueError(f"shape {(h, w)}: detectors of 2^31 pixels and more are not supported")
     if rle_bits != 7:
@@ -173,9 +152,6 @@ class EerMovie:
                               rle_bits=self.rle_bits, device=device)
 
 
-_INT_TYPES = {1: "B", 3: "H", 4: "I", 16: "Q"}  # TIFF types BYTE, SHORT, LONG, LONG8
-
-
 def read_eer(path):
     """An ``.eer`` file -> ``EerMovie``: a walk of the TIFF (magic 42) or BigTIFF (magic 43) IFD chain in plain
     Python, no decoder involved.  Every IFD is one frame and must give ImageWidth, ImageLength, Compression,
@@ -183,87 +159,40 @@ def read_eer(path):
     Compression 65001 is the 7-bit-run layout, 65002 is accepted when its tags 65007 - 65009 give 7, 2, 2 (absent
     tags mean those defaults); 65000 (8-bit runs) and anything else raise ValueError, as does every other deviation,
     with the tag named."""
-    with open(path, "rb") as fh:
-        raw = bytearray(os.fstat(fh.fileno()).st_size)  # writable, so that the tensor below shares it
-        size = fh.readinto(raw)
-    if size != len(raw):
-        del raw[size:]
+    raw, size, data = read_file(path)
 
     def fail(msg):
         raise ValueError(f"{path}: {msg}")
 
-    if size < 8 or raw[:2] not in (b"II", b"MM"):
-        fail("not a TIFF file (byte order mark)")
-    bo = "<" if raw[:2] == b"II" else ">"
-    magic = struct.unpack_from(bo + "H", raw, 2)[0]
-    if magic == 42:
-        big, entry_size, count_fmt, off_fmt = False, 12, "H", "I"
-        ifd = struct.unpack_from(bo + "I", raw, 4)[0]
-    elif magic == 43:
-        if size < 16 or struct.unpack_from(bo + "HH", raw, 4) != (8, 0):
-            fail("BigTIFF header with an offset size other than 8")
-        big, entry_size, count_fmt, off_fmt = True, 20, "Q", "Q"
-        ifd = struct.unpack_from(bo + "Q", raw, 8)[0]
-    else:
-        fail(f"TIFF magic {magic} is neither 42 (TIFF) nor 43 (BigTIFF)")
-    csz, osz = struct.calcsize(count_fmt), struct.calcsize(off_fmt)
-
-    def value(tag, typ, count, at):
-        """the single integer of an IFD entry whose value field starts at `at`"""
-        name = _TAG_NAMES[tag]
-        if typ not in _INT_TYPES:
-            fail(f"frame {len(offsets)}: {name} has TIFF type {typ}, not an unsigned integer")
-        if count != 1:  # (more values than the field holds would make it an offset to them)
-            fail(f"frame {len(offsets)}: {name} has {count} values; one strip and one value per frame are required")
-        return struct.unpack_from(bo + _INT_TYPES[typ], raw, at)[0]
-
-    offsets, nbytes, shape, compression, seen = [], [], None, None, set()
-    while ifd:
-        if ifd in seen:
-            fail("the IFD chain loops")
-        seen.add(ifd)
-        if ifd + csz > size:
-            fail(f"frame {len(offsets)}: its IFD lies outside the file")
-        n_entries = struct.unpack_from(bo + count_fmt, raw, ifd)[0]
-        end = ifd + csz + n_entries * entry_size
-        if end + osz > size:
-            fail(f"frame {len(offsets)}: its IFD lies outside the file")
-        tags = {}
-        for k in range(n_entries):
-            at = ifd + csz + k * entry_size
-            tag, typ = struct.unpack_from(bo + "HH", raw, at)
-            if tag not in _TAG_NAMES:
-                continue
-            count = struct.unpack_from(bo + off_fmt, raw, at + 4)[0]
-            tags[tag] = value(tag, typ, count, at + 4 + osz)
-        for tag in (256, 257, 259, 273, 279):
-            if tag not in tags:
-                fail(f"frame {len(offsets)}: {_TAG_NAMES[tag]} is missing")
+    offsets, nbytes, shape, compression = [], [], None, None
+    for i, found in enumerate(walk_ifds(raw, size, _TAG_NAMES, fail)):
+        require_tags(found, _TAG_NAMES, i, fail)
+        for tag, (_, values) in found.items():
+            if len(values) != 1:
+                fail(f"frame {i}: {_TAG_NAMES[tag]} has {len(values)} values; one strip and one value per frame are "
+                     "required")
+        tags = {tag: values[0] for tag, (_, values) in found.items()}
         comp = tags[259]
         if comp == 65002:
             layout = (tags.get(65007, 7), tags.get(65008, 2), tags.get(65009, 2))
             if layout != (7, 2, 2):
-                fail(f"frame {len(offsets)}: Compression 65002 with (rle, horizontal, vertical) bits {layout}; only "
-                     "(7, 2, 2) is decoded")
+                fail(f"frame {i}: Compression 65002 with (rle, horizontal, vertical) bits {layout}; only (7, 2, 2) is "
+                     "decoded")
         elif comp != 65001:
-            fail(f"frame {len(offsets)}: Compression {comp} is not supported (65001, or 65002 with 7, 2, 2 bits"
+            fail(f"frame {i}: Compression {comp} is not supported (65001, or 65002 with 7, 2, 2 bits"
                  + ("; 65000 has 8-bit runs)" if comp == 65000 else ")"))
         if compression is None:
             compression, shape = comp, (tags[257], tags[256])
         elif comp != compression:
-            fail(f"frame {len(offsets)}: Compression {comp} differs from the first frame's {compression}")
+            fail(f"frame {i}: Compression {comp} differs from the first frame's {compression}")
         elif (tags[257], tags[256]) != shape:
-            fail(f"frame {len(offsets)}: ImageLength x ImageWidth {(tags[257], tags[256])} differs from the first "
-                 f"frame's {shape}")
+            fail(f"frame {i}: ImageLength x ImageWidth {(tags[257], tags[256])} differs from the first frame's "
+                 f"{shape}")
         if tags[273] + tags[279] > size:
-            fail(f"frame {len(offsets)}: StripOffsets + StripByteCounts = {tags[273] + tags[279]} leaves the file "
-                 f"of {size} bytes")
+            fail(f"frame {i}: StripOffsets + StripByteCounts = {tags[273] + tags[279]} leaves the file of {size} "
+                 "bytes")
         offsets.append(tags[273])
         nbytes.append(tags[279])
-        ifd = struct.unpack_from(bo + off_fmt, raw, end)[0]
-    if not offsets:
-        fail("the file holds no frame (no IFD)")
     if shape[0] < 1 or shape[1] < 1:
         fail(f"ImageLength x ImageWidth {shape} is empty")
-    data = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
     return EerMovie(data=data, offsets=offsets, nbytes=nbytes, shape=shape, rle_bits=7)

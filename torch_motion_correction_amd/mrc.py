@@ -20,12 +20,12 @@ from __future__ import annotations
 
 import math
 import operator
-import os
 import struct
 from dataclasses import dataclass
 
 import torch
 
+from ._files import _check_data, _check_fits_int16, _int, _positive_ints, read_file
 from ._lib import check, device_scope, load, ptr, require_gpu, stream_ptr
 
 # mode -> (bytes of a file sample; None for the 4-bit mode, the dtype of the decoded movie)
@@ -50,25 +50,9 @@ def _out_dtype(mode, unsigned_bytes):
 
 def _check_decode_args(data, offset, shape, mode, swap, unsigned_bytes, flip_rows):
     """Every argument rule of decode_mrc_raw -> (offset, t, h, w, mode) as Python ints; ValueError otherwise."""
-    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("data must be a 1-D uint8 tensor, got "
-                         f"{getattr(data, 'dtype', type(data).__name__)} {tuple(getattr(data, 'shape', ()))}")
-    if isinstance(offset, bool):
-        raise ValueError(f"offset must be an int >= 0, got {offset!r}")
-    try:
-        off = operator.index(offset)
-    except TypeError:
-        raise ValueError(f"offset must be an int >= 0, got {offset!r}") from None
-    if off < 0:
-        raise ValueError(f"offset must be an int >= 0, got {offset!r}")
-    try:
-        if any(isinstance(s, bool) for s in shape):
-            raise TypeError
-        t, h, w = (operator.index(s) for s in shape)
-    except (TypeError, ValueError):
-        raise ValueError(f"shape must be the movie's (t, h, w), three positive ints, got {shape!r}") from None
-    if t < 1 or h < 1 or w < 1:
-        raise ValueError(f"shape must be the movie's (t, h, w), three positive ints, got {shape!r}")
+    _check_data(data)
+    off = _int(offset, "offset", 0)
+    t, h, w = _positive_ints(shape, 3, f"shape must be the movie's (t, h, w), three positive ints, got {shape!r}")
     try:
         known = not isinstance(mode, bool) and operator.index(mode) in _MODES
     except TypeError:
@@ -127,8 +111,8 @@ def decode_mrc_raw(data, offset, shape, mode, swap=False, unsigned_bytes=False, 
     ``device``: the GPU to decode on (None: the device of ``data``, the current GPU for a CPU tensor)."""
     off, t, h, w, mode = _check_decode_args(data, offset, shape, mode, swap, unsigned_bytes, flip_rows)
     movie = _decode(data, off, t, h, w, mode, swap, unsigned_bytes, flip_rows, device)
-    if mode == 6 and bool((movie < 0).any()):
-        raise ValueError("an unsigned 16-bit sample is 32768 or more: the movie does not fit the raw routes' int16")
+    if mode == 6:
+        _check_fits_int16(movie)
     return movie
 
 
@@ -169,11 +153,7 @@ def read_mrc(path):
     1024 bytes; a bzip2-compressed file.
 
     Rows are returned in stored order (``MrcMovie.decode(flip_rows=True)`` reverses them)."""
-    with open(path, "rb") as fh:
-        raw = bytearray(os.fstat(fh.fileno()).st_size)  # writable, so that the tensor below shares it
-        size = fh.readinto(raw)
-    if size != len(raw):
-        del raw[size:]
+    raw, size, data = read_file(path)
 
     def fail(msg):
         raise ValueError(f"{path}: {msg}")
@@ -219,7 +199,6 @@ def read_mrc(path):
         fail(f"a file of {size} bytes is shorter than the {need} its header gives: offset {offset} + nz {nz} x ny "
              f"{ny} rows of {_row_bytes(mode, nx)} bytes")
     spacing = None if mx == 0 or cella_x == 0 else float(cella_x) / mx
-    data = torch.frombuffer(raw, dtype=torch.uint8)
     return MrcMovie(data=data, offset=offset, shape=(nz, ny, nx), mode=mode, swap=bo == ">",
                     unsigned_bytes=mode == 0 and imod and not imod_flags & 1, pixel_spacing=spacing)
 
@@ -231,12 +210,7 @@ def _check_orient_args(x, rot90, flip):
                          f"{getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
     if x.numel() == 0:
         raise ValueError(f"x must not be empty, got shape {tuple(x.shape)}")
-    if isinstance(rot90, bool):
-        raise ValueError(f"rot90 must be an int, got {rot90!r}")
-    try:
-        k = operator.index(rot90) % 4
-    except TypeError:
-        raise ValueError(f"rot90 must be an int, got {rot90!r}") from None
+    k = _int(rot90, "rot90") % 4
     if not (flip is None or isinstance(flip, str)) or flip not in _FLIPS:
         raise ValueError(f"flip must be None, 'ud' or 'lr', got {flip!r}")
     if x.shape[-2] * x.shape[-1] >= 2**31:

@@ -19,13 +19,12 @@ csrc/tiff_lzw.h, and is pinned to files written by libtiff (tests/golden/tiff_lz
 from __future__ import annotations
 
 import ctypes as C
-import operator
-import os
 import struct
 from dataclasses import dataclass
 
 import torch
 
+from ._files import _check_data, _check_fits_int16, _int, _positive_ints, read_file, require_tags, walk_ifds
 from ._lib import check, device_scope, load, ptr, require_gpu, stream_ptr
 
 # the file's sample type -> (bytes per sample, the dtype of the decoded movie)
@@ -38,34 +37,14 @@ _TAG_NAMES = {256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: 
               273: "StripOffsets", 277: "SamplesPerPixel", 278: "RowsPerStrip", 279: "StripByteCounts",
               317: "Predictor", 322: "TileWidth", 323: "TileLength", 324: "TileOffsets", 325: "TileByteCounts",
               339: "SampleFormat"}
-_INT_TYPES = {1: "B", 3: "H", 4: "I", 16: "Q"}  # TIFF types BYTE, SHORT, LONG, LONG8
-_ARRAY_TYPES = {3: "H", 4: "I", 16: "Q"}        # StripOffsets / StripByteCounts: SHORT, LONG, LONG8
-
-
-def _int(value, what, lo):
-    if isinstance(value, bool):
-        raise ValueError(f"{what} must be an int >= {lo}, got {value!r}")
-    try:
-        v = operator.index(value)
-    except TypeError:
-        raise ValueError(f"{what} must be an int >= {lo}, got {value!r}") from None
-    if v < lo:
-        raise ValueError(f"{what} must be an int >= {lo}, got {value!r}")
-    return v
+_ARRAY_TYPES = (3, 4, 16)  # StripOffsets / StripByteCounts: SHORT, LONG, LONG8, no BYTE
 
 
 def _check_decode_args(data, offsets, nbytes, shape, rows_per_strip, compression, dtype):
     """Every argument rule of decode_tiff_raw -> (flat offsets, flat nbytes, t, strips per frame, h, w, rows per strip)
     as Python ints; ValueError otherwise."""
-    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("data must be a 1-D uint8 tensor, got "
-                         f"{getattr(data, 'dtype', type(data).__name__)} {tuple(getattr(data, 'shape', ()))}")
-    try:
-        h, w = (operator.index(s) for s in shape)
-    except (TypeError, ValueError):
-        raise ValueError(f"shape must be the frames' (h, w), got {shape!r}") from None
-    if h < 1 or w < 1:
-        raise ValueError(f"shape must be the frames' (h, w), got {shape!r}")
+    _check_data(data)
+    h, w = _positive_ints(shape, 2, f"shape must be the frames' (h, w), got {shape!r}")
     if dtype not in _DTYPES:
         raise ValueError(f"dtype must be torch.uint8, int16, uint16 (decoded to int16) or float32, got {dtype!r}")
     if isinstance(compression, bool) or compression not in (1, 5):
@@ -160,8 +139,8 @@ def decode_tiff_raw(data, offsets, nbytes, shape, rows_per_strip, compression=5,
                              f"{want[s % spf]} bytes of its rows: not a well-formed "
                              f"{'LZW' if compression == 5 else 'stored'} strip")
     movie = out.view(out_dtype).view(t, h, w)
-    if dtype == torch.uint16 and bool((movie < 0).any()):
-        raise ValueError("an unsigned 16-bit sample is 32768 or more: the movie does not fit the raw routes' int16")
+    if dtype == torch.uint16:
+        _check_fits_int16(movie)
     return movie
 
 
@@ -200,80 +179,31 @@ def read_tiff(path):
     looping chain, an empty file -- raises ValueError with the frame and the tag named.
 
     The Orientation tag is ignored: rows are returned in stored order."""
-    with open(path, "rb") as fh:
-        raw = bytearray(os.fstat(fh.fileno()).st_size)  # writable, so that the tensor below shares it
-        size = fh.readinto(raw)
-    if size != len(raw):
-        del raw[size:]
+    raw, size, data = read_file(path)
 
     def fail(msg):
         raise ValueError(f"{path}: {msg}")
 
     if size == 0:
         fail("the file is empty")
-    if size < 8 or raw[:2] not in (b"II", b"MM"):
-        fail("not a TIFF file (byte order mark)")
-    bo = "<" if raw[:2] == b"II" else ">"
-    magic = struct.unpack_from(bo + "H", raw, 2)[0]
-    if magic == 42:
-        entry_size, count_fmt, off_fmt = 12, "H", "I"
-        ifd = struct.unpack_from(bo + "I", raw, 4)[0]
-    elif magic == 43:
-        if size < 16 or struct.unpack_from(bo + "HH", raw, 4) != (8, 0):
-            fail("BigTIFF header with an offset size other than 8")
-        entry_size, count_fmt, off_fmt = 20, "Q", "Q"
-        ifd = struct.unpack_from(bo + "Q", raw, 8)[0]
-    else:
-        fail(f"TIFF magic {magic} is neither 42 (TIFF) nor 43 (BigTIFF)")
-    csz, osz = struct.calcsize(count_fmt), struct.calcsize(off_fmt)
-    frames = []  # (offsets, nbytes) per frame
-
-    def values(tag, typ, count, at, types):
-        """the integers of an IFD entry whose value field starts at `at`"""
-        where = f"frame {len(frames)}: {_TAG_NAMES[tag]}"
-        if typ not in types:
-            fail(f"{where} has TIFF type {typ}, not one of {sorted(types)} (unsigned integers)")
-        if count < 1:
-            fail(f"{where} has no value")
-        width = struct.calcsize(types[typ])
-        if width * count > osz:  # out of line
-            at = struct.unpack_from(bo + off_fmt, raw, at)[0]
-            if at + width * count > size:
-                fail(f"{where}: its {count} values at offset {at} leave the file of {size} bytes")
-        return list(struct.unpack_from(f"{bo}{count}{types[typ]}", raw, at))
-
-    first, seen = None, set()
-    while ifd:
-        i = len(frames)
-        if ifd in seen:
-            fail(f"frame {i}: the IFD chain loops")
-        seen.add(ifd)
-        if ifd + csz > size:
-            fail(f"frame {i}: its IFD lies outside the file")
-        n_entries = struct.unpack_from(bo + count_fmt, raw, ifd)[0]
-        end = ifd + csz + n_entries * entry_size
-        if end + osz > size:
-            fail(f"frame {i}: its IFD lies outside the file")
-        tags = {}
-        for k in range(n_entries):
-            at = ifd + csz + k * entry_size
-            tag, typ = struct.unpack_from(bo + "HH", raw, at)
-            if tag not in _TAG_NAMES:
-                continue  # Orientation among them: rows stay in stored order
-            if 322 <= tag <= 325:
+    offsets, nbytes, first = [], [], None
+    for i, found in enumerate(walk_ifds(raw, size, _TAG_NAMES, fail)):
+        for tag in range(322, 326):
+            if tag in found:
                 fail(f"frame {i}: {_TAG_NAMES[tag]} ({tag}): tiled TIFF is not supported, only strips")
-            count = struct.unpack_from(bo + off_fmt, raw, at + 4)[0]
+        require_tags(found, _TAG_NAMES, i, fail)
+        tags = {}
+        for tag, (typ, values) in found.items():  # Orientation is not among them: rows stay in stored order
             if tag in (273, 279):
-                tags[tag] = values(tag, typ, count, at + 4 + osz, _ARRAY_TYPES)
+                if typ not in _ARRAY_TYPES:
+                    fail(f"frame {i}: {_TAG_NAMES[tag]} has TIFF type {typ}, not one of {sorted(_ARRAY_TYPES)} "
+                         "(unsigned integers)")
+                tags[tag] = values
+            elif len(values) != 1:
+                fail(f"frame {i}: {_TAG_NAMES[tag]} has {len(values)} values"
+                     + ("; SamplesPerPixel other than 1 is not supported" if tag in (258, 339) else ""))
             else:
-                v = values(tag, typ, count, at + 4 + osz, _INT_TYPES)
-                if len(v) != 1:
-                    fail(f"frame {i}: {_TAG_NAMES[tag]} has {len(v)} values"
-                         + ("; SamplesPerPixel other than 1 is not supported" if tag in (258, 339) else ""))
-                tags[tag] = v[0]
-        for tag in (256, 257, 259, 273, 279):
-            if tag not in tags:
-                fail(f"frame {i}: {_TAG_NAMES[tag]} is missing")
+                tags[tag] = values[0]
         h, w, comp = tags[257], tags[256], tags[259]
         if h < 1 or w < 1:
             fail(f"frame {i}: ImageLength x ImageWidth {(h, w)} is empty")
@@ -290,7 +220,7 @@ def read_tiff(path):
         if (bits, fmt) not in _SAMPLES:
             fail(f"frame {i}: BitsPerSample {bits} with SampleFormat {fmt} is not supported: 8-bit unsigned, 16-bit "
                  "signed or unsigned and 32-bit float samples are")
-        if bits > 8 and bo == ">":
+        if bits > 8 and raw[:2] == b"MM":
             fail(f"frame {i}: BitsPerSample {bits} in a big-endian (MM) file is not supported")
         rps = min(tags.get(278, h), h)
         if rps < 1:
@@ -311,14 +241,11 @@ def read_tiff(path):
             if o + n > size:
                 fail(f"frame {i}, strip {k}: StripOffsets + StripByteCounts = {o + n} leaves the file of {size} "
                      "bytes")
-        frames.append((tags[273], tags[279]))
-        ifd = struct.unpack_from(bo + off_fmt, raw, end)[0]
-    if not frames:
-        fail("the file holds no frame (no IFD)")
+        offsets.append(tags[273])
+        nbytes.append(tags[279])
     h, w, comp, dtype, rps = first
-    data = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
-    return TiffMovie(data=data, offsets=[f[0] for f in frames], nbytes=[f[1] for f in frames], shape=(h, w),
-                     rows_per_strip=rps, compression=comp, dtype=dtype)
+    return TiffMovie(data=data, offsets=offsets, nbytes=nbytes, shape=(h, w), rows_per_strip=rps, compression=comp,
+                     dtype=dtype)
 
 
 # ------------------------------------------------------------------ raw movies -> LZW strips -> TIFF / BigTIFF files
