@@ -760,6 +760,26 @@ int mc_tiff_pack(const unsigned char* slots, long long slot_bytes, const long lo
 int mc_mrc_decode(const unsigned char* data, long long data_bytes, long long offset, int t, int h, int w, int mode,
                   int swap, int unsigned_bytes, int flip_rows, void* out, void* stream);
 
+/* A raw movie -> MRC2014 sample rows and the statistics the MRC header asks for, in one pass: the inverse of
+ * mc_mrc_decode for the integer types (the rule is stated in csrc/mrc_encode.h).  movie (device): the contiguous
+ * (t, h, w) elements of elem_bytes = 1 (uint8) or 2 (int16).  mode: uint8 -> 0 (the bytes) or 101 (4-bit, values
+ * 0..15); int16 -> 1 (the two bytes, little-endian), 6 (the same bytes, values 0..32767), 0 (one signed byte, values
+ * -128..127) or 101.  A mode-101 row is (w + 1) / 2 bytes, pixel 2k the low and pixel 2k + 1 the high nibble of byte
+ * k, the last high nibble of a row of odd w written as 0.  flip_rows: row r of every payload frame is row h - 1 - r of
+ * the movie's frame.  payload (device, any alignment, payload_bytes long): t * h rows one after the other, written
+ * whole bytes at a time, each byte by one thread; nothing beyond them is written.  stats (device, 8-byte aligned):
+ * t x 5 64-bit integers per frame, {min, max, sum, sum of squares of the samples as read, samples outside the mode's
+ * range}, exact and independent of scheduling; a sample out of range is written as its low bits masked to the field,
+ * and the caller refuses the movie.  scratch (device, 8-byte aligned): scratch_bytes >= t * B * 40 with B =
+ * min(1024, ceil(h * (w * elem_bytes / 16 + 2) / 256)), the workgroups of a frame (integer division inside).
+ * Before anything is launched: MC_ERR_ARG for null pointers, movie == payload, sizes < 1, a flip_rows other than 0
+ * or 1, h * w >= 2^31, a payload_bytes below t * h * the row's bytes, a movie misaligned for its element, a stats or
+ * scratch not aligned to 8 bytes and a scratch that is too small; MC_ERR_UNSUPPORTED for an (elem_bytes, mode) pair
+ * outside the list above. */
+int mc_mrc_encode(const void* movie, int elem_bytes, int t, int h, int w, int mode, int flip_rows,
+                  unsigned char* payload, long long payload_bytes, long long* stats, void* scratch,
+                  long long scratch_bytes, void* stream);
+
 /* Quarter turns and flips of n images: out = numpy.rot90(in, rot90, axes=(-2, -1)) (counter-clockwise), then
  * flip 1 ("ud": the rows' order reversed) or flip 2 ("lr": every row reversed), flip 0 for neither.  in: (n, h, w)
  * elements of elem_bytes = 1, 2 or 4 bytes (device); out: (n, h, w) for even rot90, (n, w, h) for odd, the same

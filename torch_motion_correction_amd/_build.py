@@ -45,6 +45,8 @@ SOURCES = [("xcg_rows_inv.hip", "xcg_rows_inv", []), ("xcg_cols_inv.hip", "xcg_c
            ("raw_group.hip", "raw_group", []), ("defect_fill.hip", "defect_fill", []),
            # MRC sample rows -> raw movies, over mrc.h; quarter turns and flips of raw images (the gain)
            ("mrc_decode.hip", "mrc_decode", []), ("raw_orient.hip", "raw_orient", []),
+           # raw movies -> MRC sample rows and the header's statistics, over mrc_encode.h
+           ("mrc_encode.hip", "mrc_encode", []),
            # EER event movies -> raw u8 movies, over eer.h
            ("eer_render.hip", "eer_render", []),
            # raw movies -> LZW TIFF strips, over tiff_lzw_encode.h; LZW / stored TIFF strips -> raw movies, over

@@ -103,6 +103,7 @@ SIGNATURES = {
     "mc_tiff_encode": [vp, i32, i32, i32, i32, i32, vp, i64, i64, vp, vp],
     "mc_tiff_pack": [vp, i64, vp, vp, i64, vp, i64, vp],
     "mc_mrc_decode": [vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "mc_mrc_encode": [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp],
     "mc_raw_orient": [vp, i32, i32, i32, i32, i32, i32, vp, vp],
     "mc_condition_movie": [vp, i32, vp, i32, i64, i32, vp, vp, vp],
     "mc_raw_movie_stats": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp],

@@ -10,10 +10,14 @@ SerialEM often hold 4-bit packed samples (mode 101).  This module is the third s
   orient_raw      numpy.rot90 + numpy.flip of a raw image or movie on the GPU (mc_raw_orient): the gain reference of
                   one program oriented for the movie of another
   write_mrc       a float image or stack written as an MRC2014 file (host code)
+  encode_mrc_raw  a raw uint8 / int16 movie packed into the sample rows of modes 0, 1, 6 and 101 on the GPU
+                  (mc_mrc_encode), with the header's statistics from the same pass -> ``MrcMovie``
+  write_mrc_raw   that payload written as an MRC2014 file, a chunk of frames at a time
 
 The decoded movie is a raw movie for every ``*_raw*`` function, ``RawStatistics`` and the pipelines, as the outputs
 of ``render_eer_raw`` and ``decode_tiff_raw`` are.  The format rule -- the modes and the 4-bit layout -- is stated
-once, in csrc/mrc.h; tests/mrc_reference.py restates it in numpy.
+once per direction, in csrc/mrc.h and csrc/mrc_encode.h; tests/mrc_reference.py and tests/mrc_encode_reference.py
+restate it in numpy.
 """
 
 from __future__ import annotations
@@ -265,27 +269,179 @@ def write_mrc(path, image, pixel_spacing, dtype=torch.float32):
                          f"{getattr(image, 'dtype', type(image).__name__)} {tuple(getattr(image, 'shape', ()))}")
     if dtype not in (torch.float32, torch.float16):
         raise ValueError(f"dtype must be torch.float32 (mode 2) or torch.float16 (mode 12), got {dtype!r}")
-    if isinstance(pixel_spacing, bool) or not isinstance(pixel_spacing, (int, float)) \
-            or not math.isfinite(pixel_spacing) or pixel_spacing <= 0:
-        raise ValueError(f"pixel_spacing must be a positive number, got {pixel_spacing!r}")
+    _check_pixel_spacing(pixel_spacing)
     values = image.detach().to("cpu").to(dtype).contiguous()
     nz = values.shape[0] if values.dim() == 3 else 1
     ny, nx = values.shape[-2:]
     wide = values.double()
     dmean = float(wide.mean())
     rms = math.sqrt(float(((wide - dmean) ** 2).mean()))
-    header = bytearray(1024)
-    struct.pack_into("<10i", header, 0, nx, ny, nz, 2 if dtype == torch.float32 else 12, 0, 0, 0, nx, ny, nz)
-    struct.pack_into("<6f", header, 40, nx * pixel_spacing, ny * pixel_spacing, nz * pixel_spacing, 90.0, 90.0, 90.0)
-    struct.pack_into("<3i", header, 64, 1, 2, 3)
-    struct.pack_into("<3f", header, 76, float(wide.min()), float(wide.max()), dmean)
-    struct.pack_into("<2i", header, 88, 0, 0)  # ispg, nsymbt; exttyp (104) stays blank: four zero bytes
-    struct.pack_into("<i", header, 108, 20140)
-    header[208:216] = b"MAP \x44\x44\x00\x00"
-    struct.pack_into("<f", header, 216, rms)
-    struct.pack_into("<i", header, 220, 1)
-    header[224:304] = _LABEL.ljust(80)
+    header = _header((nz, ny, nx), 2 if dtype == torch.float32 else 12, pixel_spacing,
+                     (float(wide.min()), float(wide.max()), dmean, rms))
     with open(path, "wb") as fh:
         fh.write(header)
         fh.write(values.view(torch.uint8).numpy().tobytes())
+    return path
+
+
+def _check_pixel_spacing(pixel_spacing):
+    if isinstance(pixel_spacing, bool) or not isinstance(pixel_spacing, (int, float)) \
+            or not math.isfinite(pixel_spacing) or pixel_spacing <= 0:
+        raise ValueError(f"pixel_spacing must be a positive number, got {pixel_spacing!r}")
+
+
+def _header(shape, mode, pixel_spacing, statistics, unsigned_bytes=False):
+    """The 1024 header bytes write_mrc describes, for a file of ``shape`` (nz, ny, nx) and ``mode``.  statistics:
+    (dmin, dmax, dmean, rms).  unsigned_bytes: IMOD's stamp with imodFlags 0, which marks mode-0 bytes unsigned."""
+    nz, ny, nx = shape
+    header = bytearray(1024)
+    struct.pack_into("<10i", header, 0, nx, ny, nz, mode, 0, 0, 0, nx, ny, nz)
+    struct.pack_into("<6f", header, 40, nx * pixel_spacing, ny * pixel_spacing, nz * pixel_spacing, 90.0, 90.0, 90.0)
+    struct.pack_into("<3i", header, 64, 1, 2, 3)
+    struct.pack_into("<3f", header, 76, *statistics[:3])
+    struct.pack_into("<2i", header, 88, 0, 0)  # ispg, nsymbt; exttyp (104) stays blank: four zero bytes
+    struct.pack_into("<i", header, 108, 20140)
+    if unsigned_bytes:
+        struct.pack_into("<2i", header, 152, _IMOD_STAMP, 0)
+    header[208:216] = b"MAP \x44\x44\x00\x00"
+    struct.pack_into("<f", header, 216, statistics[3])
+    struct.pack_into("<i", header, 220, 1)
+    header[224:304] = _LABEL.ljust(80)
+    return header
+
+
+# dtype of a raw movie -> (bytes of an element, the mode None stands for, {mode: (lowest, highest) accepted value})
+_ENCODE = {torch.uint8: (1, 0, {0: (0, 255), 101: (0, 15)}),
+           torch.int16: (2, 1, {1: (-32768, 32767), 6: (0, 32767), 0: (-128, 127), 101: (0, 15)})}
+_CHUNK_BYTES = 64 << 20  # of the payload, per device-to-host copy of write_mrc_raw
+
+
+def _check_encode_args(movie, mode, flip_rows, return_statistics=False):
+    """Every argument rule of encode_mrc_raw -> (t, h, w, mode) as Python ints; ValueError otherwise."""
+    if not isinstance(movie, torch.Tensor) or movie.dim() not in (2, 3) or movie.dtype not in _ENCODE:
+        raise ValueError("movie must be a (t, h, w) or (h, w) tensor of dtype uint8 or int16, got "
+                         f"{getattr(movie, 'dtype', type(movie).__name__)} {tuple(getattr(movie, 'shape', ()))}")
+    if movie.numel() == 0:
+        raise ValueError(f"movie must not be empty, got shape {tuple(movie.shape)}")
+    _, default, modes = _ENCODE[movie.dtype]
+    if mode is None:
+        mode = default
+    try:
+        known = not isinstance(mode, bool) and operator.index(mode) in modes
+    except TypeError:
+        known = False
+    if not known:
+        raise ValueError(f"mode must be None or one of {', '.join(str(m) for m in modes)} for a movie of "
+                         f"{movie.dtype}, got {mode!r}")
+    for name, v in (("flip_rows", flip_rows), ("return_statistics", return_statistics)):
+        if not isinstance(v, bool):
+            raise ValueError(f"{name} must be a bool, got {v!r}")
+    h, w = movie.shape[-2:]
+    if h * w >= 2**31:
+        raise ValueError(f"shape {tuple(movie.shape)}: frames of 2^31 samples and more are not supported")
+    return (movie.shape[0] if movie.dim() == 3 else 1), h, w, operator.index(mode)
+
+
+def _scratch_bytes(elem_bytes, t, h, w):
+    """csrc/mrc_encode.h's scratch rule: 40 bytes per workgroup, at most 1024 workgroups of 256 per frame"""
+    return t * min(1024, -(-h * (w * elem_bytes // 16 + 2) // 256)) * 40
+
+
+def _encode(movie, t, h, w, mode, flip_rows, device, out=None):
+    """The checked arguments encoded -> (the payload on the device, the (t, 5) int64 statistics on the CPU).
+    `out`: a uint8 buffer of the payload's size to encode into (the tests' guarded buffers)."""
+    dev = require_gpu(device if device is not None else movie.device)
+    elem = _ENCODE[movie.dtype][0]
+    nbytes = t * h * _row_bytes(mode, w)
+    with device_scope(dev):
+        src = movie.detach().to(dev).contiguous()
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        assert out.dtype == torch.uint8 and out.shape == (nbytes,) and out.device == dev
+        table = torch.empty((t, 5), dtype=torch.int64, device=dev)
+        scratch = torch.empty(_scratch_bytes(elem, t, h, w) // 8, dtype=torch.int64, device=dev)
+        check(load().mc_mrc_encode(ptr(src), elem, t, h, w, mode, int(flip_rows), ptr(out), nbytes, ptr(table),
+                                   ptr(scratch), scratch.numel() * 8, stream_ptr(dev)), "mc_mrc_encode")
+        table = table.cpu()
+    return out, table
+
+
+def _refuse_out_of_range(table, dtype, mode):
+    """ValueError when the statistics count samples outside the mode's range."""
+    bad = sum(table[:, 4].tolist())
+    if bad:
+        lo, hi = _ENCODE[dtype][2][mode]
+        raise ValueError(f"mode {mode} holds values {lo} .. {hi}: {bad} samples of the movie lie outside (its minimum "
+                         f"is {min(table[:, 0].tolist())}, its maximum {max(table[:, 1].tolist())})")
+
+
+def _header_statistics(table, frame_samples):
+    """The (t, 5) statistics combined in Python integers -> (dmin, dmax, dmean, rms), rms the root of the mean squared
+    deviation from dmean as write_mrc defines it: each the correctly rounded double of an exact rational."""
+    rows = table.tolist()
+    n = len(rows) * frame_samples
+    total, squares = sum(r[2] for r in rows), sum(r[3] for r in rows)
+    return (float(min(r[0] for r in rows)), float(max(r[1] for r in rows)), total / n,
+            math.sqrt((squares * n - total * total) / (n * n)))
+
+
+def encode_mrc_raw(movie, mode=None, flip_rows=False, return_statistics=False, device=None):
+    """A raw movie encoded as MRC sample rows -> ``MrcMovie``: the inverse of ``decode_mrc_raw`` for the integer
+    types, and what ``write_mrc_raw`` puts into a file.
+
+    ``movie``: ``(t, h, w)``, or ``(h, w)`` for one image; ``torch.uint8`` or ``int16``, CPU or GPU, any strides (it
+    is made contiguous).  ``mode`` (None: 0 for uint8, 1 for int16):
+
+      uint8   0    the bytes, marked unsigned (``unsigned_bytes=True``: IMOD's convention, as ``read_mrc`` takes it)
+      uint8   101  4-bit; values 0 .. 15
+      int16   1    int16
+      int16   6    uint16; values 0 .. 32767
+      int16   0    signed bytes, the MRC2014 rule; values -128 .. 127
+      int16   101  4-bit; values 0 .. 15
+
+    Mode 101 packs two pixels per byte, a row of ``(w + 1) // 2`` bytes, pixel 2k the low and pixel 2k + 1 the high
+    nibble of byte k, the last high nibble of a row of odd ``w`` 0 (csrc/mrc_encode.h states the rule and what it rests
+    on).  ``flip_rows=True`` writes every frame's rows in reverse order, the inverse of the decoder's option.
+
+    One pass on the GPU (mc_mrc_encode) packs the samples and gathers, exactly in 64-bit integers, each frame's
+    minimum, maximum, sum, sum of squares and the count of samples outside the mode's range.  A movie with such
+    samples is a ValueError that names the mode, the count and the movie's minimum and maximum; nothing is wrapped
+    silently.  The returned movie has ``data`` = the payload, 1-D uint8 on the GPU, ``offset`` 0, ``shape``
+    ``(t, h, w)``, ``mode``, ``swap=False``, ``unsigned_bytes`` True exactly for uint8 -> mode 0 and
+    ``pixel_spacing=None``; ``.decode()`` gives the movie back: int16 for modes 1, 6 and the signed mode 0, uint8 for
+    the unsigned mode 0 and mode 101.  ``return_statistics=True``: ``(movie, table)`` with the ``(t, 5)`` int64 table
+    of the five statistics on the CPU.  There is one device-to-host read, of that table.
+
+    Every argument rule is a ValueError raised before any device is touched.  ``device``: the GPU to encode on (None:
+    the device of ``movie``, the current GPU for a CPU tensor)."""
+    t, h, w, mode = _check_encode_args(movie, mode, flip_rows, return_statistics)
+    payload, table = _encode(movie, t, h, w, mode, flip_rows, device)
+    _refuse_out_of_range(table, movie.dtype, mode)
+    out = MrcMovie(data=payload, offset=0, shape=(t, h, w), mode=mode, swap=False,
+                   unsigned_bytes=movie.dtype == torch.uint8 and mode == 0, pixel_spacing=None)
+    return (out, table) if return_statistics else out
+
+
+def write_mrc_raw(path, movie, pixel_spacing, mode=None, flip_rows=False, device=None):
+    """A raw movie (uint8 or int16, ``(t, h, w)`` or ``(h, w)``, CPU or GPU) written as a little-endian MRC2014 file
+    of ``mode`` 0, 1, 6 or 101: ``encode_mrc_raw(movie, mode, flip_rows, device=device)`` on the GPU, then host code
+    for the header and the file.  Returns ``path``.
+
+    The header is ``write_mrc``'s, with the mode, with dmin, dmax, dmean and rms from the pass's exact integer
+    statistics combined in Python integers (rms: the root of the mean squared deviation), and, for uint8 -> mode 0,
+    imodStamp 1146047817 with imodFlags 0, so that ``read_mrc`` and IMOD take the bytes as unsigned.  The payload
+    comes to the host in chunks of whole frames of about 64 MiB; there is no second copy of the movie on the host.
+    A movie that is refused -- an argument rule, or samples outside the mode's range -- leaves nothing at ``path``.
+    ``read_mrc`` reads what this writes."""
+    _check_pixel_spacing(pixel_spacing)
+    encoded, table = encode_mrc_raw(movie, mode=mode, flip_rows=flip_rows, return_statistics=True, device=device)
+    t, h, w = encoded.shape
+    header = _header(encoded.shape, encoded.mode, pixel_spacing, _header_statistics(table, h * w),
+                     encoded.unsigned_bytes)
+    frame_bytes = encoded.data.numel() // t
+    frames = max(1, _CHUNK_BYTES // frame_bytes)
+    with open(path, "wb") as fh:
+        fh.write(header)
+        for f in range(0, t, frames):
+            fh.write(memoryview(encoded.data[f * frame_bytes:(f + frames) * frame_bytes].cpu().numpy()))
     return path
