@@ -790,6 +790,22 @@ int mc_mrc_encode(const void* movie, int elem_bytes, int t, int h, int w, int mo
  * h * w >= 2^31. */
 int mc_raw_orient(const void* in, int elem_bytes, int n, int h, int w, int rot90, int flip, void* out, void* stream);
 
+/* nframes frames resampled through a 2 x 2 linear map about their centre, bicubic (magnification distortion
+ * correction; the rule is stated in csrc/affine_resample.h).  src (device): contiguous (nframes, h, w) samples of
+ * `storage` MC_STORE_F32 or MC_STORE_F16; dst (device): (nframes, h, w) fp32, a buffer that does not overlap src.
+ * m (host, read before the call returns): m00, m01, m10, m11 in (y, x) order.  Output pixel (y, x) samples the frame at
+ * py = (cy + m00 (y - cy)) + m01 (x - cx), px = (cx + m10 (y - cy)) + m11 (x - cx), cy = h / 2, cx = w / 2, evaluated
+ * in float64 on the device; a position outside [0, h - 1] x [0, w - 1] gives fill_value, any other the 4 x 4 Keys
+ * (A = -0.75) sum in fp32 with the fractions rounded to fp32 and taps outside the frame clamped to its edge.  One
+ * 64 x 64 output tile per workgroup, its source window staged in LDS; no scratch, no atomics, results independent of
+ * scheduling; the identity returns the input's values exactly.
+ * Before anything is launched: MC_ERR_ARG for null pointers, nframes < 1, h < 4 or w < 4, a value of m that is not
+ * finite, a row sum |m00| + |m01| or |m10| + |m11| outside [0.8, 1.25] (the bound the window's size rests on), a
+ * misaligned src or dst and byte ranges of src and dst that overlap; MC_ERR_UNSUPPORTED for another storage and for
+ * h * w >= 2^31. */
+int mc_affine_resample(const void* src, int storage, int nframes, int h, int w, const double m[4] /* host */,
+                       float fill_value, float* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

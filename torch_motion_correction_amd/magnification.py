@@ -1,0 +1,135 @@
+"""Anisotropic magnification distortion correction of sums and stacks (mc_affine_resample, csrc/affine_resample.hip
+over csrc/affine_resample.h): what MotionCor2's ``-Mag major minor angle``, cisTEM / Unblur and RELION do at this stage.
+
+THE CONVENTION.  The distortion stretches the image by ``major_scale`` along the direction at ``major_axis_angle``
+degrees, measured from +x (columns) towards +y (rows) of the array, and by ``minor_scale`` across it.  With
+u = (cos, sin) of that angle as (x, y) components, D = major_scale * u u^T + minor_scale * (I - u u^T) in (x, y) order;
+the corrected image samples the distorted one at c + D (p - c), c = (h // 2, w // 2), so that content stretched by
+``major_scale`` along the angle returns to scale 1.  M is D rewritten in (y, x) order.  This is the package's OWN sign
+and angle convention: it has not been checked against output of MotionCor2 or cisTEM, none of which was available where
+this was written.  The resampling rule itself is stated once, in csrc/affine_resample.h.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, engine
+from ._lib import check, ptr, require_gpu, stream_ptr
+from .api import _on_gpu, _out_device
+
+SCALE_MIN, SCALE_MAX = 0.9, 1.1  # of major_scale and minor_scale; bounds the source footprint of an output tile
+
+
+def _real(value, name):
+    """A finite real number (no bool, no tensor-likes that float() refuses) -> float; ValueError otherwise."""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} must be a finite real number, got {value!r}")
+    v = float(value)
+    if not math.isfinite(v):
+        raise ValueError(f"{name} must be a finite real number, got {value!r}")
+    return v
+
+
+def _check_parameters(major_scale, minor_scale, major_axis_angle):
+    major, minor = _real(major_scale, "major_scale"), _real(minor_scale, "minor_scale")
+    angle = _real(major_axis_angle, "major_axis_angle")
+    for name, v in (("major_scale", major), ("minor_scale", minor)):
+        if not SCALE_MIN <= v <= SCALE_MAX:
+            raise ValueError(f"{name} must lie in [{SCALE_MIN}, {SCALE_MAX}], got {v!r}")
+    return major, minor, angle
+
+
+def magnification_distortion_matrix(major_scale, minor_scale, major_axis_angle):
+    """The (2, 2) float64 matrix M, in (y, x) order, that ``correct_magnification_distortion`` resamples through:
+    output pixel p samples the input at c + M (p - c), c = (h // 2, w // 2).  Host only.
+
+    ``major_scale``, ``minor_scale``: the distortion's magnification along and across the major axis, each in
+    [0.9, 1.1].  ``major_axis_angle``: degrees from +x (columns) towards +y (rows) of the array.  In (x, y) order
+    D = major_scale * u u^T + minor_scale * (I - u u^T) with u = (cos, sin) of the angle; M is D with its axes
+    swapped: M[0, 0] = D_yy, M[0, 1] = M[1, 0] = D_xy, M[1, 1] = D_xx.  The angle and the angle + 180 degrees, and
+    (major, minor, angle) and (minor, major, angle + 90 degrees), give the same matrix.  This is the package's own
+    sign and angle convention, not checked against MotionCor2 or cisTEM output (none was available).
+
+    A bool, a value that is not a finite real number and a scale outside [0.9, 1.1] raise ValueError naming the
+    argument."""
+    major, minor, angle = _check_parameters(major_scale, minor_scale, major_axis_angle)
+    # u u^T from cos(2 a), sin(2 a) of the angle reduced into (-180, 180): a and a + 180 reduce to the same value, and
+    # at a = 0 the products below are exactly 1, 0, 0, so that axis' scale alone changes and the other stays `minor`
+    a2 = math.radians(2.0 * math.fmod(angle, 180.0))
+    c2, s2 = math.cos(a2), math.sin(a2)
+    cc, ss, sc = 0.5 * (1.0 + c2), 0.5 * (1.0 - c2), 0.5 * s2
+    d = major - minor
+    # D = minor I + (major - minor) u u^T in (x, y) order
+    dxx, dyy, dxy = minor + d * cc, minor + d * ss, d * sc
+    return torch.tensor([[dyy, dxy], [dxy, dxx]], dtype=torch.float64)
+
+
+def _check_image(image):
+    if not isinstance(image, torch.Tensor) or image.dim() not in (2, 3) or \
+            image.dtype not in (torch.float32, torch.float16):
+        raise ValueError("image must be an (h, w) or (t, h, w) tensor of dtype float32 or float16, got "
+                         f"{getattr(image, 'dtype', type(image).__name__)} {tuple(getattr(image, 'shape', ()))}")
+    if image.numel() == 0:
+        raise ValueError(f"image must not be empty, got shape {tuple(image.shape)}")
+    h, w = image.shape[-2:]
+    if h < 4 or w < 4:
+        raise ValueError(f"image must have at least 4 rows and 4 columns, got shape {tuple(image.shape)}")
+    if h * w >= 2**31:
+        raise ValueError(f"image shape {tuple(image.shape)}: frames of 2^31 samples and more are not supported")
+
+
+def _resample(src, matrix, fill_value, out=None):
+    """The (t, h, w) stack `src` on the current GPU through mc_affine_resample -> (t, h, w) fp32, in chunks of frames
+    by the workspace rule (engine._chunks over an output frame's bytes).  Chunks are independent: the result does not
+    depend on their size.  `out`: the buffer to write (the tests' guarded buffers)."""
+    lib = _lib.load()
+    t, h, w = src.shape
+    if out is None:
+        out = torch.empty((t, h, w), dtype=torch.float32, device=src.device)
+    assert out.dtype == torch.float32 and out.shape == src.shape and out.device == src.device and out.is_contiguous()
+    m = (C.c_double * 4)(*(float(v) for v in matrix.reshape(-1).tolist()))
+    _, spans = engine._chunks(t, h * w * 4)
+    for a, n in spans:
+        check(lib.mc_affine_resample(ptr(src[a:a + n]), engine.storage_of(src), n, h, w, m, fill_value,
+                                     ptr(out[a:a + n]), stream_ptr(src.device)), "mc_affine_resample")
+    return out
+
+
+@_on_gpu
+def _correct(image, matrix, fill_value, device=None):
+    out_dev = _out_device(image, device)
+    dev = require_gpu(out_dev)
+    src = image.detach().to(dev).contiguous()
+    out = _resample(src if src.dim() == 3 else src[None], matrix, fill_value)
+    return (out if image.dim() == 3 else out[0]).to(out_dev)
+
+
+def correct_magnification_distortion(image, major_scale, minor_scale, major_axis_angle, fill_value=0.0, device=None):
+    """A sum ``(h, w)`` or a stack ``(t, h, w)`` with the microscope's anisotropic magnification distortion removed
+    -> float32 of the same shape.  Correct the sums, or the aligned stack, after motion correction and before CTF
+    estimation.
+
+    ``image``: float32 or float16 (read from its bytes; the result is that of the up-cast input, bit for bit), CPU or
+    GPU, h, w >= 4.  ``major_scale``, ``minor_scale``, ``major_axis_angle``: the distortion as
+    ``magnification_distortion_matrix`` takes it -- the magnification along and across the major axis, each in
+    [0.9, 1.1], and the axis' angle in degrees from +x towards +y of the array; the package's own convention, not
+    checked against MotionCor2 or cisTEM output.  Output pixel p is the input sampled at c + M (p - c),
+    c = (h // 2, w // 2): the position in float64 on the device, 4 x 4 bicubic (Keys, A = -0.75, the weights of the
+    package's warps) in fp32 with taps beyond the edge clamped to it; a position outside [0, h - 1] x [0, w - 1]
+    gives ``fill_value`` (csrc/affine_resample.h states the rule).  Scales of 1 still run the kernel and return the
+    input's values exactly.  Frames are independent; a stack beyond the engine's workspace rule goes through in
+    chunks of frames, with the same result.
+
+    The result is on ``device`` if given, else on the device of ``image``; a CPU image is staged to the current GPU
+    and the result copied back.  There is no CPU fallback.  Every argument rule -- a bool or a value that is not a
+    finite real number for a parameter or ``fill_value``, a scale outside [0.9, 1.1], an ``image`` that is not a 2-
+    or 3-dimensional float32 / float16 tensor -- is a ValueError naming the argument, raised before any device is
+    touched."""
+    _check_image(image)
+    matrix = magnification_distortion_matrix(major_scale, minor_scale, major_axis_angle)
+    return _correct(image, matrix, _real(fill_value, "fill_value"), device=device)
