@@ -10,32 +10,8 @@ import re
 import pytest
 import torch
 
+from crop_reference import band_limited, crop64 as crop_ref  # noqa: F401  (tests/test_fourier_crop.py imports them here)
 from torch_motion_correction_amd import _lib
-
-
-def crop_ref(x):
-    """The definition, in float64 on the CPU: rows -h/4 <= ky < h/4 (signed; the new Nyquist row from the negative
-    side) and columns 0 <= kx <= w/4 of rfft2(x), inverted at (h/2, w/2); irfft2's 1 / ((h/2)(w/2)) is the only
-    scale.  One frame at a time (an 8184 x 11520 spectrum is 754 MB in complex128)."""
-    x = x.detach().cpu()
-    if x.dim() == 3:
-        return torch.stack([crop_ref(f) for f in x])
-    x = x.double()
-    h, w = x.shape
-    h2, w2 = h // 2, w // 2
-    F = torch.fft.rfft2(x)
-    G = torch.cat((F[: h2 // 2, : w2 // 2 + 1], F[h - h2 // 2:, : w2 // 2 + 1]), dim=0)
-    return torch.fft.irfft2(G, s=(h2, w2))
-
-
-def band_limited(h, w, seed, t=None):
-    """float64 frames whose spectrum is zero at and beyond the Nyquist frequencies of the (h/2, w/2) grid."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn((h, w) if t is None else (t, h, w), generator=g, dtype=torch.float64)
-    F = torch.fft.rfft2(x)
-    F[..., h // 4: h - h // 4 + 1, :] = 0  # |ky| >= h/4
-    F[..., :, w // 4:] = 0  # kx >= w/4
-    return torch.fft.irfft2(F, s=(h, w))
 
 
 def _defaults(fn):

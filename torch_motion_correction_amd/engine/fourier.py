@@ -104,10 +104,14 @@ def _fourier_shift_row_major(img, shifts):
 
 
 def _rows_forward(src, first, n, S):
-    """mc_full_rows_forward of the fp32 frames first .. first+n-1 of `src` (t, h, w) into S (chunk, h, pitch, 2)."""
+    """mc_full_rows_forward of the fp32 frames first .. first+n-1 of `src` (t, h, w) into S (chunk, h, pitch, 2).
+    The row pass reads its samples in pairs and refuses a pointer that is not 8-byte aligned: a stack that starts
+    4 bytes off (a view into a larger buffer) is copied, these n frames at a time, into an aligned one."""
     lib = _lib.load()
     _, h, w = src.shape
     dev = src.device
+    if src.data_ptr() % 8:
+        src, first = src[first:first + n].clone(), 0
     off = torch.arange(first, first + n, device=dev, dtype=torch.int64) * (h * w)
     check(lib.mc_full_rows_forward(ptr(src), ptr(off), w, ptr(S), ptr(planmod.get_twiddles(w, dev)), n, h, w,
                                    S.shape[2], stream_ptr(dev)), "mc_full_rows_forward")
