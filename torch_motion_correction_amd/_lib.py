@@ -6,6 +6,7 @@ caller gets an exception.  Nothing here touches the oracle.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import operator
 import os
@@ -226,3 +227,26 @@ def require_gpu(device=None) -> torch.device:
         return torch.device("cuda", torch.cuda.current_device())
     d = torch.device(device)
     return d if d.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+@contextlib.contextmanager
+def gpu_entry(first, device=None):
+    """The device prelude of an API entry point: ``with gpu_entry(image, device) as (out_dev, dev):``.  `out_dev`,
+    where the results go, is `device` if given, else the device of `first` (the reference's ``device=None`` ->
+    ``image.device``); `dev` = ``require_gpu(out_dev)`` is the GPU that computes, and the body runs with it as the
+    current HIP device (``device_scope``).  A `first` that is no tensor, without a `device`, targets the current
+    device.  Without a GPU this raises McorrError and enters no scope: an entry point's argument rules stand BEFORE
+    the ``with``."""
+    out_dev = first.device if device is None and isinstance(first, torch.Tensor) else device
+    dev = require_gpu(out_dev)
+    with device_scope(dev):
+        yield (dev if out_dev is None else torch.device(out_dev)), dev
+
+
+def say(msg: str):
+    """A progress line of the reference, printed when ``api.VERBOSE`` is set (read at the call: the switch is assigned
+    on `api`)."""
+    from . import api
+
+    if api.VERBOSE:
+        print(msg)

@@ -17,31 +17,21 @@ peaks).  Q4-Q9 are plain semantics and are always reproduced.
 
 from __future__ import annotations
 
-import functools
-import inspect
 import math
 
 import torch
 
 from . import engine
-from ._lib import McorrUnsupported, device_scope, normalize_frame_index, require_gpu
+from ._lib import McorrUnsupported, gpu_entry, normalize_frame_index, say
+from ._lib import device_scope, require_gpu  # noqa: F401  (unused here; host tests patch these names on `api`)
 
 BUG_COMPATIBLE = True
 RIGID_FAST_PATH = True  # (2,nt,1,1) fields use the separable rigid warp kernel
-VERBOSE = False  # the reference prints progress lines; opt in with VERBOSE = True
-
-
-def _say(msg: str):
-    if VERBOSE:
-        print(msg)
+VERBOSE = False  # the reference prints progress lines (_lib.say); opt in with VERBOSE = True
 
 
 def _is_rigid(field: torch.Tensor) -> bool:
     return tuple(field.shape[-2:]) == (1, 1)
-
-
-def _out_device(image: torch.Tensor, device):
-    return image.device if device is None else torch.device(device)
 
 
 def _stage(x: torch.Tensor, dev, keep_half: bool = False) -> torch.Tensor:
@@ -53,34 +43,19 @@ def _stage(x: torch.Tensor, dev, keep_half: bool = False) -> torch.Tensor:
     return x.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
-def _on_gpu(fn):
-    """Run `fn` with the GPU it computes on as the CURRENT HIP device (libmcorr launches on the
-    current device; the reference takes ``device=`` / the first tensor's device per call).  The
-    device is chosen exactly as the body does: ``device`` if given, else the first argument's."""
-    sig = inspect.signature(fn)
-
-    @functools.wraps(fn)
-    def scoped(*args, **kwargs):
-        bound = sig.bind(*args, **kwargs)
-        first = next(iter(bound.arguments.values()))
-        device = bound.arguments.get("device")
-        out_dev = first.device if device is None and isinstance(first, torch.Tensor) else device
-        with device_scope(require_gpu(out_dev)):
-            return fn(*args, **kwargs)
-
-    return scoped
-
+# Every entry point computes under ``with gpu_entry(first, device) as (out_dev, dev):`` (_lib): libmcorr launches on
+# the current HIP device, the reference takes ``device=`` / the first tensor's device per call.  Where a function has
+# argument rules of its own that are promised "before any device is touched", they stand before the ``with``; every
+# other function opens with it, and so needs a GPU before its body refuses anything.
 
 # ------------------------------------------------------------------ raw movies: one route
 RAW_DTYPES = (torch.uint8, torch.int16)  # storage the fused kernels (engine.RawMovie) read
 
 
-def _stage_raw(movie, gain, device):
-    """Staging of every raw entry point -> (result device, GPU, the movie on the GPU in its own storage type, the
-    gain on the GPU or None)."""
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    return out_dev, dev, movie.detach().to(dev), None if gain is None else gain.to(dev)
+def _stage_raw(movie, gain, dev):
+    """Staging of every raw entry point -> (the movie on the GPU `dev` in its own storage type, the gain there or
+    None)."""
+    return movie.detach().to(dev), None if gain is None else gain.to(dev)
 
 
 def _raw_or_conditioned(raw, gd, mean_zero, thr, fused, conditioned, allow_fused=True):
@@ -142,63 +117,55 @@ def image_shifts_to_deformation_field(shifts, pixel_spacing, device=None):
     return (shifts * pixel_spacing).transpose(0, 1)[:, :, None, None]
 
 
-@_on_gpu
 def evaluate_deformation_field(deformation_field, tyx, grid_type="catmull_rom"):
     """(c,nt,nh,nw) spline grid evaluated at (...,3) tyx points in [0,1] -> (...,c)
     (deformation_field_utils.py:9-39): one launch over all points (mc_spline_points)."""
-    out_dev = deformation_field.device
-    dev = require_gpu(out_dev)
-    field = _stage(deformation_field, dev)
-    vals = engine.spline_points(field, tyx.reshape(-1, 3), grid_type)
-    return vals.reshape(*tyx.shape[:-1], field.shape[0]).to(out_dev)
+    with gpu_entry(deformation_field) as (out_dev, dev):
+        field = _stage(deformation_field, dev)
+        vals = engine.spline_points(field, tyx.reshape(-1, 3), grid_type)
+        return vals.reshape(*tyx.shape[:-1], field.shape[0]).to(out_dev)
 
 
-@_on_gpu
 def evaluate_deformation_field_at_t(deformation_field, t, grid_shape, grid_type="catmull_rom"):
     """(c, H, W) shifts on the linspace(0,1) lattice at time t
     (deformation_field_utils.py:42-93)."""
-    out_dev = deformation_field.device
-    dev = require_gpu(out_dev)
-    H, W = grid_shape
-    lat = engine.spline_lattice(_stage(deformation_field, dev),
-                                torch.as_tensor([float(t)], dtype=torch.float32),
-                                torch.linspace(0, 1, steps=H), torch.linspace(0, 1, steps=W), grid_type)
-    return lat[:, 0].to(out_dev)
+    with gpu_entry(deformation_field) as (out_dev, dev):
+        H, W = grid_shape
+        lat = engine.spline_lattice(_stage(deformation_field, dev),
+                                    torch.as_tensor([float(t)], dtype=torch.float32),
+                                    torch.linspace(0, 1, steps=H), torch.linspace(0, 1, steps=W), grid_type)
+        return lat[:, 0].to(out_dev)
 
 
-@_on_gpu
 def resample_deformation_field(deformation_field, target_resolution):
     """Catmull-Rom resample to (nt,nh,nw) (deformation_field_utils.py:96-126)."""
-    out_dev = deformation_field.device
-    dev = require_gpu(out_dev)
-    nt, nh, nw = target_resolution
-    lat = engine.spline_lattice(_stage(deformation_field, dev), torch.linspace(0, 1, steps=nt),
-                                torch.linspace(0, 1, steps=nh), torch.linspace(0, 1, steps=nw),
-                                "catmull_rom")
-    return lat.to(out_dev)
+    with gpu_entry(deformation_field) as (out_dev, dev):
+        nt, nh, nw = target_resolution
+        lat = engine.spline_lattice(_stage(deformation_field, dev), torch.linspace(0, 1, steps=nt),
+                                    torch.linspace(0, 1, steps=nh), torch.linspace(0, 1, steps=nw),
+                                    "catmull_rom")
+        return lat.to(out_dev)
 
 
 # ------------------------------------------------------------------ estimators
 
 
-@_on_gpu
 def estimate_global_motion(image, pixel_spacing, reference_frame=None, b_factor=500,
                            frequency_range=(300, 10), device=None):
     """Whole-frame cross-correlation shift estimate (estimate_motion_xc.py:21-135).
     Returns the (2,t,1,1) float32 deformation field in Angstrom (integer px shifts x
     pixel_spacing; the reference frame's entry is exactly 0)."""
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    img = _stage(image, dev, keep_half=True)  # fp16 stacks: K1 reads the 16-bit samples (4096-column frames)
-    t = img.shape[0]
-    ref = t // 2 if reference_frame is None else reference_frame
-    normalize_frame_index(ref, t)  # IndexError outside [-t, t), as filtered_fft[ref] (xc.py:101)
-    _say(f"Cross-correlation whole image: using frame {ref} as reference")
-    shifts = engine.global_shifts(img, ref, float(pixel_spacing), float(b_factor), frequency_range)
-    if VERBOSE:
-        _say(f"Estimated shifts range: y=[{shifts[:, 0].min():.1f}, {shifts[:, 0].max():.1f}], "
-             f"x=[{shifts[:, 1].min():.1f}, {shifts[:, 1].max():.1f}]")
-    return image_shifts_to_deformation_field(shifts, pixel_spacing).to(out_dev)
+    with gpu_entry(image, device) as (out_dev, dev):
+        img = _stage(image, dev, keep_half=True)  # fp16 stacks: K1 reads the 16-bit samples (4096-column frames)
+        t = img.shape[0]
+        ref = t // 2 if reference_frame is None else reference_frame
+        normalize_frame_index(ref, t)  # IndexError outside [-t, t), as filtered_fft[ref] (xc.py:101)
+        say(f"Cross-correlation whole image: using frame {ref} as reference")
+        shifts = engine.global_shifts(img, ref, float(pixel_spacing), float(b_factor), frequency_range)
+        if VERBOSE:
+            say(f"Estimated shifts range: y=[{shifts[:, 0].min():.1f}, {shifts[:, 0].max():.1f}], "
+                f"x=[{shifts[:, 1].min():.1f}, {shifts[:, 1].max():.1f}]")
+        return image_shifts_to_deformation_field(shifts, pixel_spacing).to(out_dev)
 
 
 def _check_refine_call(t, reference_frame, max_iterations, convergence_threshold):
@@ -235,11 +202,18 @@ def refine_global_motion(image, pixel_spacing, deformation_field=None, reference
     if not isinstance(image, torch.Tensor) or image.dim() != 3:
         raise ValueError(f"image must be (t, h, w), got {tuple(getattr(image, 'shape', ()))}")
     t = image.shape[0]
-    ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations, convergence_threshold)
+    ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations=max_iterations,
+                                          convergence_threshold=convergence_threshold)
     if deformation_field is not None:
         _check_fast_field(deformation_field, t)
-    return _refine_global_motion(image, pixel_spacing, deformation_field, ref, b_factor, frequency_range, n_iter, thr,
-                                 bool(return_history), device)
+    want_history = bool(return_history)
+    with gpu_entry(image, device) as (out_dev, dev):
+        img = _stage(image, dev, keep_half=True)
+        ps = float(pixel_spacing)
+        shifts, hist = engine.global_shifts_refined(img, ref, ps, float(b_factor), tuple(frequency_range),
+                                                    _start_shifts(deformation_field, ps, dev), n_iter, thr)
+        field = image_shifts_to_deformation_field(shifts, pixel_spacing).to(out_dev)
+        return (field, hist) if want_history else field
 
 
 def _start_shifts(deformation_field, ps, dev):
@@ -247,19 +221,6 @@ def _start_shifts(deformation_field, ps, dev):
     if deformation_field is None:
         return None
     return (deformation_field.detach().to(device=dev, dtype=torch.float32)[:, :, 0, 0].transpose(0, 1) / ps).contiguous()
-
-
-@_on_gpu
-def _refine_global_motion(image, pixel_spacing, deformation_field, ref, b_factor, frequency_range, n_iter, thr,
-                          want_history, device):
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    img = _stage(image, dev, keep_half=True)
-    ps = float(pixel_spacing)
-    shifts, hist = engine.global_shifts_refined(img, ref, ps, float(b_factor), tuple(frequency_range),
-                                                _start_shifts(deformation_field, ps, dev), n_iter, thr)
-    field = image_shifts_to_deformation_field(shifts, pixel_spacing).to(out_dev)
-    return (field, hist) if want_history else field
 
 
 def refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field=None, reference_frame=None, b_factor=500,
@@ -275,23 +236,21 @@ def refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field=None,
     thr_hot = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # every argument rule before any device
     _check_raw_args(movie, gain)
     t = movie.shape[0]
-    ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations, convergence_threshold)
+    ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations=max_iterations,
+                                          convergence_threshold=convergence_threshold)
     if deformation_field is not None:
         _check_fast_field(deformation_field, t)
-    return _refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field, ref, b_factor, frequency_range,
-                                     mean_zero, thr_hot, n_iter, thr, bool(return_history), device)
-
-
-@_on_gpu
-def _refine_global_motion_raw(movie, gain, pixel_spacing, deformation_field, ref, b_factor, frequency_range, mean_zero,
-                              thr_hot, n_iter, thr, want_history, device):
-    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
-    ps = float(pixel_spacing)
-    args = (ref, ps, float(b_factor), tuple(frequency_range), _start_shifts(deformation_field, ps, dev), n_iter, thr)
-    res, _ = _raw_or_conditioned(raw, gd, mean_zero, thr_hot, lambda rm: engine.global_shifts_raw_refined(rm, *args),
-                                 lambda img: engine.global_shifts_refined(img, *args))
-    field = image_shifts_to_deformation_field(res[0], pixel_spacing).to(out_dev)
-    return (field, res[1]) if want_history else field
+    want_history = bool(return_history)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        ps = float(pixel_spacing)
+        args = (ref, ps, float(b_factor), tuple(frequency_range), _start_shifts(deformation_field, ps, dev), n_iter,
+                thr)
+        res, _ = _raw_or_conditioned(raw, gd, mean_zero, thr=thr_hot,
+                                     fused=lambda rm: engine.global_shifts_raw_refined(rm, *args),
+                                     conditioned=lambda img: engine.global_shifts_refined(img, *args))
+        field = image_shifts_to_deformation_field(res[0], pixel_spacing).to(out_dev)
+        return (field, res[1]) if want_history else field
 
 
 def _check_local_refine_call(movie, patch_sidelength, deformation_field, reference_frame, max_iterations,
@@ -301,7 +260,8 @@ def _check_local_refine_call(movie, patch_sidelength, deformation_field, referen
     if not isinstance(movie, torch.Tensor) or movie.dim() != 3:
         raise ValueError(f"{what} must be (t, h, w), got {tuple(getattr(movie, 'shape', ()))}")
     t, h, w = movie.shape
-    ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations, convergence_threshold)
+    ref, n_iter, thr = _check_refine_call(t, reference_frame, max_iterations=max_iterations,
+                                          convergence_threshold=convergence_threshold)
     p = _check_patch_sidelength(patch_sidelength, (h, w))
     if deformation_field is not None:
         _check_field_4d(deformation_field, "deformation_field must be a (2, nt, gh, gw) tensor")
@@ -343,22 +303,16 @@ def refine_local_motion(image, pixel_spacing, patch_sidelength=1024, deformation
 
     `reference_frame` follows Python indexing (None: t // 2; outside [-t, t): IndexError).  Argument errors are raised
     before any device is touched.  At most 512 frames."""
-    p, ref, n_iter, thr = _check_local_refine_call(image, patch_sidelength, deformation_field, reference_frame,
-                                                   max_iterations, convergence_threshold, "image")
-    return _refine_local_motion(image, pixel_spacing, p, deformation_field, ref, b_factor, frequency_range, n_iter,
-                                thr, bool(return_history), device)
-
-
-@_on_gpu
-def _refine_local_motion(image, pixel_spacing, p, deformation_field, ref, b_factor, frequency_range, n_iter, thr,
-                         want_history, device):
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    img = _stage(image, dev, keep_half=True)
-    ps = float(pixel_spacing)
-    field = None if deformation_field is None else _stage(deformation_field, dev)
-    res = engine.local_shifts_refined(img, ps, p, field, ref, float(b_factor), tuple(frequency_range), n_iter, thr)
-    return _local_refine_result(res, ps, want_history, out_dev)
+    p, ref, n_iter, thr = _check_local_refine_call(
+        image, patch_sidelength, deformation_field, reference_frame=reference_frame, max_iterations=max_iterations,
+        convergence_threshold=convergence_threshold, what="image")
+    want_history = bool(return_history)
+    with gpu_entry(image, device) as (out_dev, dev):
+        img = _stage(image, dev, keep_half=True)
+        ps = float(pixel_spacing)
+        field = None if deformation_field is None else _stage(deformation_field, dev)
+        res = engine.local_shifts_refined(img, ps, p, field, ref, float(b_factor), tuple(frequency_range), n_iter, thr)
+        return _local_refine_result(res, ps, want_history=want_history, out_dev=out_dev)
 
 
 def refine_local_motion_raw(movie, gain, pixel_spacing, patch_sidelength=1024, deformation_field=None,
@@ -376,23 +330,21 @@ def refine_local_motion_raw(movie, gain, pixel_spacing, patch_sidelength=1024, d
     Every other case runs exactly condition_movie followed by refine_local_motion."""
     thr_hot = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # every argument rule before any device
     _check_raw_args(movie, gain)
-    p, ref, n_iter, thr = _check_local_refine_call(movie, patch_sidelength, deformation_field, reference_frame,
-                                                   max_iterations, convergence_threshold, "movie")
-    return _refine_local_motion_raw(movie, gain, pixel_spacing, p, deformation_field, ref, b_factor, frequency_range,
-                                    n_iter, thr, bool(return_history), device, mean_zero, thr_hot)
-
-
-@_on_gpu
-def _refine_local_motion_raw(movie, gain, pixel_spacing, p, deformation_field, ref, b_factor, frequency_range, n_iter,
-                             thr, want_history, device, mean_zero, thr_hot):
-    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
-    ps = float(pixel_spacing)
-    field = None if deformation_field is None else _stage(deformation_field, dev)
-    args = (ps, p, field, ref, float(b_factor), tuple(frequency_range), n_iter, thr)
-    # (the engine refuses a hot-pixel threshold)
-    res, _ = _raw_or_conditioned(raw, gd, mean_zero, thr_hot, lambda rm: engine.local_shifts_raw_refined(rm, *args),
-                                 lambda img: engine.local_shifts_refined(img, *args), allow_fused=thr_hot is None)
-    return _local_refine_result(res, ps, want_history, out_dev)
+    p, ref, n_iter, thr = _check_local_refine_call(
+        movie, patch_sidelength, deformation_field, reference_frame=reference_frame, max_iterations=max_iterations,
+        convergence_threshold=convergence_threshold, what="movie")
+    want_history = bool(return_history)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        ps = float(pixel_spacing)
+        field = None if deformation_field is None else _stage(deformation_field, dev)
+        args = (ps, p, field, ref, float(b_factor), tuple(frequency_range), n_iter, thr)
+        # (the engine refuses a hot-pixel threshold)
+        res, _ = _raw_or_conditioned(raw, gd, mean_zero, thr=thr_hot,
+                                     fused=lambda rm: engine.local_shifts_raw_refined(rm, *args),
+                                     conditioned=lambda img: engine.local_shifts_refined(img, *args),
+                                     allow_fused=thr_hot is None)
+        return _local_refine_result(res, ps, want_history=want_history, out_dev=out_dev)
 
 
 def _check_patch_estimate_args(t, reference_frame, reference_strategy, sub_pixel_refinement, outlier_rejection):
@@ -410,7 +362,6 @@ def _check_patch_estimate_args(t, reference_frame, reference_strategy, sub_pixel
     return ref
 
 
-@_on_gpu
 def estimate_motion_cross_correlation_patches(
     image, pixel_spacing, reference_frame=None, reference_strategy="mean_except_current",
     b_factor=500, frequency_range=(300, 10), patch_sidelength=1024, sub_pixel_refinement=True,
@@ -420,37 +371,38 @@ def estimate_motion_cross_correlation_patches(
     """Per-patch cross-correlation shift estimate (estimate_motion_xc.py:138-411).
     Returns ((2,t,gh,gw) Angstrom field with its global mean subtracted,
     (t,gh,gw,3) int64 patch centres)."""
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    # an fp16 stack stays fp16 unless a prior field has to be applied first (that path normalises
-    # and resamples in fp32)
-    img = _stage(image, dev, keep_half=deformation_field is None)
-    t, h, w = img.shape
-    ref = _check_patch_estimate_args(t, reference_frame, reference_strategy, sub_pixel_refinement, outlier_rejection)
-    stats = engine.central_box_stats(img)  # statistics of the *uncorrected* stack (Q9)
-    field0 = None
-    if deformation_field is not None:
-        if deformation_field.device != out_dev:
-            deformation_field = deformation_field.clone()  # the reference's .to(device) copy
-        norm = engine.normalize(img, stats)
-        stats = None
-        if tuple(deformation_field.shape[-2:]) == (1, 1):
-            _say("Applying single patch deformation field using correct_motion_fast")
-            img = _correct_motion_fast_impl(norm, deformation_field, dev, mutate=BUG_COMPATIBLE)
-        else:
-            _say("Applying full deformation field using correct_motion")
-            lat = engine.frame_lattices(_stage(deformation_field, dev), t, "bspline")
-            img, _ = engine.warp(norm, lat, float(pixel_spacing))
-        # the prior field (after Q1's in-place negation, if any) is the accumulator base
-        from .lattice import patch_grid_centers
+    with gpu_entry(image, device) as (out_dev, dev):
+        # an fp16 stack stays fp16 unless a prior field has to be applied first (that path normalises
+        # and resamples in fp32)
+        img = _stage(image, dev, keep_half=deformation_field is None)
+        t, h, w = img.shape
+        ref = _check_patch_estimate_args(t, reference_frame, reference_strategy,
+                                         sub_pixel_refinement=sub_pixel_refinement,
+                                         outlier_rejection=outlier_rejection)
+        stats = engine.central_box_stats(img)  # statistics of the *uncorrected* stack (Q9)
+        field0 = None
+        if deformation_field is not None:
+            if deformation_field.device != out_dev:
+                deformation_field = deformation_field.clone()  # the reference's .to(device) copy
+            norm = engine.normalize(img, stats)
+            stats = None
+            if tuple(deformation_field.shape[-2:]) == (1, 1):
+                say("Applying single patch deformation field using correct_motion_fast")
+                img = _correct_motion_fast_impl(norm, deformation_field, dev, mutate=BUG_COMPATIBLE)
+            else:
+                say("Applying full deformation field using correct_motion")
+                lat = engine.frame_lattices(_stage(deformation_field, dev), t, "bspline")
+                img, _ = engine.warp(norm, lat, float(pixel_spacing))
+            # the prior field (after Q1's in-place negation, if any) is the accumulator base
+            from .lattice import patch_grid_centers
 
-        cy, cx = patch_grid_centers(t, h, w, int(patch_sidelength))
-        field0 = resample_deformation_field(_stage(deformation_field, dev), (t, len(cy), len(cx)))
-    field, centers = engine.patch_field(
-        img, stats, float(pixel_spacing), ref, reference_strategy, float(b_factor), frequency_range,
-        patch_sidelength, bool(sub_pixel_refinement), bool(temporal_smoothing),
-        int(smoothing_window_size), field0, bool(outlier_rejection), float(outlier_threshold))
-    return field.to(out_dev), centers.to(out_dev)
+            cy, cx = patch_grid_centers(t, h, w, int(patch_sidelength))
+            field0 = resample_deformation_field(_stage(deformation_field, dev), (t, len(cy), len(cx)))
+        field, centers = engine.patch_field(
+            img, stats, float(pixel_spacing), ref, reference_strategy, float(b_factor), frequency_range,
+            patch_sidelength, bool(sub_pixel_refinement), bool(temporal_smoothing),
+            int(smoothing_window_size), field0, bool(outlier_rejection), float(outlier_threshold))
+        return field.to(out_dev), centers.to(out_dev)
 
 
 def estimate_motion(image, pixel_spacing, patch_sidelength=None, **kwargs):
@@ -465,21 +417,19 @@ def estimate_motion(image, pixel_spacing, patch_sidelength=None, **kwargs):
 # ------------------------------------------------------------------ correctors
 
 
-@_on_gpu
 def correct_motion(image, deformation_grid, pixel_spacing, grad=False, grid_type="catmull_rom",
                    device=None):
     """Apply a (2,nt,gh,gw) Angstrom deformation field (correct_motion.py:18-78).
     Returns the (t,h,w) corrected frames, detached.  ``grad=True`` (autograd through
     the resampling) is not available on the HIP path."""
-    if grad:
-        raise NotImplementedError("grad=True is not supported by the HIP path (forward only)")
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    img = _stage(image, dev, keep_half=True)
-    lat = engine.frame_lattices(_stage(deformation_grid, dev), img.shape[0], grid_type)
-    frames, _ = engine.warp(img, lat, float(pixel_spacing), want_frames=True, want_sum=False,
-                            rigid=RIGID_FAST_PATH and _is_rigid(deformation_grid))
-    return frames.to(out_dev)
+    with gpu_entry(image, device) as (out_dev, dev):
+        if grad:
+            raise NotImplementedError("grad=True is not supported by the HIP path (forward only)")
+        img = _stage(image, dev, keep_half=True)
+        lat = engine.frame_lattices(_stage(deformation_grid, dev), img.shape[0], grid_type)
+        frames, _ = engine.warp(img, lat, float(pixel_spacing), want_frames=True, want_sum=False,
+                                rigid=RIGID_FAST_PATH and _is_rigid(deformation_grid))
+        return frames.to(out_dev)
 
 
 def _grid_data_and_type(grid, default="catmull_rom"):
@@ -500,7 +450,6 @@ def _wants_grad(grid) -> bool:
     return any(p.requires_grad for p in params()) if callable(params) else False
 
 
-@_on_gpu
 def correct_motion_two_grids(image, new_deformation_grid, base_deformation_grid, pixel_spacing, grad=True,
                              device=None):
     """correct_motion.py:188-299 -- the frames resampled through the SUM of two spline grids
@@ -509,26 +458,25 @@ def correct_motion_two_grids(image, new_deformation_grid, base_deformation_grid,
     spline package; they may differ in resolution and basis.  Forward only: with ``grad=True`` (the
     reference's default) and a grid that requires gradients the result is attached to that grid, as
     in the reference, but calling ``backward`` through it raises NotImplementedError."""
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    img = _stage(image, dev)
-    new, new_type = _grid_data_and_type(new_deformation_grid)
-    base, base_type = _grid_data_and_type(base_deformation_grid)
-    t = img.shape[0]
-    _, _, gh, gw = new.shape
-    lin = lambda n: torch.linspace(0, 1, steps=n)
-    lat = (engine.spline_lattice(_stage(new, dev), lin(t), lin(10 * gh), lin(10 * gw), new_type)
-           + engine.spline_lattice(_stage(base, dev), lin(t), lin(10 * gh), lin(10 * gw), base_type))
-    frames, _ = engine.warp(img, lat.permute(1, 0, 2, 3).contiguous(), float(pixel_spacing),
-                            want_frames=True, want_sum=False)
-    frames = frames.to(out_dev)
-    if grad and _wants_grad(new_deformation_grid):
-        # the reference returns frames attached to the new grid's graph; the forward here is the
-        # same, the backward is refused where it would be needed
-        params = ([new_deformation_grid] if isinstance(new_deformation_grid, torch.Tensor)
-                  else [p for p in new_deformation_grid.parameters() if p.requires_grad])
-        frames = _ForwardOnly.apply(frames, *params)
-    return frames
+    with gpu_entry(image, device) as (out_dev, dev):
+        img = _stage(image, dev)
+        new, new_type = _grid_data_and_type(new_deformation_grid)
+        base, base_type = _grid_data_and_type(base_deformation_grid)
+        t = img.shape[0]
+        _, _, gh, gw = new.shape
+        lin = lambda n: torch.linspace(0, 1, steps=n)
+        lat = (engine.spline_lattice(_stage(new, dev), lin(t), lin(10 * gh), lin(10 * gw), new_type)
+               + engine.spline_lattice(_stage(base, dev), lin(t), lin(10 * gh), lin(10 * gw), base_type))
+        frames, _ = engine.warp(img, lat.permute(1, 0, 2, 3).contiguous(), float(pixel_spacing),
+                                want_frames=True, want_sum=False)
+        frames = frames.to(out_dev)
+        if grad and _wants_grad(new_deformation_grid):
+            # the reference returns frames attached to the new grid's graph; the forward here is the
+            # same, the backward is refused where it would be needed
+            params = ([new_deformation_grid] if isinstance(new_deformation_grid, torch.Tensor)
+                      else [p for p in new_deformation_grid.parameters() if p.requires_grad])
+            frames = _ForwardOnly.apply(frames, *params)
+        return frames
 
 
 class _ForwardOnly(torch.autograd.Function):
@@ -544,33 +492,30 @@ class _ForwardOnly(torch.autograd.Function):
                                   "(forward only); use grad=False")
 
 
-@_on_gpu
 def correct_motion_slow(image, deformation_grid, grad=False, device=None):
     """correct_motion.py:302-427 -- the (2,nt,nh,nw) field evaluated (Catmull-Rom) at EVERY pixel
     (t_i, y/(h-1), x/(w-1)) and used as PIXEL shifts (no pixel spacing), then bicubic resampling.
     One frame at a time: the per-pixel shifts are a tensor-product spline lattice of the frame's
     own size, which the general warp kernel consumes directly (its bicubic lattice upsample is the
     identity at the lattice nodes up to 1e-4 of the shift difference between adjacent pixels)."""
-    if grad:
-        raise NotImplementedError("grad=True is not supported by the HIP path (forward only)")
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    img = _stage(image, dev)
-    field = _stage(deformation_grid, dev)
-    t, h, w = img.shape
-    times = torch.linspace(0, 1, steps=t)
-    uy = torch.arange(h, dtype=torch.float32) / float(h - 1)
-    ux = torch.arange(w, dtype=torch.float32) / float(w - 1)
-    out = torch.empty_like(img)
-    for f in range(t):
-        lat = engine.spline_lattice(field, times[f:f + 1], uy, ux, "catmull_rom")  # (2, 1, h, w)
-        frames, _ = engine.warp(img[f:f + 1], lat.permute(1, 0, 2, 3).contiguous(), 1.0,
-                                want_frames=True, want_sum=False)
-        out[f] = frames[0]
-    return out.to(out_dev)
+    with gpu_entry(image, device) as (out_dev, dev):
+        if grad:
+            raise NotImplementedError("grad=True is not supported by the HIP path (forward only)")
+        img = _stage(image, dev)
+        field = _stage(deformation_grid, dev)
+        t, h, w = img.shape
+        times = torch.linspace(0, 1, steps=t)
+        uy = torch.arange(h, dtype=torch.float32) / float(h - 1)
+        ux = torch.arange(w, dtype=torch.float32) / float(w - 1)
+        out = torch.empty_like(img)
+        for f in range(t):
+            lat = engine.spline_lattice(field, times[f:f + 1], uy, ux, "catmull_rom")  # (2, 1, h, w)
+            frames, _ = engine.warp(img[f:f + 1], lat.permute(1, 0, 2, 3).contiguous(), 1.0,
+                                    want_frames=True, want_sum=False)
+            out[f] = frames[0]
+        return out.to(out_dev)
 
 
-@_on_gpu
 def motion_correct_sum(image, deformation_grid, pixel_spacing, grid_type="catmull_rom", device=None,
                        return_frames=False, dose_per_frame=None, pre_exposure=0.0, voltage=300.0):
     """Fused correct_motion + the caller-side ``torch.sum(movie, dim=0)`` of the
@@ -578,17 +523,15 @@ def motion_correct_sum(image, deformation_grid, pixel_spacing, grid_type="catmul
     (and the frames when asked) without a second pass over the stack.  With
     ``dose_per_frame`` (e/A^2) the sum is exposure-filtered as in the reference's
     ``dose_weight`` step (examples/ttMotion.py:331-351; see ``dose_weighted_sum``)."""
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    img = _stage(image, dev, keep_half=True)
-    lat = engine.frame_lattices(_stage(deformation_grid, dev), img.shape[0], grid_type)
-    rigid = RIGID_FAST_PATH and _is_rigid(deformation_grid)
-    total, _, frames = engine.corrected_sums(img, lat, pixel_spacing, rigid, dose_per_frame, pre_exposure, voltage,
-                                             False, return_frames)
-    return (total.to(out_dev), frames.to(out_dev)) if return_frames else total.to(out_dev)
+    with gpu_entry(image, device) as (out_dev, dev):
+        img = _stage(image, dev, keep_half=True)
+        lat = engine.frame_lattices(_stage(deformation_grid, dev), img.shape[0], grid_type)
+        rigid = RIGID_FAST_PATH and _is_rigid(deformation_grid)
+        total, _, frames = engine.corrected_sums(img, lat, pixel_spacing, rigid, dose_per_frame, pre_exposure,
+                                                 voltage, False, return_frames)
+        return (total.to(out_dev), frames.to(out_dev)) if return_frames else total.to(out_dev)
 
 
-@_on_gpu
 def condition_movie(movie, gain=None, mean_zero=True, device=None, hot_pixel_threshold=None,
                     return_hot_counts=False):
     """Raw detector frames -> the fp32 stack the estimators expect: ``movie * gain`` (a (h,w)
@@ -601,13 +544,12 @@ def condition_movie(movie, gain=None, mean_zero=True, device=None, hot_pixel_thr
     is replaced by the mean of its neighbours that are not hot (the example draws a RANDOM
     neighbour: that part has no deterministic counterpart and the rule here is ours).
     `return_hot_counts`: also the (t,) int32 number of hot pixels found per frame."""
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    res = engine.condition_movie(movie.detach().to(dev), gain, bool(mean_zero), hot_pixel_threshold,
-                                 bool(return_hot_counts))
-    if return_hot_counts:
-        return res[0].to(out_dev), res[1].to(out_dev)
-    return res.to(out_dev)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        res = engine.condition_movie(movie.detach().to(dev), gain, bool(mean_zero), hot_pixel_threshold,
+                                     bool(return_hot_counts))
+        if return_hot_counts:
+            return res[0].to(out_dev), res[1].to(out_dev)
+        return res.to(out_dev)
 
 
 def _check_dose(dose_per_frame):
@@ -649,36 +591,31 @@ def motion_correct_raw(movie, gain, pixel_spacing, reference_frame=None, b_facto
     return_plain_sum=True)``."""
     thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # ValueError before any device is touched
     dose = _check_dose(dose_per_frame)
-    return _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, grid_type,
-                               mean_zero, return_frames, device, thr, return_hot_counts, dose, pre_exposure, voltage)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        t = raw.shape[0]
+        ref = t // 2 if reference_frame is None else int(reference_frame)
+        ps = float(pixel_spacing)
 
+        def route(estimate):  # the same steps on a RawMovie and on the conditioned movie
+            def run(src):
+                shifts = estimate(src, ref, ps, float(b_factor), tuple(frequency_range))
+                field = image_shifts_to_deformation_field(shifts, ps)
+                lat = engine.frame_lattices(field.contiguous(), t, grid_type)
+                total, _, frames = engine.corrected_sums(src, lat, ps, True, dose, pre_exposure, voltage, False,
+                                                         bool(return_frames))
+                return field, total, frames
+            return run
 
-@_on_gpu
-def _motion_correct_raw(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, grid_type, mean_zero,
-                        return_frames, device, thr, return_hot_counts, dose, pre_exposure, voltage):
-    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
-    t = raw.shape[0]
-    ref = t // 2 if reference_frame is None else int(reference_frame)
-    ps = float(pixel_spacing)
-
-    def route(estimate):  # the same steps on a RawMovie and on the conditioned movie
-        def run(src):
-            shifts = estimate(src, ref, ps, float(b_factor), tuple(frequency_range))
-            field = image_shifts_to_deformation_field(shifts, ps)
-            lat = engine.frame_lattices(field.contiguous(), t, grid_type)
-            total, _, frames = engine.corrected_sums(src, lat, ps, True, dose, pre_exposure, voltage, False,
-                                                     bool(return_frames))
-            return field, total, frames
-        return run
-
-    (field, total, frames), counts = _raw_or_conditioned(raw, gd, mean_zero, thr, route(engine.global_shifts_raw),
-                                                         route(engine.global_shifts))
-    out = [field.to(out_dev), total.to(out_dev)]
-    if return_frames:
-        out.append(frames.to(out_dev))
-    if return_hot_counts:
-        out.append(_hot_counts_out(counts, t, out_dev))
-    return tuple(out)
+        (field, total, frames), counts = _raw_or_conditioned(raw, gd, mean_zero, thr=thr,
+                                                             fused=route(engine.global_shifts_raw),
+                                                             conditioned=route(engine.global_shifts))
+        out = [field.to(out_dev), total.to(out_dev)]
+        if return_frames:
+            out.append(frames.to(out_dev))
+        if return_hot_counts:
+            out.append(_hot_counts_out(counts, t, out_dev))
+        return tuple(out)
 
 
 def motion_correct_raw_patches(movie, gain, pixel_spacing, patch_sidelength=1024, reference_frame=None,
@@ -703,56 +640,46 @@ def motion_correct_raw_patches(movie, gain, pixel_spacing, patch_sidelength=1024
         raise ValueError(f"Unknown reference_strategy: {reference_strategy}")
     thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # ValueError before any device is touched
     p = _check_patch_sidelength(patch_sidelength)
-    return _motion_correct_raw_patches(movie, gain, pixel_spacing, p, reference_frame,
-                                       reference_strategy, b_factor, frequency_range, sub_pixel_refinement,
-                                       temporal_smoothing, smoothing_window_size, deformation_field, outlier_rejection,
-                                       outlier_threshold, grid_type, mean_zero, return_frames, device, thr,
-                                       return_hot_counts)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        t = raw.shape[0]
+        ps = float(pixel_spacing)
+        allow_fused = deformation_field is None and thr is None
+        ref = None
+        if allow_fused and raw.dtype in RAW_DTYPES:  # the estimator's own argument rules, before any launch
+            ref = _check_patch_estimate_args(t, reference_frame, reference_strategy,
+                                             sub_pixel_refinement=sub_pixel_refinement,
+                                             outlier_rejection=outlier_rejection)
 
+        def fused(rm):
+            field, centers = engine.patch_field_raw(
+                rm, ps, ref, reference_strategy, float(b_factor), frequency_range, p,
+                bool(sub_pixel_refinement), bool(temporal_smoothing), int(smoothing_window_size),
+                bool(outlier_rejection), float(outlier_threshold))
+            lat = engine.frame_lattices(field, t, grid_type)
+            # (a single patch: motion_correct_sum's rigid warp)
+            total, _, frames = engine.corrected_sums(rm, lat, ps, RIGID_FAST_PATH and _is_rigid(field),
+                                                     want_frames=bool(return_frames))
+            return field, centers, total, frames
 
-@_on_gpu
-def _motion_correct_raw_patches(movie, gain, pixel_spacing, patch_sidelength, reference_frame, reference_strategy,
-                                b_factor, frequency_range, sub_pixel_refinement, temporal_smoothing,
-                                smoothing_window_size, deformation_field, outlier_rejection, outlier_threshold,
-                                grid_type, mean_zero, return_frames, device, thr, return_hot_counts):
-    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
-    t = raw.shape[0]
-    ps = float(pixel_spacing)
-    allow_fused = deformation_field is None and thr is None
-    ref = None
-    if allow_fused and raw.dtype in RAW_DTYPES:  # the estimator's own argument rules, before any launch
-        ref = _check_patch_estimate_args(t, reference_frame, reference_strategy, sub_pixel_refinement,
-                                         outlier_rejection)
+        def conditioned(img):
+            field, centers = estimate_motion_cross_correlation_patches(
+                img, ps, reference_frame=reference_frame, reference_strategy=reference_strategy, b_factor=b_factor,
+                frequency_range=frequency_range, patch_sidelength=p,
+                sub_pixel_refinement=sub_pixel_refinement, temporal_smoothing=temporal_smoothing,
+                smoothing_window_size=smoothing_window_size, deformation_field=deformation_field,
+                outlier_rejection=outlier_rejection, outlier_threshold=outlier_threshold)
+            res = motion_correct_sum(img, field, ps, grid_type=grid_type, return_frames=bool(return_frames))
+            return (field, centers, *(res if return_frames else (res, None)))
 
-    def fused(rm):
-        field, centers = engine.patch_field_raw(
-            rm, ps, ref, reference_strategy, float(b_factor), frequency_range, patch_sidelength,
-            bool(sub_pixel_refinement), bool(temporal_smoothing), int(smoothing_window_size),
-            bool(outlier_rejection), float(outlier_threshold))
-        lat = engine.frame_lattices(field, t, grid_type)
-        # (a single patch: motion_correct_sum's rigid warp)
-        total, _, frames = engine.corrected_sums(rm, lat, ps, RIGID_FAST_PATH and _is_rigid(field),
-                                                 want_frames=bool(return_frames))
-        return field, centers, total, frames
-
-    def conditioned(img):
-        field, centers = estimate_motion_cross_correlation_patches(
-            img, ps, reference_frame=reference_frame, reference_strategy=reference_strategy, b_factor=b_factor,
-            frequency_range=frequency_range, patch_sidelength=patch_sidelength,
-            sub_pixel_refinement=sub_pixel_refinement, temporal_smoothing=temporal_smoothing,
-            smoothing_window_size=smoothing_window_size, deformation_field=deformation_field,
-            outlier_rejection=outlier_rejection, outlier_threshold=outlier_threshold)
-        res = motion_correct_sum(img, field, ps, grid_type=grid_type, return_frames=bool(return_frames))
-        return (field, centers, *(res if return_frames else (res, None)))
-
-    (field, centers, total, frames), counts = _raw_or_conditioned(raw, gd, mean_zero, thr, fused, conditioned,
-                                                                  allow_fused)
-    out = [field.to(out_dev), centers.to(out_dev), total.to(out_dev)]
-    if return_frames:
-        out.append(frames.to(out_dev))
-    if return_hot_counts:
-        out.append(_hot_counts_out(counts, t, out_dev))
-    return tuple(out)
+        (field, centers, total, frames), counts = _raw_or_conditioned(
+            raw, gd, mean_zero, thr=thr, fused=fused, conditioned=conditioned, allow_fused=allow_fused)
+        out = [field.to(out_dev), centers.to(out_dev), total.to(out_dev)]
+        if return_frames:
+            out.append(frames.to(out_dev))
+        if return_hot_counts:
+            out.append(_hot_counts_out(counts, t, out_dev))
+        return tuple(out)
 
 
 def motion_correct_sum_raw(movie, gain, deformation_grid, pixel_spacing, grid_type="catmull_rom", mean_zero=True,
@@ -776,52 +703,45 @@ def motion_correct_sum_raw(movie, gain, deformation_grid, pixel_spacing, grid_ty
     thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)
     _check_field_4d(deformation_grid, "deformation_grid must be a (2, nt, gh, gw) tensor")
     _check_raw_args(movie, gain)
-    return _motion_correct_sum_raw(movie, gain, deformation_grid, pixel_spacing, grid_type, mean_zero, thr, dose,
-                                   pre_exposure, voltage, bool(return_plain_sum), bool(return_frames), device)
+    want_plain, want_frames = bool(return_plain_sum), bool(return_frames)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        t = raw.shape[0]
+        ps = float(pixel_spacing)
+        field = _stage(deformation_grid, dev)
+        rigid = RIGID_FAST_PATH and _is_rigid(field)
+
+        def fused(rm):
+            lat = engine.frame_lattices(field, t, grid_type)
+            return engine.corrected_sums(rm, lat, ps, rigid, dose, pre_exposure, voltage, want_plain, want_frames)
+
+        def conditioned(img):  # motion_correct_sum, once more without the dose for the plain sum
+            res = motion_correct_sum(img, field, ps, grid_type=grid_type, return_frames=want_frames,
+                                     dose_per_frame=dose, pre_exposure=pre_exposure, voltage=voltage)
+            total, frames = res if want_frames else (res, None)
+            return total, (motion_correct_sum(img, field, ps, grid_type=grid_type) if want_plain else None), frames
+
+        (total, plain, frames), _ = _raw_or_conditioned(raw, gd, mean_zero, thr=thr, fused=fused,
+                                                        conditioned=conditioned)
+        out = [total.to(out_dev)]
+        if want_plain:
+            out.append(plain.to(out_dev))
+        if want_frames:
+            out.append(frames.to(out_dev))
+        return out[0] if len(out) == 1 else tuple(out)
 
 
-@_on_gpu
-def _motion_correct_sum_raw(movie, gain, field, pixel_spacing, grid_type, mean_zero, thr, dose, pre_exposure, voltage,
-                            want_plain, want_frames, device):
-    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
-    t = raw.shape[0]
-    ps = float(pixel_spacing)
-    field = _stage(field, dev)
-    rigid = RIGID_FAST_PATH and _is_rigid(field)
-
-    def fused(rm):
-        lat = engine.frame_lattices(field, t, grid_type)
-        return engine.corrected_sums(rm, lat, ps, rigid, dose, pre_exposure, voltage, want_plain, want_frames)
-
-    def conditioned(img):  # motion_correct_sum, once more without the dose for the plain sum
-        res = motion_correct_sum(img, field, ps, grid_type=grid_type, return_frames=want_frames, dose_per_frame=dose,
-                                 pre_exposure=pre_exposure, voltage=voltage)
-        total, frames = res if want_frames else (res, None)
-        return total, (motion_correct_sum(img, field, ps, grid_type=grid_type) if want_plain else None), frames
-
-    (total, plain, frames), _ = _raw_or_conditioned(raw, gd, mean_zero, thr, fused, conditioned)
-    out = [total.to(out_dev)]
-    if want_plain:
-        out.append(plain.to(out_dev))
-    if want_frames:
-        out.append(frames.to(out_dev))
-    return out[0] if len(out) == 1 else tuple(out)
-
-
-@_on_gpu
 def dose_weighted_sum(movie, pixel_spacing, dose_per_frame, pre_exposure=0.0, voltage=300.0, device=None):
     """``sum_f irfft2(q_f * rfft2(frame_f))`` with the Grant & Grigorieff exposure filter
     ``q_f = exp(-0.5 N_f / N_c(|k|))`` normalised by ``sqrt(sum_f q_f^2)``: the reference
     pipeline's ``dose_weight(movie)`` (examples/ttMotion.py:331-351: rfft2(norm='ortho') ->
     torch_fourier_filter dose_weight_movie(crit_exposure_bfactor=-1) -> irfft2 -> sum).  The
     third-party filter is not part of the reference tree and untested there: parity unpinned."""
-    out_dev = _out_device(movie, device)
-    dev = require_gpu(out_dev)
-    return engine.dose_weighted_sum(_stage(movie, dev), float(pixel_spacing), float(dose_per_frame),
-                                    float(pre_exposure), float(voltage)).to(out_dev)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        return engine.dose_weighted_sum(_stage(movie, dev), float(pixel_spacing), float(dose_per_frame),
+                                        float(pre_exposure), float(voltage)).to(out_dev)
 
 
-@_on_gpu
 def estimate_local_motion(image, pixel_spacing, patch_shape, deformation_field_resolution,
                           initial_deformation_field=None, device=None, n_iterations=100, b_factor=500,
                           frequency_range=(300, 10), optimizer_type="adam", grid_type="catmull_rom",
@@ -831,31 +751,31 @@ def estimate_local_motion(image, pixel_spacing, patch_shape, deformation_field_r
     Fourier-shifted patches with the mean of the other frames (estimate_motion_optimizer.py:28-439;
     same arguments, defaults, return values and error messages).  The loss and its analytic
     gradient are HIP kernels over patch spectra that are transformed once (local_motion.py)."""
-    from . import local_motion
-    from .optimization_state import OptimizationTracker
+    # CPU tensors are staged to the GPU and the field comes back on `out_dev`
+    with gpu_entry(image, device) as (out_dev, dev):
+        from . import local_motion
+        from .optimization_state import OptimizationTracker
 
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)  # CPU tensors are staged to the GPU and the field comes back on `out_dev`
-    img = _stage(image, dev)
-    if grid_type not in ("catmull_rom", "bspline"):
-        raise ValueError(f"Invalid grid type: {grid_type}. Must be 'catmull_rom' or 'bspline'.")
-    res = tuple(int(r) for r in deformation_field_resolution)
-    trajectory = None
-    if return_trajectory:
-        tk = trajectory_kwargs if trajectory_kwargs is not None else {}
-        tk.setdefault("sample_every_n_steps", 1)
-        tk.setdefault("total_steps", n_iterations)
-        trajectory = OptimizationTracker(**tk)
-    if initial_deformation_field is None:
-        init = torch.zeros((2, *res), dtype=torch.float32, device=dev)
-    else:
-        init = resample_deformation_field(_stage(initial_deformation_field.detach(), dev), res).contiguous()
-        init = init - torch.mean(init)
-    final = local_motion.estimate_local_motion(img, float(pixel_spacing), patch_shape, res, init, n_iterations,
-                                               b_factor, frequency_range, optimizer_type, grid_type, loss_type,
-                                               optimizer_kwargs, trajectory)
-    final = final.to(out_dev)
-    return (final, trajectory) if return_trajectory else final
+        img = _stage(image, dev)
+        if grid_type not in ("catmull_rom", "bspline"):
+            raise ValueError(f"Invalid grid type: {grid_type}. Must be 'catmull_rom' or 'bspline'.")
+        res = tuple(int(r) for r in deformation_field_resolution)
+        trajectory = None
+        if return_trajectory:
+            tk = trajectory_kwargs if trajectory_kwargs is not None else {}
+            tk.setdefault("sample_every_n_steps", 1)
+            tk.setdefault("total_steps", n_iterations)
+            trajectory = OptimizationTracker(**tk)
+        if initial_deformation_field is None:
+            init = torch.zeros((2, *res), dtype=torch.float32, device=dev)
+        else:
+            init = resample_deformation_field(_stage(initial_deformation_field.detach(), dev), res).contiguous()
+            init = init - torch.mean(init)
+        final = local_motion.estimate_local_motion(img, float(pixel_spacing), patch_shape, res, init, n_iterations,
+                                                   b_factor, frequency_range, optimizer_type, grid_type, loss_type,
+                                                   optimizer_kwargs, trajectory)
+        final = final.to(out_dev)
+        return (final, trajectory) if return_trajectory else final
 
 
 def _correct_motion_fast_impl(img_dev, deformation_grid, dev, mutate):
@@ -871,17 +791,15 @@ def _correct_motion_fast_impl(img_dev, deformation_grid, dev, mutate):
     return engine.fourier_shift(img_dev, shifts.to(dev))
 
 
-@_on_gpu
 def correct_motion_fast(image, deformation_grid, device=None):
     """Rigid correction by a Fourier phase ramp (correct_motion.py:430-498); field
     values are used as pixels.  With BUG_COMPATIBLE the caller's `deformation_grid` is
     negated in place exactly when the reference would do so (grid already on the
     target device)."""
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    mutate = BUG_COMPATIBLE and (device is None or deformation_grid.device == torch.device(device))
-    out = _correct_motion_fast_impl(_stage(image, dev), deformation_grid, dev, mutate)
-    return out.to(out_dev)
+    with gpu_entry(image, device) as (out_dev, dev):
+        mutate = BUG_COMPATIBLE and (device is None or deformation_grid.device == torch.device(device))
+        out = _correct_motion_fast_impl(_stage(image, dev), deformation_grid, dev, mutate=mutate)
+        return out.to(out_dev)
 
 
 def _check_fast_field(deformation_grid, t):
@@ -906,10 +824,12 @@ def _check_fast_sum_args(dose_per_frame, return_plain_sum):
     return dose
 
 
-def _fast_sums(img, field, ps, dose, pre_exposure, voltage, want_plain):
+def _fast_sums(img, field, sums):
     """(dose-weighted sum or None, plain sum or None) of the fp32 stack `img` (on the device) shifted by the
     Angstrom `field` (on the device): the fused sums, or -- where they raise McorrUnsupported -- exactly
-    correct_motion_fast(img, field / ps) followed by .sum(0) and dose_weighted_sum."""
+    correct_motion_fast(img, field / ps) followed by .sum(0) and dose_weighted_sum.  `sums`: engine.fast_shift_sums'
+    trailing arguments (ps, dose, pre_exposure, voltage, want_plain)."""
+    ps, dose, pre_exposure, voltage, want_plain = sums
     g = field / ps
     shifts = engine.fast_shifts(g)
     try:
@@ -921,7 +841,8 @@ def _fast_sums(img, field, ps, dose, pre_exposure, voltage, want_plain):
         return dw, plain
 
 
-def _fast_result(dw, plain, want_plain, out_dev):
+def _fast_result(sums, want_plain, out_dev):
+    dw, plain = sums
     if dw is None:
         return plain.to(out_dev)
     return (dw.to(out_dev), plain.to(out_dev)) if want_plain else dw.to(out_dev)
@@ -949,17 +870,11 @@ def motion_correct_sum_fast(image, deformation_grid, pixel_spacing, dose_per_fra
     if image.dim() != 3:
         raise ValueError(f"image must be (t, h, w), got {tuple(image.shape)}")
     _check_fast_field(deformation_grid, image.shape[0])
-    return _motion_correct_sum_fast(image, deformation_grid, pixel_spacing, dose, pre_exposure, voltage,
-                                    bool(return_plain_sum), device)
-
-
-@_on_gpu
-def _motion_correct_sum_fast(image, deformation_grid, pixel_spacing, dose, pre_exposure, voltage, want_plain, device):
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    dw, plain = _fast_sums(_stage(image, dev), deformation_grid.detach().to(dev), float(pixel_spacing), dose,
-                           pre_exposure, voltage, want_plain)
-    return _fast_result(dw, plain, want_plain, out_dev)
+    want_plain = bool(return_plain_sum)
+    with gpu_entry(image, device) as (out_dev, dev):
+        sums = _fast_sums(_stage(image, dev), deformation_grid.detach().to(dev),
+                          (float(pixel_spacing), dose, pre_exposure, voltage, want_plain))
+        return _fast_result(sums, want_plain, out_dev)
 
 
 def _check_raw_args(movie, gain):
@@ -983,21 +898,17 @@ def motion_correct_sum_fast_raw(movie, gain, deformation_grid, pixel_spacing, me
     thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)
     _check_raw_args(movie, gain)
     _check_fast_field(deformation_grid, movie.shape[0])
-    return _motion_correct_sum_fast_raw(movie, gain, deformation_grid, pixel_spacing, mean_zero, thr, dose,
-                                        pre_exposure, voltage, bool(return_plain_sum), device)
-
-
-@_on_gpu
-def _motion_correct_sum_fast_raw(movie, gain, deformation_grid, pixel_spacing, mean_zero, thr, dose, pre_exposure,
-                                 voltage, want_plain, device):
-    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
-    ps = float(pixel_spacing)
-    field = deformation_grid.detach().to(dev)
-    sums = (ps, dose, pre_exposure, voltage, want_plain)
-    res, _ = _raw_or_conditioned(raw, gd, mean_zero, thr,
-                                 lambda rm: engine.fast_shift_sums(rm, engine.fast_shifts(field / ps), *sums),
-                                 lambda img: _fast_sums(img, field, *sums))
-    return _fast_result(*res, want_plain, out_dev)
+    want_plain = bool(return_plain_sum)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        ps = float(pixel_spacing)
+        field = deformation_grid.detach().to(dev)
+        sums = (ps, dose, pre_exposure, voltage, want_plain)
+        res, _ = _raw_or_conditioned(
+            raw, gd, mean_zero, thr=thr,
+            fused=lambda rm: engine.fast_shift_sums(rm, engine.fast_shifts(field / ps), *sums),
+            conditioned=lambda img: _fast_sums(img, field, sums))
+        return _fast_result(res, want_plain, out_dev)
 
 
 def motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame=None, b_factor=500, frequency_range=(300, 10),
@@ -1014,37 +925,32 @@ def motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame=None, b_
     dose = _check_fast_sum_args(dose_per_frame, return_plain_sum)  # every argument rule before any device
     thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)
     _check_raw_args(movie, gain)
-    return _motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, mean_zero,
-                                    thr, dose, pre_exposure, voltage, bool(return_plain_sum), bool(return_hot_counts),
-                                    device)
+    want_plain, want_counts = bool(return_plain_sum), bool(return_hot_counts)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        t = raw.shape[0]
+        ref = t // 2 if reference_frame is None else int(reference_frame)
+        ps = float(pixel_spacing)
+        sums = (ps, dose, pre_exposure, voltage, want_plain)
 
+        def route(estimate, fast_sums):  # the same steps on a RawMovie and on the conditioned movie
+            def run(src):
+                shifts = estimate(src, ref, ps, float(b_factor), tuple(frequency_range))
+                field = image_shifts_to_deformation_field(shifts, ps)  # as motion_correct_raw
+                return field, fast_sums(src, field)
+            return run
 
-@_on_gpu
-def _motion_correct_raw_fast(movie, gain, pixel_spacing, reference_frame, b_factor, frequency_range, mean_zero, thr,
-                             dose, pre_exposure, voltage, want_plain, want_counts, device):
-    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
-    t = raw.shape[0]
-    ref = t // 2 if reference_frame is None else int(reference_frame)
-    ps = float(pixel_spacing)
-    sums = (ps, dose, pre_exposure, voltage, want_plain)
-
-    def route(estimate, fast_sums):  # the same steps on a RawMovie and on the conditioned movie
-        def run(src):
-            shifts = estimate(src, ref, ps, float(b_factor), tuple(frequency_range))
-            field = image_shifts_to_deformation_field(shifts, ps)  # as motion_correct_raw
-            return field, fast_sums(src, field)
-        return run
-
-    (field, (dw, plain)), counts = _raw_or_conditioned(
-        raw, gd, mean_zero, thr,
-        route(engine.global_shifts_raw, lambda rm, f: engine.fast_shift_sums(rm, engine.fast_shifts(f / ps), *sums)),
-        route(engine.global_shifts, lambda img, f: _fast_sums(img, f, *sums)))
-    out = [field.to(out_dev), (plain if dw is None else dw).to(out_dev)]
-    if want_plain:
-        out.append(plain.to(out_dev))
-    if want_counts:
-        out.append(_hot_counts_out(counts, t, out_dev))
-    return tuple(out)
+        (field, (dw, plain)), counts = _raw_or_conditioned(
+            raw, gd, mean_zero, thr=thr,
+            fused=route(engine.global_shifts_raw,
+                        lambda rm, f: engine.fast_shift_sums(rm, engine.fast_shifts(f / ps), *sums)),
+            conditioned=route(engine.global_shifts, lambda img, f: _fast_sums(img, f, sums)))
+        out = [field.to(out_dev), (plain if dw is None else dw).to(out_dev)]
+        if want_plain:
+            out.append(plain.to(out_dev))
+        if want_counts:
+            out.append(_hot_counts_out(counts, t, out_dev))
+        return tuple(out)
 
 
 # ------------------------------------------------------------------ Fourier cropping (2x binning)
@@ -1074,22 +980,16 @@ def fourier_crop(image, binning=2, device=None):
     if not isinstance(image, torch.Tensor) or image.dim() not in (2, 3):
         raise ValueError(f"image must be (h, w) or (t, h, w), got {tuple(getattr(image, 'shape', ()))}")
     _check_crop_args(image.shape, binning)
-    return _fourier_crop(image, device)
-
-
-@_on_gpu
-def _fourier_crop(image, device):
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    img = _stage(image, dev)
-    out = engine.fourier_crop(img if img.dim() == 3 else img[None])
-    return (out if img.dim() == 3 else out[0]).to(out_dev)
+    with gpu_entry(image, device) as (out_dev, dev):
+        img = _stage(image, dev)
+        out = engine.fourier_crop(img if img.dim() == 3 else img[None])
+        return (out if img.dim() == 3 else out[0]).to(out_dev)
 
 
 def _crop_raw(raw, gd, mean_zero, thr):
     """(binned fp32 movie, hot counts or None) of a movie on the device: engine.fourier_crop of the RawMovie, or of
     the conditioned movie."""
-    return _raw_or_conditioned(raw, gd, mean_zero, thr, engine.fourier_crop, engine.fourier_crop)
+    return _raw_or_conditioned(raw, gd, mean_zero, thr=thr, fused=engine.fourier_crop, conditioned=engine.fourier_crop)
 
 
 def fourier_crop_raw(movie, gain, binning=2, mean_zero=True, hot_pixel_threshold=None, return_hot_counts=False,
@@ -1104,16 +1004,13 @@ def fourier_crop_raw(movie, gain, binning=2, mean_zero=True, hot_pixel_threshold
     thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # every argument rule before any device
     _check_raw_args(movie, gain)
     _check_crop_args(movie.shape, binning)
-    return _fourier_crop_raw(movie, gain, mean_zero, thr, bool(return_hot_counts), device)
-
-
-@_on_gpu
-def _fourier_crop_raw(movie, gain, mean_zero, thr, want_counts, device):
-    out_dev, _, raw, gd = _stage_raw(movie, gain, device)
-    binned, counts = _crop_raw(raw, gd, mean_zero, thr)
-    if not want_counts:
-        return binned.to(out_dev)
-    return binned.to(out_dev), _hot_counts_out(counts, movie.shape[0], out_dev)
+    want_counts = bool(return_hot_counts)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        binned, counts = _crop_raw(raw, gd, mean_zero, thr=thr)
+        if not want_counts:
+            return binned.to(out_dev)
+        return binned.to(out_dev), _hot_counts_out(counts, movie.shape[0], out_dev)
 
 
 def motion_correct_raw_binned(movie, gain, pixel_spacing, binning=2, patch_sidelength=None, reference_frame=None,
@@ -1144,34 +1041,27 @@ def motion_correct_raw_binned(movie, gain, pixel_spacing, binning=2, patch_sidel
         _check_patch_sidelength(patch_sidelength)
         if return_plain_sum:
             raise ValueError("return_plain_sum belongs to the whole-image route (patch_sidelength=None)")
-    return _motion_correct_raw_binned(movie, gain, pixel_spacing, binning, patch_sidelength, reference_frame, b_factor,
-                                      frequency_range, grid_type, mean_zero, thr, dose, pre_exposure, voltage,
-                                      bool(return_plain_sum), bool(return_hot_counts), device)
-
-
-@_on_gpu
-def _motion_correct_raw_binned(movie, gain, pixel_spacing, binning, patch_sidelength, reference_frame, b_factor,
-                               frequency_range, grid_type, mean_zero, thr, dose, pre_exposure, voltage, want_plain,
-                               want_counts, device):
-    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
-    binned, counts = _crop_raw(raw, gd, mean_zero, thr)
-    ps = binning * float(pixel_spacing)
-    # the public functions themselves on the device-resident binned movie: the composition by construction
-    if patch_sidelength is None:
-        field = estimate_global_motion(binned, ps, reference_frame=reference_frame, b_factor=b_factor,
-                                       frequency_range=frequency_range)
-        sums = motion_correct_sum_fast(binned, field, ps, dose_per_frame=dose, pre_exposure=pre_exposure,
-                                       voltage=voltage, return_plain_sum=want_plain)
-        out = [field, *(sums if want_plain else (sums,))]
-    else:
-        field, centers = estimate_motion_cross_correlation_patches(
-            binned, ps, reference_frame=reference_frame, b_factor=b_factor, frequency_range=frequency_range,
-            patch_sidelength=int(patch_sidelength))
-        out = [field, centers, motion_correct_sum(binned, field, ps, grid_type=grid_type, dose_per_frame=dose,
-                                                  pre_exposure=pre_exposure, voltage=voltage)]
-    if want_counts:
-        out.append(_hot_counts_out(counts, movie.shape[0], dev))  # (moved to out_dev with the rest)
-    return tuple(x.to(out_dev) for x in out)
+    want_plain, want_counts = bool(return_plain_sum), bool(return_hot_counts)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        binned, counts = _crop_raw(raw, gd, mean_zero, thr=thr)
+        ps = binning * float(pixel_spacing)
+        # the public functions themselves on the device-resident binned movie: the composition by construction
+        if patch_sidelength is None:
+            field = estimate_global_motion(binned, ps, reference_frame=reference_frame, b_factor=b_factor,
+                                           frequency_range=frequency_range)
+            sums = motion_correct_sum_fast(binned, field, ps, dose_per_frame=dose, pre_exposure=pre_exposure,
+                                           voltage=voltage, return_plain_sum=want_plain)
+            out = [field, *(sums if want_plain else (sums,))]
+        else:
+            field, centers = estimate_motion_cross_correlation_patches(
+                binned, ps, reference_frame=reference_frame, b_factor=b_factor, frequency_range=frequency_range,
+                patch_sidelength=int(patch_sidelength))
+            out = [field, centers, motion_correct_sum(binned, field, ps, grid_type=grid_type, dose_per_frame=dose,
+                                                      pre_exposure=pre_exposure, voltage=voltage)]
+        if want_counts:
+            out.append(_hot_counts_out(counts, movie.shape[0], dev))  # (moved to out_dev with the rest)
+        return tuple(x.to(out_dev) for x in out)
 
 
 # ------------------------------------------------------------------ frame groups (low-dose movies)
@@ -1201,13 +1091,9 @@ def group_frames_raw(movie, group, device=None):
     device is touched.  An int16 window sum outside [-32768, 32767] raises ValueError naming ``group`` (a device
     flag, the one device-to-host read)."""
     group = _check_group_args(movie, group)
-    return _group_frames_raw(movie, group, device)
-
-
-@_on_gpu
-def _group_frames_raw(movie, group, device):
-    out_dev, dev, raw, _ = _stage_raw(movie, None, device)
-    return engine.group_frames_raw(raw, group).to(out_dev)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, _ = _stage_raw(movie, None, dev)
+        return engine.group_frames_raw(raw, group).to(out_dev)
 
 
 def motion_correct_raw_grouped(movie, gain, pixel_spacing, group, patch_sidelength=None, reference_frame=None,
@@ -1241,66 +1127,63 @@ def motion_correct_raw_grouped(movie, gain, pixel_spacing, group, patch_sideleng
         if return_plain_sum:
             raise ValueError("return_plain_sum belongs to the whole-image route (patch_sidelength=None)")
     _check_fast_sum_args(dose, return_plain_sum)
-    return _motion_correct_raw_grouped(movie, gain, pixel_spacing, group, p, reference_frame, b_factor,
-                                       frequency_range, grid_type, mean_zero, dose, pre_exposure, voltage,
-                                       bool(return_plain_sum), device)
+    want_plain = bool(return_plain_sum)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        t, h, w = raw.shape
+        ps = float(pixel_spacing)
+        grouped = engine.group_frames_raw(raw, group)
+        # the sums: the public functions themselves on the device-resident movie (their argument rules pass by
+        # construction, their results stay on `dev`)
+        if p is None:
+            ref = t // 2 if reference_frame is None else int(reference_frame)
+            fused_sums = not engine.POLYPHASE_FOURIER_SHIFT and engine._full_row_major_ok(h, w)
+
+            def estimate(shifts_of, fused):  # motion_correct_raw_fast's routes, without the sums of the grouped movie
+                def run(src):
+                    field = image_shifts_to_deformation_field(
+                        shifts_of(src, ref, ps, float(b_factor), tuple(frequency_range)), ps)
+                    if fused and not fused_sums:  # its fused sums refuse the shape: estimate on the conditioned movie
+                        raise McorrUnsupported(f"no fused Fourier-shift sums for frames of {h} x {w}")
+                    return field
+                return run
+
+            field, _ = _raw_or_conditioned(grouped, gd, mean_zero, thr=None,
+                                           fused=estimate(engine.global_shifts_raw, True),
+                                           conditioned=estimate(engine.global_shifts, False))
+            sums = motion_correct_sum_fast_raw(raw, gd, field, pixel_spacing=ps, mean_zero=mean_zero,
+                                               dose_per_frame=dose, pre_exposure=pre_exposure, voltage=voltage,
+                                               return_plain_sum=want_plain)
+            out = [field, *(sums if want_plain else (sums,))]
+        else:
+            # the public route itself on the device-resident grouped movie (its aligned sum of the groups is dropped):
+            # which shapes take its fused kernels is decided there
+            field, centers, _ = motion_correct_raw_patches(
+                grouped, gd, ps, patch_sidelength=p, reference_frame=reference_frame, b_factor=b_factor,
+                frequency_range=frequency_range, grid_type=grid_type, mean_zero=mean_zero)
+            out = [field, centers, motion_correct_sum_raw(raw, gd, field, pixel_spacing=ps, grid_type=grid_type,
+                                                          mean_zero=mean_zero, dose_per_frame=dose,
+                                                          pre_exposure=pre_exposure, voltage=voltage)]
+        return tuple(x.to(out_dev) for x in out)
 
 
-@_on_gpu
-def _motion_correct_raw_grouped(movie, gain, pixel_spacing, group, patch_sidelength, reference_frame, b_factor,
-                                frequency_range, grid_type, mean_zero, dose, pre_exposure, voltage, want_plain, device):
-    out_dev, dev, raw, gd = _stage_raw(movie, gain, device)
-    t, h, w = raw.shape
-    ps = float(pixel_spacing)
-    grouped = engine.group_frames_raw(raw, group)
-    if patch_sidelength is None:
-        ref = t // 2 if reference_frame is None else int(reference_frame)
-        fused_sums = not engine.POLYPHASE_FOURIER_SHIFT and engine._full_row_major_ok(h, w)
-
-        def estimate(shifts_of, fused):  # motion_correct_raw_fast's routes, without the sums of the grouped movie
-            def run(src):
-                field = image_shifts_to_deformation_field(
-                    shifts_of(src, ref, ps, float(b_factor), tuple(frequency_range)), ps)
-                if fused and not fused_sums:  # where its fused sums refuse the shape it estimates on the conditioned movie
-                    raise McorrUnsupported(f"no fused Fourier-shift sums for frames of {h} x {w}")
-                return field
-            return run
-
-        field, _ = _raw_or_conditioned(grouped, gd, mean_zero, None, estimate(engine.global_shifts_raw, True),
-                                       estimate(engine.global_shifts, False))
-        sums = _motion_correct_sum_fast_raw(raw, gd, field, ps, mean_zero, None, dose, pre_exposure, voltage,
-                                            want_plain, None)
-        out = [field, *(sums if want_plain else (sums,))]
-    else:
-        # the public route itself on the device-resident grouped movie (its aligned sum of the groups is dropped):
-        # which shapes take its fused kernels is decided there
-        field, centers, _ = motion_correct_raw_patches(grouped, gd, ps, patch_sidelength, reference_frame,
-                                                       b_factor=b_factor, frequency_range=frequency_range,
-                                                       grid_type=grid_type, mean_zero=mean_zero)
-        out = [field, centers, _motion_correct_sum_raw(raw, gd, field, ps, grid_type, mean_zero, None, dose,
-                                                       pre_exposure, voltage, False, False, None)]
-    return tuple(x.to(out_dev) for x in out)
-
-
-@_on_gpu
 def get_pixel_shifts(frame, pixel_spacing, frame_deformation_grid, pixel_grid=None):
     """(h,w,2) per-pixel shifts in px from a (2,G_h,G_w) Angstrom lattice
     (correct_motion.py:132-185).  `pixel_grid` (..., 2) holds the (y, x) pixel coordinates to
     evaluate at (correct_motion.py:167-168); the reference always passes the identity grid
     coordinate_grid((h,w)), which -- like None -- takes the tabulated kernel; any other grid is
     evaluated point by point (mc_pixel_shifts_at), result shape = pixel_grid's."""
-    out_dev = frame.device
-    dev = require_gpu(out_dev)
-    h, w = frame.shape[-2:]
-    lat = _stage(frame_deformation_grid, dev)
-    if pixel_grid is not None:
-        if pixel_grid.shape[-1] != 2:
-            raise ValueError(f"pixel_grid must have shape (..., 2), got {tuple(pixel_grid.shape)}")
-        grid = _stage(pixel_grid, dev)
-        identity = tuple(grid.shape) == (h, w, 2) and bool(
-            (grid[..., 0] == torch.arange(h, device=dev, dtype=torch.float32)[:, None]).all()
-            and (grid[..., 1] == torch.arange(w, device=dev, dtype=torch.float32)[None, :]).all())
-        if not identity:
-            return engine.pixel_shifts_at(lat, h, w, float(pixel_spacing), grid).to(out_dev)
-    out = engine.pixel_shifts(lat, h, w, float(pixel_spacing))
-    return out.to(out_dev)
+    with gpu_entry(frame) as (out_dev, dev):
+        h, w = frame.shape[-2:]
+        lat = _stage(frame_deformation_grid, dev)
+        if pixel_grid is not None:
+            if pixel_grid.shape[-1] != 2:
+                raise ValueError(f"pixel_grid must have shape (..., 2), got {tuple(pixel_grid.shape)}")
+            grid = _stage(pixel_grid, dev)
+            identity = tuple(grid.shape) == (h, w, 2) and bool(
+                (grid[..., 0] == torch.arange(h, device=dev, dtype=torch.float32)[:, None]).all()
+                and (grid[..., 1] == torch.arange(w, device=dev, dtype=torch.float32)[None, :]).all())
+            if not identity:
+                return engine.pixel_shifts_at(lat, h, w, float(pixel_spacing), grid).to(out_dev)
+        out = engine.pixel_shifts(lat, h, w, float(pixel_spacing))
+        return out.to(out_dev)

@@ -12,7 +12,7 @@ from typing import Union
 import numpy as np
 import torch
 
-from .api import _say
+from ._lib import say
 
 
 def write_deformation_field_to_csv(deformation_field: torch.Tensor, output_path: Union[str, Path]) -> None:
@@ -30,8 +30,8 @@ def write_deformation_field_to_csv(deformation_field: torch.Tensor, output_path:
     output_path = Path(output_path)
     output_path.parent.mkdir(parents=True, exist_ok=True)
     df.to_csv(output_path, index=False)
-    _say(f"Deformation field written to {output_path}")
-    _say(f"CSV contains {len(df)} rows with {t} time points and {h * w} spatial positions per time point")
+    say(f"Deformation field written to {output_path}")
+    say(f"CSV contains {len(df)} rows with {t} time points and {h * w} spatial positions per time point")
 
 
 def read_deformation_field_from_csv(csv_path: Union[str, Path], device: torch.device = None) -> torch.Tensor:
@@ -51,5 +51,5 @@ def read_deformation_field_from_csv(csv_path: Union[str, Path], device: torch.de
     field = np.zeros((2, len(axes[0]), len(axes[1]), len(axes[2])), dtype=np.float32)
     field[0, pos[0], pos[1], pos[2]] = df["y_shift"].to_numpy(dtype=np.float32)
     field[1, pos[0], pos[1], pos[2]] = df["x_shift"].to_numpy(dtype=np.float32)
-    _say(f"Detected dimensions: t={field.shape[1]}, h={field.shape[2]}, w={field.shape[3]}")
+    say(f"Detected dimensions: t={field.shape[1]}, h={field.shape[2]}, w={field.shape[3]}")
     return torch.from_numpy(field).to(device)

@@ -19,8 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib, engine
-from ._lib import check, ptr, require_gpu, stream_ptr
-from .api import _on_gpu, _out_device
+from ._lib import check, gpu_entry, ptr, stream_ptr
+from ._lib import require_gpu  # noqa: F401  (unused here; tests/test_magnification_host.py patches this name)
 
 SCALE_MIN, SCALE_MAX = 0.9, 1.1  # of major_scale and minor_scale; bounds the source footprint of an output tile
 
@@ -100,15 +100,6 @@ def _resample(src, matrix, fill_value, out=None):
     return out
 
 
-@_on_gpu
-def _correct(image, matrix, fill_value, device=None):
-    out_dev = _out_device(image, device)
-    dev = require_gpu(out_dev)
-    src = image.detach().to(dev).contiguous()
-    out = _resample(src if src.dim() == 3 else src[None], matrix, fill_value)
-    return (out if image.dim() == 3 else out[0]).to(out_dev)
-
-
 def correct_magnification_distortion(image, major_scale, minor_scale, major_axis_angle, fill_value=0.0, device=None):
     """A sum ``(h, w)`` or a stack ``(t, h, w)`` with the microscope's anisotropic magnification distortion removed
     -> float32 of the same shape.  Correct the sums, or the aligned stack, after motion correction and before CTF
@@ -132,4 +123,8 @@ def correct_magnification_distortion(image, major_scale, minor_scale, major_axis
     touched."""
     _check_image(image)
     matrix = magnification_distortion_matrix(major_scale, minor_scale, major_axis_angle)
-    return _correct(image, matrix, _real(fill_value, "fill_value"), device=device)
+    fill_value = _real(fill_value, "fill_value")
+    with gpu_entry(image, device) as (out_dev, dev):
+        src = image.detach().to(dev).contiguous()
+        out = _resample(src if src.dim() == 3 else src[None], matrix, fill_value)
+        return (out if image.dim() == 3 else out[0]).to(out_dev)
