@@ -806,6 +806,23 @@ int mc_raw_orient(const void* in, int elem_bytes, int n, int h, int w, int rot90
 int mc_affine_resample(const void* src, int storage, int nframes, int h, int w, const double m[4] /* host */,
                        float fill_value, float* dst, void* stream);
 
+/* The aligned sum of a movie with the magnification map folded into the rigid warp: ONE bicubic resampling per frame
+ * (the rule is stated in csrc/affine_warp_sum.h over csrc/affine_resample.h).  src (device): contiguous (t, h, w)
+ * samples of `storage`, any MC_STORE_* kind; gain (h, w) fp32 and mu (t) fp32 from mc_raw_movie_stats (device) are
+ * read for MC_STORE_U8 / MC_STORE_I16 only, whose samples enter as fp32(raw) * gain - mu[f], product and difference
+ * rounded separately as mc_condition_movie rounds them.  m (host, read before the call returns): m00, m01, m10, m11 in
+ * (y, x) order; shifts (device): (t, 2) fp32 pixel shifts (y, x) of the frames.  Output pixel (y, x) samples frame f
+ * at py = ((cy + m00 (y - cy)) + m01 (x - cx)) + shifts[f][0], px likewise with shifts[f][1], in float64 on the device;
+ * a position outside [0, h - 1] x [0, w - 1] contributes exactly 0, any other the 4 x 4 Keys (A = -0.75) sum of
+ * mc_affine_resample.  sum (h, w) fp32 = ((0 + v_0) + v_1) + ... + v_{t-1}, one accumulator per pixel in registers;
+ * frames: NULL, or (t, h, w) fp32 that receives every v_f.  One 64 x 64 output tile per workgroup, the frames in a loop,
+ * each frame's source window staged in LDS; no scratch, no atomics, bits independent of the launch geometry.
+ * Before anything is launched: MC_ERR_ARG for a null src, m, shifts or sum, t < 1, h < 4 or w < 4, a storage outside
+ * 0 .. 3, a null gain or mu with MC_STORE_U8 / MC_STORE_I16, an m that mc_affine_resample refuses, a misaligned
+ * pointer and outputs that overlap src or each other; MC_ERR_UNSUPPORTED for h * w >= 2^31. */
+int mc_affine_warp_sum(const void* src, int storage, const float* gain, const float* mu, int t, int h, int w,
+                       const double* m /* host: 4 doubles */, const float* shifts, float* sum, float* frames, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

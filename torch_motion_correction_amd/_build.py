@@ -51,6 +51,8 @@ SOURCES = [("xcg_rows_inv.hip", "xcg_rows_inv", []), ("xcg_cols_inv.hip", "xcg_c
            ("eer_render.hip", "eer_render", []),
            # frames through a 2 x 2 linear map, bicubic (magnification distortion), over affine_resample.h
            ("affine_resample.hip", "affine_resample", []),
+           # the aligned sum with that map folded into the rigid warp, over affine_warp_sum.h
+           ("affine_warp_sum.hip", "affine_warp_sum", []),
            # raw movies -> LZW TIFF strips, over tiff_lzw_encode.h; LZW / stored TIFF strips -> raw movies, over
            # tiff_lzw.h
            ("tiff_encode.hip", "tiff_encode", []), ("tiff_decode.hip", "tiff_decode", [])]

@@ -107,6 +107,7 @@ SIGNATURES = {
     "mc_mrc_encode": [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp],
     "mc_raw_orient": [vp, i32, i32, i32, i32, i32, i32, vp, vp],
     "mc_affine_resample": [vp, i32, i32, i32, i32, C.POINTER(C.c_double), f32, vp, vp],
+    "mc_affine_warp_sum": [vp, i32, vp, vp, i32, i32, i32, C.POINTER(C.c_double), vp, vp, vp, vp],
     "mc_condition_movie": [vp, i32, vp, i32, i64, i32, vp, vp, vp],
     "mc_raw_movie_stats": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "mc_xc_rows_forward_raw": [vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, GP, vp, vp],

@@ -8,6 +8,12 @@ the corrected image samples the distorted one at c + D (p - c), c = (h // 2, w /
 ``major_scale`` along the angle returns to scale 1.  M is D rewritten in (y, x) order.  This is the package's OWN sign
 and angle convention: it has not been checked against output of MotionCor2 or cisTEM, none of which was available where
 this was written.  The resampling rule itself is stated once, in csrc/affine_resample.h.
+
+THE ALIGNED SUM IN ONE RESAMPLING.  ``motion_correct_sum_magnified`` and ``motion_correct_sum_magnified_raw``
+(mc_affine_warp_sum, csrc/affine_warp_sum.hip over csrc/affine_warp_sum.h) fold M into the rigid warp: frame f is
+sampled once, at c + M (p - c) + shift_f, and the frames are added as they are formed -- one interpolation instead of
+the rigid warp's followed by ``correct_magnification_distortion``'s, and for a raw uint8 / int16 movie no conditioned
+fp32 copy of it.
 """
 
 from __future__ import annotations
@@ -128,3 +134,126 @@ def correct_magnification_distortion(image, major_scale, minor_scale, major_axis
         src = image.detach().to(dev).contiguous()
         out = _resample(src if src.dim() == 3 else src[None], matrix, fill_value)
         return (out if image.dim() == 3 else out[0]).to(out_dev)
+
+
+# ------------------------------------------------------------------ the aligned sum with M folded into the rigid warp
+
+
+def _check_stack(stack, name, dtypes, names):
+    if not isinstance(stack, torch.Tensor) or stack.dim() != 3 or stack.dtype not in dtypes:
+        raise ValueError(f"{name} must be a (t, h, w) tensor of dtype {names}, got "
+                         f"{getattr(stack, 'dtype', type(stack).__name__)} {tuple(getattr(stack, 'shape', ()))}")
+    if stack.numel() == 0:
+        raise ValueError(f"{name} must not be empty, got shape {tuple(stack.shape)}")
+    h, w = stack.shape[-2:]
+    if h < 4 or w < 4:
+        raise ValueError(f"{name} must have at least 4 rows and 4 columns, got shape {tuple(stack.shape)}")
+    if h * w >= 2**31:
+        raise ValueError(f"{name} shape {tuple(stack.shape)}: frames of 2^31 samples and more are not supported")
+
+
+def _pixel_shifts(deformation_grid, t, pixel_spacing):
+    """The (t, 2) fp32 pixel shifts (y, x), on the CPU, of a rigid (2, t, 1, 1) Angstrom field with one node per frame:
+    the correctly rounded fp32 quotient fp32(L) / fp32(ps), true division of a CPU tensor by an fp32 tensor (the
+    canonical rule of the rigid warp; a multiply by the fp32 reciprocal is one ulp off for some shifts).  Every rule
+    of the field and of the spacing is a ValueError."""
+    field = deformation_grid
+    if not isinstance(field, torch.Tensor) or field.dim() != 4 or field.shape[0] != 2 or min(field.shape) < 1:
+        raise ValueError(f"deformation_grid must be a (2, t, 1, 1) tensor, got {tuple(getattr(field, 'shape', ()))}")
+    if tuple(field.shape[-2:]) != (1, 1):
+        raise ValueError(f"deformation_grid must be a rigid (2, t, 1, 1) field, one shift per frame, got shape "
+                         f"{tuple(field.shape)}: a local field (more than one patch) is not supported by the "
+                         "magnified sum")
+    if field.shape[1] != t:
+        raise ValueError(f"deformation_grid has {field.shape[1]} time points, the movie {t} frames")
+    if not field.dtype.is_floating_point:
+        raise ValueError(f"deformation_grid must be a floating-point tensor, got {field.dtype}")
+    ps = _real(pixel_spacing, "pixel_spacing")
+    if not ps > 0.0:
+        raise ValueError(f"pixel_spacing must be > 0, got {pixel_spacing!r}")
+    lattice = field.detach()[:, :, 0, 0].to(device="cpu", dtype=torch.float32)
+    if not bool(torch.isfinite(lattice).all()):
+        raise ValueError("deformation_grid must be finite: it holds a value that is not a finite number")
+    shifts = torch.div(lattice, torch.tensor(ps, dtype=torch.float32))
+    if not bool(torch.isfinite(shifts).all()):
+        raise ValueError(f"deformation_grid / pixel_spacing overflows fp32 (pixel_spacing {ps!r})")
+    return shifts.t().contiguous()
+
+
+def _warp_sum(src, kind, gain, mu, matrix, shifts, want_frames, out=None):
+    """mc_affine_warp_sum on the current GPU: `src` (t, h, w) of storage `kind` there, `gain` / `mu` for the raw
+    kinds, `shifts` (t, 2) fp32 on the CPU -> (sum (h, w) fp32, frames (t, h, w) fp32 or None).  `out`: the
+    (sum, frames or None) buffers to write (the tests' guarded buffers)."""
+    lib = _lib.load()
+    t, h, w = src.shape
+    dev = src.device
+    total, frames = out if out is not None else (
+        torch.empty((h, w), dtype=torch.float32, device=dev),
+        torch.empty((t, h, w), dtype=torch.float32, device=dev) if want_frames else None)
+    m = (C.c_double * 4)(*(float(v) for v in matrix.reshape(-1).tolist()))
+    sh = shifts.to(dev)
+    check(lib.mc_affine_warp_sum(ptr(src), kind, ptr(gain), ptr(mu), t, h, w, m, ptr(sh), ptr(total), ptr(frames),
+                                 stream_ptr(dev)), "mc_affine_warp_sum")
+    return total, frames
+
+
+def motion_correct_sum_magnified(image, deformation_grid, pixel_spacing, major_scale, minor_scale, major_axis_angle,
+                                 return_frames=False, device=None):
+    """The aligned sum of a movie with the magnification distortion removed, each frame interpolated ONCE -> the
+    ``(h, w)`` float32 sum, or ``(sum, frames (t, h, w))`` with ``return_frames``.
+
+    What ``correct_magnification_distortion(motion_correct_sum(image, ...), ...)`` does with two bicubic passes (the
+    rigid warp, then the 2 x 2 map) is done here with one: output pixel p of frame f samples it at
+    c + M (p - c) + s_f, c = (h // 2, w // 2), in float64 on the device, with the 4 x 4 Keys weights of
+    ``correct_magnification_distortion`` in fp32 and taps beyond the edge clamped to it; a position outside
+    [0, h - 1] x [0, w - 1] contributes exactly 0, the rigid warp's rule (there is no ``fill_value``).  The sum is the
+    fp32 sequence ((0 + v_0) + v_1) + ... in frame order, one accumulator per pixel: its bits do not depend on the
+    launch.  csrc/affine_warp_sum.h states the rule.
+
+    ``image``: a (t, h, w) float32 or float16 stack (fp16 is read from its bytes; the result is that of the up-cast
+    input, bit for bit), CPU or GPU, h, w >= 4.  ``deformation_grid``: a rigid (2, t, 1, 1) field in Angstrom with one
+    node per frame, (y, x) as for ``motion_correct_sum``; the pixel shift is the correctly rounded fp32 quotient
+    ``fp32(field) / fp32(pixel_spacing)`` and, as in the rigid warp, a sample is taken at p + s.  A local field
+    (more than one patch) is a ValueError: the general-field warp with M folded in is not built.  ``major_scale``,
+    ``minor_scale``, ``major_axis_angle``: as ``magnification_distortion_matrix`` takes them (the package's own
+    convention).
+
+    There is no hot-pixel step and no dose weighting here: a dose-weighted sum needs a transform per frame.  The
+    result is on ``device`` if given, else on the device of ``image``; a CPU image is staged to the current GPU and
+    the result copied back.  There is no CPU fallback.  Every argument rule is a ValueError raised before any device
+    is touched."""
+    _check_stack(image, "image", (torch.float32, torch.float16), "float32 or float16")
+    shifts = _pixel_shifts(deformation_grid, image.shape[0], pixel_spacing)
+    matrix = magnification_distortion_matrix(major_scale, minor_scale, major_axis_angle)
+    want_frames = bool(return_frames)
+    with gpu_entry(image, device) as (out_dev, dev):
+        src = image.detach().to(dev).contiguous()
+        total, frames = _warp_sum(src, engine.storage_of(src), None, None, matrix, shifts, want_frames)
+        return (total.to(out_dev), frames.to(out_dev)) if want_frames else total.to(out_dev)
+
+
+def motion_correct_sum_magnified_raw(movie, gain, deformation_grid, pixel_spacing, major_scale, minor_scale,
+                                     major_axis_angle, mean_zero=True, return_frames=False, device=None):
+    """``motion_correct_sum_magnified(condition_movie(movie, gain, mean_zero), ...)`` for a RAW uint8 / int16 movie,
+    without the conditioned fp32 movie: one statistics pass (engine.RawMovie) gives the frame means, and the kernel
+    forms ``fp32(raw) * gain - frame mean`` as ``condition_movie`` rounds it (product and difference rounded
+    separately) on its way into the resampler's window, once per sample.  With the frame means of that pass equal to
+    ``condition_movie``'s -- always without ``mean_zero``; with it, wherever both kernels sum a frame in the same
+    order (w % 8 == 0) -- the result is that composition's bit for bit.
+
+    ``movie``: (t, h, w) uint8 or int16, CPU or GPU; ``gain``: (h, w), or None for ones.  Every other argument, the
+    sampling rule and the result are ``motion_correct_sum_magnified``'s.  There is no hot-pixel step and no dose
+    weighting here; there is no CPU fallback; every argument rule is a ValueError raised before any device is
+    touched."""
+    _check_stack(movie, "movie", (torch.uint8, torch.int16), "uint8 or int16")
+    if gain is not None and (not isinstance(gain, torch.Tensor) or tuple(gain.shape) != tuple(movie.shape[-2:])):
+        raise ValueError(f"gain reference has shape {tuple(getattr(gain, 'shape', ()))}, frames are "
+                         f"{tuple(movie.shape[-2:])}")
+    shifts = _pixel_shifts(deformation_grid, movie.shape[0], pixel_spacing)
+    matrix = magnification_distortion_matrix(major_scale, minor_scale, major_axis_angle)
+    want_frames = bool(return_frames)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        rm = engine.RawMovie(movie.detach().to(dev), None if gain is None else gain.detach().to(dev),
+                             mean_zero=bool(mean_zero))
+        total, frames = _warp_sum(rm.raw, rm.kind, rm.gain, rm.mu, matrix, shifts, want_frames)
+        return (total.to(out_dev), frames.to(out_dev)) if want_frames else total.to(out_dev)
