@@ -3,7 +3,7 @@ stage: the forward spectra (workgroup rows + Stockham columns, the wave-per-row 
 chords on and off and forced back to the workgroup kernel, radix-16 4096-row and wave 1024-row columns and their
 Stockham fallback, the fused-statistics route and its fix-up, fp16 stacks read natively, chirp-z / direct mixed-radix /
 odd unpacked lines, patch jobs with per-job mask exponents through the dual wave kernel and through two ordinary
-passes, raw u8 / i16 movies), the correlation map seen through its arg-max and 3 x 3 neighbourhood (separate kernels,
+passes, raw u8 / i16 movies and patch jobs), the correlation map seen through its arg-max and 3 x 3 neighbourhood (separate kernels,
 the chirp-z engine's, the fused near-window search and its device-side fallback, several workspace chunks), the
 parabola on planted fractional drifts, and mc_field_accumulate on hand-built input.  No frame, pair or bin is skipped;
 the only tolerance on the arg-max is 2E.  Every test asserts which entry points of libmcorr ran (a recorder around
@@ -42,7 +42,11 @@ arg-max deficit / neighbourhood / parabola (the oracle column adds the map itsel
   chirp-z M = 5120, 10240, 16384                                   0.016 / 0.009    0.013 / 0.009
   patch jobs 1024, dual wave kernel, fp32 / fp16                   0.025 / 0.035    0.023 / 0.031
   patch jobs 1024 / 48 / 63 / 80, two ordinary passes              0.033 / 0.030    0.031 / 0.008
-  raw u8 / i16 + gain                                              0.035 / 0.013
+  raw patch jobs 1024, u8 / i16 + gain, dual / single              0.020 / 0.014    0.016 / 0.006
+  raw patch jobs (16, 1024): ny = 16, the group tail (1024: 800)   0.026 / 0.007    0.035 / 0.005
+  raw u8 / i16, gain 1 +- 0.05, 1024 / 4096 / 5760 / 11520 columns 0.035 / 0.013
+  the same movies, gain log-uniform in [0.25, 4]                   0.027 / 0.013
+  raw (2, 512, 4096) without row chords, both gains                0.020 / 0.012
   separate kernels 256 / 512: arg-max / nb / parabola              0 / 0.079 / 0.017      0.012 / 0.058; 0 / 0.058 / 0.007
   chirp-z engine (mc_xcg_*) (100, 120), (121, 135), (96, 5760)     0 / 0.033 / 0.004      0.005 / 0.020; 0 / 0.020 / 0.003
   fused near-window search (1024, 1024), (4096, 256)               0 / 0.159 / 0.040      0.013 / 0.093; 0 / 0.092 / 0.019
@@ -57,8 +61,18 @@ in all).  The near-tie cases ('tie': xc_reference.tied, two exactly tied maxima 
 tolerant branch of the criterion, on the separate, the chirp-z and the fused path; white noise almost never ties
 within 2E, so the pure-noise cases mostly reduce to the unique maximum and are kept as the inputs on which the
 branch and bound cannot prune.  mc_xcg_peak_neighbourhood is judged against E alone, like the row transform.  No
-kernel is outside its bound and none was changed.  On the MI355X the file's 113 tests take 13 s in all; the
-(3, 4096, 4096) case is the slowest with 2.0 s, every other test stays under 0.8 s.
+kernel is outside its bound and none was changed.
+
+The raw patch jobs (mc_xc_rows_forward_dual_raw: the wave-per-patch-row kernel reading u8 / i16 bytes and the gain)
+run on xc_reference.raw_patch_input: frames of an odd width, jobs at odd origins in both frames and not sorted by
+frame, a gain of dynamic range 16, a brighter second frame (so the per-job subtrahends differ), i16 counts negative
+in both halves of a pair, the (1, 2) exponent pair and the power loops in one launch; dual and single, row chords
+on and off, in workspace chunks, and on the one plan whose ny % 32 != 0 (window (16, 1024): ny = 16; (1024, 1024):
+ny = 800).  tests/test_xc_reference_host.py holds an fp32 restatement of that pass on the same input inside the same
+bounds (the oracle column) and plants the faults the RAW branch could make, each of which leaves the bound.
+
+On the MI355X the file's 138 tests take 16 s in all; the (3, 4096, 4096) case is the slowest with 2.0 s, the first
+raw patch test, which builds the float64 reference the others share, takes 1.1 s, every other test stays under 0.8 s.
 """
 
 import contextlib
@@ -70,13 +84,14 @@ import torch
 
 import xc_reference as xr
 from global_refine_reference import planted_movie
-from kernel_harness import calls, switches  # noqa: F401
+import kernel_harness
+from kernel_harness import calls, nan_empty, switches  # noqa: F401
 from rigid_reference import condition_float64, conditioning_error
 
 pytestmark = pytest.mark.gpu
 
 U = xr.U
-STORE_F16, STORE_F32 = 2, 3
+MC_STORE_U8, MC_STORE_I16, STORE_F16, STORE_F32 = 0, 1, 2, 3  # MC_STORE_* of include/mcorr.h
 
 
 @contextlib.contextmanager
@@ -480,16 +495,144 @@ def test_patch_jobs_two_ordinary_passes(dev, calls, switches, p):
         print(f"RATIO patch jobs {p} two passes {tag}: L2 {r[0]:.3f} bin {r[1]:.3f}")
 
 
-# ------------------------------------------------------------------ raw movies
+# ------------------------------------------------------------------ raw patch jobs
+
+
+def _arg(name, param):
+    """Position of the argument `param` of the entry point `name`, read from its declaration in include/mcorr.h (and
+    the declaration has as many arguments as _lib.SIGNATURES[name])."""
+    import os
+    import re
+
+    from torch_motion_correction_amd import _lib
+
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mcorr.h")) as fh:
+        decl = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", fh.read(), flags=re.M | re.S).group(1)
+    names = [re.search(r"(\w+)\s*$", a).group(1) for a in decl.split(",")]
+    assert len(names) == len(_lib.SIGNATURES[name]) and names.count(param) == 1, (name, names)
+    return names.index(param)
+
+
+@pytest.fixture
+def nan_outputs(monkeypatch, nan_empty):  # noqa: F811
+    """kernel_harness.nan_empty, and the same for torch.empty_like: the dual form's second spectrum and second T1 are
+    allocated with it, and a buffer the allocator hands out again may hold the previous test's correct values."""
+    real = torch.empty_like
+
+    def empty_like(*a, **k):
+        out = real(*a, **k)
+        return out.fill_(float("nan")) if out.is_floating_point() else out
+
+    monkeypatch.setattr(torch, "empty_like", empty_like)
+
+
+def _raw_patch_spectra(engine, calls, dev, kind, h, dual):
+    """xr.RAW_PATCH_JOBS of xr.raw_patch_input(kind, h) through the engine's own seam, engine.raw._patch_spectra_raw
+    -> (sub, rstd read back from the RawMovie, plan args, S or (Sa, Sb)); the recorder holds that call alone."""
+    raw, gain = xr.raw_patch_input(kind, h)
+    _, H, W = raw.shape
+    rm = engine.RawMovie(raw.to(dev), gain.to(dev))
+    pa = xr.args(h, 1024)
+    pl = _plan(pa, dev)
+    off = torch.tensor(xr.check_raw_patch_jobs(h), dtype=torch.int64, device=dev)
+    ea, eb = (torch.tensor(e, dtype=torch.int32, device=dev) for e in xr.RAW_PATCH_EXPO)
+    frames = np.array([f for f, _, _ in xr.RAW_PATCH_JOBS])
+    calls.clear()
+    out = engine.raw._patch_spectra_raw(rm, pl)(off, ea, frames, eb if dual else None, min_expo=1)
+    torch.cuda.synchronize()
+    calls.ran("mc_xc_rows_forward_dual_raw", "mc_xc_cols_forward",
+              absent=("mc_xc_rows_forward", "mc_xc_rows_forward_dual_t", "mc_condition_movie"))
+    name = "mc_xc_rows_forward_dual_raw"
+    for a in calls.args[name]:
+        assert a[_arg(name, "storage")] == {"u8": MC_STORE_U8, "i16": MC_STORE_I16}[kind]
+        assert a[_arg(name, "frame_area")] == H * W and a[_arg(name, "row_stride")] == W
+        assert (a[_arg(name, "expo_b")] is not None) == dual and (a[_arg(name, "T1b")] is not None) == dual
+        assert (a[_arg(name, "row_chord")] is not None) == bool(engine.USE_ROW_CHORDS)
+    sub, rstd = rm.sub.cpu().numpy(), float(rm.mean_rstd.cpu()[1])
+    # a job that took the other frame's subtrahend would be off by a constant of this many standard deviations
+    assert float(sub[1] - sub[0]) >= 0.25 * abs(float(sub[0])) and float(sub[1] - sub[0]) * rstd >= 0.25, (sub, rstd)
+    return sub, rstd, pa, out
+
+
+def _raw_patch_check(kind, pa, sub, rstd, spectra, what):
+    worst = []
+    for S, ex, tag in zip(spectra, xr.RAW_PATCH_EXPO, "ab"):
+        parts, bounds = xr.raw_patch_reference(kind, pa, sub, rstd, ex)
+        r = xr.check_spectra(S, parts, bounds, f"{what} {tag}")
+        print(f"RATIO raw patch jobs {what} {tag} (conditioning {bounds[0]['conditioning'] / U:.1f} u of "
+              f"{bounds[0]['rel'] / U:.0f} u): L2 {r[0]:.3f} bin {r[1]:.3f}")
+        worst.append(r)
+    return worst
+
+
+@pytest.mark.parametrize("chords", [True, False], ids=["chords", "no-chords"])
+@pytest.mark.parametrize("kind", ["u8", "i16"])
+def test_raw_patch_jobs_dual(dev, calls, switches, nan_outputs, kind, chords):
+    """mc_xc_rows_forward_dual_raw, both spectra from one read of the raw rows: five 1024-px jobs in two frames of
+    (1033, 1039) u8 / i16 counts -- an odd frame width, which engine.RawMovie and mc_raw_movie_stats take (the scalar
+    statistics kernel) -- not sorted by frame, at odd origins, one at the origin of frame 1; a gain of dynamic range
+    16; frame 1 brighter, so the per-job subtrahends differ; i16 counts negative in both halves of a pair; exponents
+    (1, 2, 3, 1, 1) and (2, 4, 6, 2, 2): the (1, 2) fast path and the power loops in one launch; row chords on and
+    off.  Against the float64 conditioning with the statistics the kernel was given, output buffers NaN-filled."""
+    engine, plan = switches
+    engine.USE_ROW_CHORDS = chords
+    sub, rstd, pa, out = _raw_patch_spectra(engine, calls, dev, kind, 1024, dual=True)
+    assert calls.count("mc_xc_rows_forward_dual_raw") == 1 and calls.count("mc_xc_cols_forward") == 2
+    _raw_patch_check(kind, pa, sub, rstd, out, f"1024 {kind} dual chords={chords}")
 
 
 @pytest.mark.parametrize("kind", ["u8", "i16"])
-@pytest.mark.parametrize("shape", [(3, 512, 1024), (2, 512, 4096), (2, 96, 5760)], ids=lambda s: "x".join(map(str, s)))
-def test_raw_movies(dev, calls, switches, shape, kind):
-    """engine._global_spectra_raw on u8 and i16 counts with a gain reference: the workgroup kernel (1024 columns),
-    the wave-per-row kernel (4096) and the direct 2880-point rows (5760), against the float64 conditioning
-    (raw * gain - sub_f) * rstd with the statistics the kernels were given; the bound includes the conditioning term."""
+def test_raw_patch_jobs_single(dev, calls, switches, nan_outputs, kind):
+    """The same jobs with one exponent per job (no second exponent list, no second T1): the single-spectrum form,
+    whose power loop runs over expo_a, against the bounds of the dual form's first spectrum."""
     engine, plan = switches
+    sub, rstd, pa, S = _raw_patch_spectra(engine, calls, dev, kind, 1024, dual=False)
+    assert calls.count("mc_xc_rows_forward_dual_raw") == 1 and calls.count("mc_xc_cols_forward") == 1
+    _raw_patch_check(kind, pa, sub, rstd, (S,), f"1024 {kind} single")
+
+
+def test_raw_patch_jobs_in_chunks(dev, calls, switches, nan_outputs):
+    """WORKSPACE_BYTES lowered to two jobs per chunk: three launches (2 + 2 + 1 jobs), each with its own slice of the
+    offsets, the exponents and the per-job subtrahends -- bit for bit the spectra of the one launch."""
+    engine, plan = switches
+    sub, rstd, pa, whole = _raw_patch_spectra(engine, calls, dev, "u8", 1024, dual=True)
+    g = xr.geometry(pa)
+    engine.WORKSPACE_BYTES = 2 * g.nkx * g.ny * 8 * 2
+    assert engine._chunks(5, g.nkx * g.ny * 8 * 2) == (2, [(0, 2), (2, 2), (4, 1)])
+    sub2, rstd2, _, parts = _raw_patch_spectra(engine, calls, dev, "u8", 1024, dual=True)
+    assert calls.count("mc_xc_rows_forward_dual_raw") == 3 and calls.count("mc_xc_cols_forward") == 6
+    name = "mc_xc_rows_forward_dual_raw"
+    assert [a[_arg(name, "njobs")] for a in calls.args[name]] == [2, 2, 1]
+    assert np.array_equal(sub, sub2) and rstd == rstd2
+    assert torch.equal(whole[0], parts[0]) and torch.equal(whole[1], parts[1])
+    _raw_patch_check("u8", pa, sub, rstd, parts, "1024 u8 dual in chunks")
+
+
+@pytest.mark.parametrize("kind", ["u8", "i16"])
+def test_raw_patch_jobs_group_tail(dev, calls, switches, nan_outputs, kind):
+    """The row groups' tail, rounds = min(4, (ny - r16) / 8) with ny % 32 != 0.  ny follows from the window height
+    alone (the mask's rows, rounded to the row grouping of 16), and among the heights whose column pass is
+    mc_xc_cols_forward only h = 16 has ny % 32 != 0: ny = 16, two rounds in one group; the 1024 x 1024 window of the
+    other tests has ny = 800, whole groups of four rounds.  Same jobs, gain, frame brightness and exponents, frames of
+    (25, 1039)."""
+    engine, plan = switches
+    ny = {h: xr.geometry(xr.args(h, 1024)).ny for h in xr.RAW_PATCH_HEIGHTS}
+    print(f"raw patch jobs: ny = {ny[1024]} for the (1024, 1024) window, ny = {ny[16]} for the (16, 1024) window")
+    assert ny[1024] % 32 == 0 and ny[16] % 32 != 0 and ny[16] % 8 == 0
+    sub, rstd, pa, out = _raw_patch_spectra(engine, calls, dev, kind, 16, dual=True)
+    _raw_patch_check(kind, pa, sub, rstd, out, f"16 {kind} dual")
+
+
+# ------------------------------------------------------------------ raw movies
+
+
+RAW_SHAPES = [(3, 512, 1024), (2, 512, 4096), (2, 96, 5760), (2, 96, 11520)]
+
+
+def _raw_movie_case(engine, plan, calls, dev, shape, kind, wide_gain=False):
+    """One raw movie through engine._global_spectra_raw against the float64 conditioning (raw * gain - sub_f) * rstd
+    with the statistics the kernels were given; the bound includes the conditioning term.  `wide_gain`:
+    kernel_harness.gain (log-uniform in [0.25, 4]) instead of 1 + 0.05 randn."""
     t, h, w = shape
     g = torch.Generator().manual_seed(h + w + (kind == "u8"))
     if kind == "u8":
@@ -497,13 +640,20 @@ def test_raw_movies(dev, calls, switches, shape, kind):
     else:
         raw = torch.round(torch.randn(t, h, w, generator=g) * 30 + 1000).to(torch.int16)
     gain = (1.0 + 0.05 * torch.randn(h, w, generator=g)).float()
+    if wide_gain:
+        gain = kernel_harness.gain(h, w)
     rm = engine.RawMovie(raw.to(dev), gain.to(dev))
     calls.clear()
     S, pl = engine._global_spectra_raw(rm, t // 2, 1.0, xr.B_FACTOR, xr.DEFAULT_BAND)
     torch.cuda.synchronize()
     native = plan.native_rows(pl.geom)
+    assert native == (w != 5760 and w != 11520)
     calls.ran("mc_xc_rows_forward_raw" if native else "mc_xcg_rows_forward_raw", _cols_entry(plan, pl.geom),
               absent=("mc_xc_rows_forward", "mc_xcg_rows_forward", "mc_condition_movie"))
+    if native:  # the chord table goes to the kernel exactly when the switch is on
+        name = "mc_xc_rows_forward_raw"
+        assert pl.chord is not None
+        assert all((a[_arg(name, "row_chord")] is not None) == bool(engine.USE_ROW_CHORDS) for a in calls.args[name])
     sub = rm.sub.cpu().numpy()
     rstd = float(rm.mean_rstd.cpu()[1])
     v = condition_float64(raw.numpy(), gain.numpy(), sub)
@@ -514,9 +664,44 @@ def test_raw_movies(dev, calls, switches, shape, kind):
     for f in range(t):
         cond = np.linalg.norm(conditioning_error(raw[f].numpy(), gain.numpy(), sub[f]) * mask) / np.linalg.norm(v[f] * mask)
         bs.append(xr.spectra_bounds(pa, 0.0, 1.0 / rstd, conditioning=float(cond)))
-    r = xr.check_spectra(S, parts, bs, f"raw {kind} {shape}")
-    print(f"RATIO raw {kind} {shape} (conditioning {bs[0]['conditioning'] / U:.1f} u of {bs[0]['rel'] / U:.0f} u): "
+    what = f"raw {kind} {shape} {'gain [0.25, 4]' if wide_gain else 'gain 1 +- 0.05'} chords={bool(engine.USE_ROW_CHORDS)}"
+    r = xr.check_spectra(S, parts, bs, what)
+    print(f"RATIO {what} {bs[0]['kinds']} (conditioning {bs[0]['conditioning'] / U:.1f} u of {bs[0]['rel'] / U:.0f} u): "
           f"L2 {r[0]:.3f} bin {r[1]:.3f}")
+
+
+@pytest.mark.parametrize("kind", ["u8", "i16"])
+@pytest.mark.parametrize("shape", RAW_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_raw_movies(dev, calls, switches, shape, kind):
+    """engine._global_spectra_raw on u8 and i16 counts with a gain reference of 1 +- 0.05: the workgroup kernel (1024
+    columns), the wave-per-row kernel (4096, with its row chords) and the direct 2880- and 5760-point rows (5760 and
+    11520 columns, the K3 formats: mc_xcg_rows_forward_raw)."""
+    engine, plan = switches
+    assert engine.USE_ROW_CHORDS
+    _raw_movie_case(engine, plan, calls, dev, shape, kind)
+    assert calls.count("mc_xcg_rows_forward_raw") == (1 if shape[2] in (5760, 11520) else 0)
+
+
+@pytest.mark.parametrize("kind", ["u8", "i16"])
+@pytest.mark.parametrize("shape", RAW_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_raw_movies_gain_of_large_dynamic_range(dev, calls, switches, shape, kind):
+    """The same movies with kernel_harness.gain, log-uniform in [0.25, 4]: a gain read one row or column off changes
+    a sample by a factor, where a gain of 1 +- 0.05 changes it by a few percent."""
+    engine, plan = switches
+    _raw_movie_case(engine, plan, calls, dev, shape, kind, wide_gain=True)
+
+
+@pytest.mark.parametrize("wide_gain", [False, True], ids=["gain-near-1", "gain-wide"])
+@pytest.mark.parametrize("kind", ["u8", "i16"])
+def test_raw_movies_without_row_chords(dev, calls, switches, kind, wide_gain):
+    """(2, 512, 4096) with USE_ROW_CHORDS = False: engine._global_spectra_raw hands mc_xc_rows_forward_raw no chord
+    table (asserted on the recorded argument, whose position comes from the header), and the wave-per-row kernel
+    clamps its loads to the mask's bounding columns instead."""
+    engine, plan = switches
+    engine.USE_ROW_CHORDS = False
+    _raw_movie_case(engine, plan, calls, dev, (2, 512, 4096), kind, wide_gain)
+    name = "mc_xc_rows_forward_raw"
+    assert calls.count(name) == 1 and calls.args[name][0][_arg(name, "row_chord")] is None
 
 
 # ------------------------------------------------------------------ map, arg-max, neighbourhood

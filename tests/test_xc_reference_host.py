@@ -4,6 +4,10 @@ tests/global_refine_reference.py where the two overlap and against planted drift
 bound on every table case (a bound the oracle broke would be a wrong bound), the conditions that keep the arg-max
 criterion sharp (a unique float64 maximum by more than 2E on the planted cases; no gap and 2 .. MAX_TIES admissible
 positions on the constructed near-tie cases; at most MAX_TIES on pure noise), and deliberately wrong stand-ins that every comparison helper must reject.
+The raw patch row pass (mc_xc_rows_forward_dual_raw) has its own section: an fp32 restatement on the input the GPU
+test uses (xc_reference.raw_patch_input) inside the same bounds, the faults its RAW branch could make -- a gain
+column, the gain offset without the modulo, the other frame's subtrahend, a sample to the left, an unsigned i16
+half, the exponents exchanged -- each outside them, and the clamped loads shown to be an addressing matter only.
 
 The oracle's worst ratio per family is printed as `RATIO ...` (run with -s); those figures are the last column of
 the table in tests/test_xc_kernels_float64.py."""
@@ -149,6 +153,132 @@ def test_oracle_patch_spectra_stay_inside_the_bound(p):
     bs = [xr.spectra_bounds(pa, parts["mean"], parts["std"], expo=e) for e in expo]
     r = xr.check_spectra(_oracle_spectra(x, pa, jobs, expo), parts, bs, f"oracle patches {p}")
     print(f"RATIO oracle patch spectra {p}: L2 {r[0]:.3f} bin {r[1]:.3f}")
+
+
+# ------------------------------------------------------------------ raw patch jobs: the fp32 restatement and planted faults
+
+
+def _raw_patch_fp32(kind, h, sub, rstd, ex, fault=None, clamp=None, chords=True):
+    """The raw patch row pass + column pass (mc_xc_rows_forward_dual_raw, mc_xc_cols_forward) restated in fp32 torch on
+    the CPU for xr.RAW_PATCH_JOBS of xr.raw_patch_input(kind, h): per job the window of raw counts and of the gain
+    at the job's offset within its frame, (float32(raw) * gain - sub[frame]) * rstd with one rounding per operation
+    (no fma), times mask^e as a product of e factors, fp32 rfft2, the kept bins, the fp32 filter -> (njobs, nkx, nky).
+
+    `fault`: one deliberate error of the classes the kernel's RAW branch could make (the test below names them).
+    `clamp`: the kernel's addressing instead of the plain window -- a pair of samples at the even window column p is
+    read at min(max(p, xlo), xhi), xlo / xhi the row's chord (`chords`) or the mask's bounding columns, and rows
+    outside the mask's rows are not read at all; 'both' as the kernel, 'left' with the clamp on the right omitted."""
+    from torch_motion_correction_amd import plan
+
+    raw, gain = xr.raw_patch_input(kind, h)
+    _, H, W = raw.shape
+    pa = xr.args(h, 1024)
+    mask, benv, bandf = om._filters((h, 1024), pa[2], pa[3], pa[4])
+    g = xr.geometry(pa)
+    rows = torch.from_numpy(xr.kept_rows(g))
+    area = H * W
+    rflat = raw.reshape(-1)
+    gflat = gain.reshape(-1)
+    if fault == "gain without the modulo":  # what lies past the gain's end: modelled as the gain one row further down
+        gflat = torch.cat([gflat, gflat.roll(-W)])
+    sub = torch.from_numpy(np.asarray(sub, dtype=np.float32))
+    rstd = torch.tensor(float(rstd), dtype=torch.float32)
+    if clamp:
+        p = torch.arange(1024) & ~1
+        if chords:
+            ch = plan.row_chords(mask).long()
+            xlo, xhi = ch[:, 0:1], ch[:, 1:2] + 2
+        else:
+            xlo, xhi = torch.full((h, 1), g.x0), torch.full((h, 1), g.x1 - 2)
+        lo = torch.minimum(torch.maximum(p[None, :], xlo), xhi)
+        src = (lo if clamp == "both" else torch.maximum(p[None, :], xlo)) + (torch.arange(1024) & 1)[None, :]
+        live = torch.zeros(h, 1, dtype=torch.bool)
+        live[g.y0:g.y0 + g.ny] = True
+        assert not bool(mask[src != torch.arange(1024)[None, :]].any()) and not bool(mask[~live[:, 0]].any())
+    out = []
+    for (f, y0, x0), e in zip(xr.RAW_PATCH_JOBS, ex):
+        off = f * area + y0 * W + x0
+        goff = off if fault == "gain without the modulo" else off % area
+        if fault == "gain one column to the right":
+            goff += 1
+        if fault == "raw window one sample to the left":
+            off -= 1
+        win = torch.as_strided(rflat, (h, 1024), (W, 1), off)
+        gwin = torch.as_strided(gflat, (h, 1024), (W, 1), goff)
+        if clamp:
+            win, gwin = torch.gather(win, 1, src), torch.gather(gwin, 1, src)
+        x = win.float()
+        if fault == "i16 high half widened unsigned":
+            x[:, 1::2] = (win[:, 1::2].int() & 0xffff).float()
+        s = sub[1 - f] if fault == "sub of the other frame" else sub[f]
+        c = (x * gwin - s) * rstd
+        pw = mask.clone()
+        for _ in range(e - 1):
+            pw = pw * mask
+        c = c * pw
+        if clamp:
+            c = torch.where(live, c, torch.zeros(()))
+        spec = torch.fft.rfftn(c, dim=(-2, -1)) * bandf * benv
+        out.append(spec[rows][:, :g.nkx].T)
+    return torch.stack(out)
+
+
+def _raw_patch_case(kind, h):
+    """-> (sub, rstd, pa, [(exponents, parts, bounds) of the dual form's two spectra])."""
+    raw, gain = xr.raw_patch_input(kind, h)
+    sub, rstd = xr.raw_stats64(raw, gain)
+    pa = xr.args(h, 1024)
+    return sub, rstd, pa, [(ex,) + xr.raw_patch_reference(kind, pa, sub, rstd, ex) for ex in xr.RAW_PATCH_EXPO]
+
+
+@pytest.mark.parametrize("h", xr.RAW_PATCH_HEIGHTS)
+@pytest.mark.parametrize("kind", ["u8", "i16"])
+def test_raw_patch_restatement_stays_inside_the_bound(kind, h):
+    """The conditions of the raw patch test -- a gain of dynamic range 16, a second frame brighter by more than a
+    quarter of the mean, i16 counts negative in both halves of a pair, odd origins on an odd frame width -- are
+    satisfiable: a correct fp32 computation of the same jobs stays inside the bounds the kernel is held to, on the
+    1024 x 1024 window (ny = 800) and on the 16 x 1024 one (ny = 16: the plan whose ny % 32 != 0)."""
+    xr.check_raw_patch_jobs(h)
+    sub, rstd, pa, refs = _raw_patch_case(kind, h)
+    g = xr.geometry(pa)
+    assert (g.ny % 32 == 0) == (h == 1024) and g.ny % 8 == 0 and g.nkx <= 128 and g.W == 1024
+    assert float(sub[1] - sub[0]) * float(rstd) >= 0.25  # the other frame's subtrahend: a quarter of a std, >> any bound
+    for tag, (ex, parts, bounds) in zip("ab", refs):
+        assert float(sub[1] - sub[0]) * float(rstd) >= 1e4 * max(b["rel"] for b in bounds)
+        r = xr.check_spectra(_raw_patch_fp32(kind, h, sub, rstd, ex), parts, bounds, f"raw patch restatement {kind} {h} {tag}")
+        print(f"RATIO oracle raw patch jobs {h} {kind} {tag} (ny {g.ny}; conditioning {bounds[0]['conditioning'] / U:.1f} u of "
+              f"{bounds[0]['rel'] / U:.0f} u): L2 {r[0]:.3f} bin {r[1]:.3f}")
+
+
+RAW_FAULTS = ["gain one column to the right", "gain without the modulo", "sub of the other frame",
+              "raw window one sample to the left", "i16 high half widened unsigned", "ea and eb exchanged"]
+
+
+@pytest.mark.parametrize("kind,fault", [(k, f) for k in ("u8", "i16") for f in RAW_FAULTS if k == "i16" or not f.startswith("i16")])
+def test_raw_patch_planted_faults_are_caught(kind, fault):
+    """Each error the RAW branch could make, planted into the restatement, leaves the bound -- on the spectrum of
+    mask^ea and on that of mask^eb.  (Unsigned widening of the high half is an i16 matter; u8 has no such half.)"""
+    sub, rstd, pa, refs = _raw_patch_case(kind, 1024)
+    for i, (ex, parts, bounds) in enumerate(refs):
+        wrong_ex = xr.RAW_PATCH_EXPO[1 - i] if fault == "ea and eb exchanged" else ex
+        S = _raw_patch_fp32(kind, 1024, sub, rstd, wrong_ex, fault=fault)
+        with pytest.raises(AssertionError, match="job"):
+            xr.check_spectra(S, parts, bounds, f"{fault} {kind} {'ab'[i]}")
+
+
+@pytest.mark.parametrize("chords", [True, False])
+def test_raw_patch_clamp_is_only_an_addressing_matter(chords):
+    """The kernel reads a pair outside its row's chord (or the mask's bounding columns) at the clamped address; the
+    mask is exactly 0 there, so which sample it reads cannot matter.  Stated as a test: the restatement with the
+    kernel's clamped reads, with the clamp on the right omitted (the unclamped sample where the mask is 0) and with
+    plain window reads give the same spectra, all inside the bound -- this 'fault' must NOT be seen."""
+    sub, rstd, pa, refs = _raw_patch_case("i16", 1024)
+    ex, parts, bounds = refs[0]
+    plain = _raw_patch_fp32("i16", 1024, sub, rstd, ex)
+    for clamp in ("both", "left"):
+        S = _raw_patch_fp32("i16", 1024, sub, rstd, ex, clamp=clamp, chords=chords)
+        assert torch.equal(S, plain), clamp
+    xr.check_spectra(plain, parts, bounds, f"clamp chords={chords}")
 
 
 MAP_CASES = ([(c, k) for c in xr.MAP_SEPARATE + xr.MAP_FUSED for k in ("small", "large", "noise", "tie", "border")]

@@ -507,6 +507,114 @@ STAT_INPUTS = [(0.0, 1.0), (40.0, 2.5), (1000.0, 30.0)]
 MAP_SEPARATE = [(5, 256, 256), (4, 512, 512), (3, 100, 120), (2, 121, 135), (2, 96, 5760)]
 MAP_FUSED = [(6, 1024, 1024), (3, 4096, 256)]
 
+
+# ------------------------------------------------------------------ raw patch jobs (mc_xc_rows_forward_dual_raw)
+# One input for tests/test_xc_kernels_float64.py (the kernel) and tests/test_xc_reference_host.py (the fp32
+# restatement and the planted faults), so that the two cannot drift apart.
+
+RAW_PATCH_MARGIN = (9, 15)  # frames are (h + 9, 1024 + 15): an ODD width (1039), so row starts alternate in parity
+# (frame, y0, x0), not sorted by frame: x0 odd (13, 3, 15), x0 % 4 == 2 (6), y0 * W + x0 odd ((9, 6), (4, 15)), and the
+# origin of frame 1, whose offset is a whole frame: job_off % frame_area == 0 with job_off != 0
+RAW_PATCH_JOBS = [(1, 7, 13), (0, 1, 3), (1, 0, 0), (0, 9, 6), (1, 4, 15)]
+RAW_PATCH_EXPO = ((1, 2, 3, 1, 1), (2, 4, 6, 2, 2))  # the (1, 2) pair of the fast path and the power loops in one launch
+RAW_PATCH_HEIGHTS = (1024, 16)  # windows (h, 1024): ny = 800 (ny % 32 == 0) and ny = 16 (the group tail, ny % 32 != 0)
+RAW_KINDS = {"u8": torch.uint8, "i16": torch.int16}
+
+
+def raw_patch_frame(h):
+    return h + RAW_PATCH_MARGIN[0], 1024 + RAW_PATCH_MARGIN[1]
+
+
+def raw_patch_offsets(h, jobs=RAW_PATCH_JOBS):
+    H, W = raw_patch_frame(h)
+    return [f * H * W + y0 * W + x0 for f, y0, x0 in jobs]
+
+
+def check_raw_patch_jobs(h, jobs=RAW_PATCH_JOBS):
+    """The properties the job list is there for (asserted, not assumed)."""
+    H, W = raw_patch_frame(h)
+    off = raw_patch_offsets(h, jobs)
+    frames = [f for f, _, _ in jobs]
+    assert len(jobs) >= 5 and set(frames) == {0, 1} and frames != sorted(frames), jobs
+    assert all(0 <= y0 <= H - h and 0 <= x0 <= W - 1024 for _, y0, x0 in jobs), "a window leaves its frame"
+    assert W % 2 == 1 and (H * W) % 2 == 1
+    assert any(x0 % 2 == 1 for _, _, x0 in jobs) and any(x0 % 4 == 2 for _, _, x0 in jobs)
+    assert any((y0 * W + x0) % 2 == 1 for _, y0, x0 in jobs)
+    assert any(o != 0 and o % (H * W) == 0 for o in off), "no job at the origin of frame 1"
+    assert {o % 2 for o in off} == {0, 1} and any(o % 4 == 2 for o in off)
+    return off
+
+
+@functools.lru_cache(maxsize=4)
+def raw_patch_input(kind, h=1024):
+    """-> (raw (2, H, W) u8 / i16, gain (H, W) fp32) of the raw patch tests.  Counts: kernel_harness.drifting_raw_movie
+    (a texture in [10, 50) + noise), frame 1 drifted and BRIGHTER -- u8 by 12 counts of a mean of 30; i16 (8 v - 340
+    against 8 v - 240: means of about -100 and 0, a difference as large as the mean) -- so that a job that takes the
+    other frame's subtrahend is off by a constant of more than a quarter of a standard deviation, over ten thousand
+    times the bound (with a gain of this range the conditioned standard deviation is itself three quarters of the
+    brightness, so the difference cannot be many standard deviations; what counts is its size against the bound,
+    and both are asserted by the tests).  i16: four fifths of frame 0 and half of frame 1 are negative.  Gain: kernel_harness.gain, log-uniform
+    in [0.25, 4]."""
+    import kernel_harness as kh
+
+    H, W = raw_patch_frame(h)
+    dtype = RAW_KINDS[kind]
+    raw = kh.drifting_raw_movie([0, 3], [0, -2], H, W, dtype, seed=41 + h + (kind == "u8"))
+    if kind == "u8":
+        raw[1] += 12
+        assert int(raw.max()) < 250
+    else:
+        raw -= torch.tensor([240, 140], dtype=torch.int16)[:, None, None]
+        assert float((raw < 0).float().mean()) >= 0.25
+        for f, y0, x0 in RAW_PATCH_JOBS:  # negative counts in both halves of the pairs of every window
+            neg = raw[f, y0:y0 + h, x0:x0 + 1024] < 0
+            assert bool(neg[:, 0::2].any()) and bool(neg[:, 1::2].any()) and bool((neg[:, 0::2] & neg[:, 1::2]).any())
+    m = raw.double().mean(dim=(1, 2))
+    assert float(m[1] - m[0]) >= 0.25 * abs(float(m[0])), m
+    return raw, kh.gain(H, W)
+
+
+def raw_stats64(raw, gain):
+    """(sub (t,) fp32, rstd fp32) of engine.RawMovie(raw, gain) by raw_stats_finalize's formulas on float64 moments:
+    mu_f = fp32(frame mean of raw * gain), the mean and the unbiased std of raw * gain - mu_f over the central box of
+    all frames jointly, sub_f = fp32(mu_f + fp32(mean)), rstd = fp32(1 / std).  For the host tests, which have no
+    device to ask."""
+    x = raw.double().numpy() * gain.double().numpy()
+    _, H, W = x.shape
+    mu = x.mean(axis=(1, 2)).astype(F32)
+    c = (x - mu.astype(np.float64)[:, None, None])[:, int(0.25 * H):int(0.75 * H), int(0.25 * W):int(0.75 * W)]
+    return (mu + F32(c.mean())).astype(F32), F32(1.0 / c.std(ddof=1))
+
+
+@functools.lru_cache(maxsize=8)
+def _raw_patch_reference(kind, plan_args, sub, rstd, expo):
+    from rigid_reference import condition_float64, conditioning_error
+
+    h = int(plan_args[0])
+    raw, gain = raw_patch_input(kind, h)
+    sub = np.asarray(sub, dtype=F32)
+    std = 1.0 / float(rstd)
+    v = condition_float64(raw.numpy(), gain.numpy(), sub)
+    parts = spectra_parts(v, plan_args, RAW_PATCH_JOBS, expo, stats=(0.0, std))
+    mask = tables64(plan_args)[0]
+    bounds = []
+    for (f, y0, x0), e in zip(RAW_PATCH_JOBS, expo):
+        win = (slice(y0, y0 + h), slice(x0, x0 + 1024))
+        err = conditioning_error(raw[f][win].numpy(), gain[win].numpy(), sub[f])
+        c = float(np.linalg.norm(err * mask ** e) / np.linalg.norm(v[f][win] * mask ** e))
+        bounds.append(spectra_bounds(plan_args, 0.0, std, expo=e, conditioning=c))
+    return parts, bounds
+
+
+def raw_patch_reference(kind, plan_args, sub, rstd, expo):
+    """(parts, [bounds per job]) of RAW_PATCH_JOBS with the mask exponents `expo` on raw_patch_input(kind, h): the
+    float64 conditioning (raw * gain - sub_f) with the subtrahends and 1 / std the kernels were given, spectra_parts
+    with stats (0, 1 / rstd), and per job spectra_bounds with the conditioning term
+    ||conditioning_error mask^e||_2 / ||v mask^e||_2 over that job's window.  Computed once per argument set."""
+    return _raw_patch_reference(kind, _key(plan_args), tuple(float(s) for s in sub), float(rstd),
+                                tuple(int(e) for e in expo))
+
+
 def point_symmetric(x):
     """x + its point reflection about the mask centre (h // 2, w // 2), indices taken circularly: exactly symmetric
     in fp32 (a sum of two floats commutes)."""
