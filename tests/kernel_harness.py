@@ -1,6 +1,7 @@
 """What the float64 kernel tests (tests/test_*_kernels_float64.py and their neighbours) measure with, defined once:
-which entry points of libmcorr ran (Recorder, `calls`) and what the header says of them (header_signature), that nothing
-was written outside an output buffer (nan_buffer, assert_guards, nan_empty; byte_buffer, assert_byte_guards for the
+which entry points of libmcorr ran (Recorder, `calls`), what the header says of them and whether the ctypes table binds
+them so (header_signature, assert_entry_point), a host program built and run under the sanitizers as a child process
+(run_host_program), that nothing was written outside an output buffer (nan_buffer, assert_guards, nan_empty; byte_buffer, assert_byte_guards for the
 byte-moving kernels), the inputs (float_stack, raw_movie, gain, raw_setup), the worst error over bound per
 output family (ratios_fixture, worse) and the engine's test switches (`switches`).  tests/test_kernel_harness_host.py
 pins every one of them on the CPU.
@@ -10,12 +11,16 @@ A test module takes a fixture with `from kernel_harness import calls  # noqa: F4
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 GUARD = 8  # NaN words kept on either side of an output buffer
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "torch_motion_correction_amd", "csrc")
 
 
 # ------------------------------------------------------------------ the package, the library, which entry points ran
@@ -33,17 +38,6 @@ def lib():
     from torch_motion_correction_amd import _lib
 
     return _lib.load()
-
-
-def header_signature(name, header=None):
-    """The ctypes argument types of the entry point `name` as include/mcorr.h declares it (pointer, long long, int),
-    for comparison with _lib.SIGNATURES[name].  `header`: the header's text instead of the file's."""
-    if header is None:
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        with open(os.path.join(root, "include", "mcorr.h")) as fh:
-            header = fh.read()
-    args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
-    return [ctypes.c_void_p if "*" in a else ctypes.c_int64 if "long long" in a else ctypes.c_int for a in args]
 
 
 class Recorder:
@@ -87,6 +81,122 @@ def calls(monkeypatch):
     rec = Recorder(_lib.load())
     monkeypatch.setattr(_lib, "load", lambda: rec)
     return rec
+
+
+# ------------------------------------------------------------------ the header against the ctypes table
+
+SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_int64, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+           "unsigned": ctypes.c_uint, "double": ctypes.c_double}
+POINTEES = {"long long": ctypes.c_int64, "int64_t": ctypes.c_int64, "double": ctypes.c_double}  # + the two structs
+
+
+def header_text(header=None):
+    """include/mcorr.h (or `header`, a header's text) without its /* */ and // comments."""
+    if header is None:
+        with open(os.path.join(ROOT, "include", "mcorr.h")) as fh:
+            header = fh.read()
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", header, flags=re.S)
+
+
+def declared_entry_points(header=None):
+    """The names of the entry points (`int mc_x(...);`) the header declares."""
+    return set(re.findall(r"^int\s+(mc_\w+)\s*\(", header_text(header), flags=re.M))
+
+
+def header_parameters(name, header=None):
+    """The parameters of the entry point `name` as the header writes them, comments stripped and blanks folded:
+    ["const void* src", "int h", "const double m[4]", ...]; [] for (void).  KeyError where `name` is not declared."""
+    found = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header_text(header), flags=re.M | re.S)
+    if found is None:
+        raise KeyError(f"the header declares no {name}")
+    params = [" ".join(p.split()) for p in found.group(1).split(",")]
+    return [] if params in ([""], ["void"]) else params
+
+
+def _declared(name, header=None):
+    """Per parameter of `name`: (its ctypes type with every pointer and array as c_void_p, the ctypes pointee a
+    binding may spell out instead -- POINTEES, mc_xc_geom, mc_xc_line -- or None)."""
+    from torch_motion_correction_amd import _lib
+
+    pointees = {**POINTEES, "mc_xc_geom": _lib.XcGeom, "mc_xc_line": _lib.XcLine}
+    out = []
+    for param in header_parameters(name, header):
+        words = re.sub(r"\bconst\b", " ", re.split(r"[*\[]", param)[0]).split()  # `T` of `T* x`, `T x` otherwise
+        base = " ".join(words if "*" in param else words[:-1])
+        if "*" in param or "[" in param:
+            out.append((ctypes.c_void_p, pointees.get(base)))
+        elif base in SCALARS:
+            out.append((SCALARS[base], None))
+        else:
+            raise ValueError(f"{name}: no ctypes twin for the parameter {param!r}")
+    return out
+
+
+def header_signature(name, header=None):
+    """The ctypes argument types of the entry point `name` as the header declares it, for comparison with
+    _lib.SIGNATURES[name]: a scalar is its ctypes twin (SCALARS), a pointer or an array c_void_p.  ValueError for a
+    scalar of any other type: nothing falls back to int."""
+    return [ctype for ctype, _ in _declared(name, header)]
+
+
+def binding_disagreement(name, bound, header=None):
+    """None where the ctypes list `bound` can stand for the header's declaration of `name`, else what is wrong.  A
+    scalar is bound as itself; a pointer as c_void_p or, where the header names a pointee the binding may spell out,
+    as the POINTER to it."""
+    declared = _declared(name, header)
+    if len(declared) != len(bound):
+        return f"the header has {len(declared)} parameters, the binding {len(bound)}"
+    for i, ((ctype, pointee), b) in enumerate(zip(declared, bound)):
+        if b is not ctype and (pointee is None or b is not ctypes.POINTER(pointee)):
+            what = ctype.__name__ if pointee is None else f"a pointer to {pointee.__name__}"
+            return f"parameter {i}: the header says {what}, the binding {b.__name__}"
+    return None
+
+
+def assert_entry_point(name, want=None, source=None, header=None, signatures=None):
+    """`name` is declared in include/mcorr.h, bound in _lib.SIGNATURES, exported by the loaded library, and bound as
+    declared, parameter by parameter.  `want`: the literal ctypes list the binding must equal.  `source`: the
+    (file, stem, flags) entry _build.SOURCES must hold.  `header`, `signatures`: a header's text and a table to check
+    instead of the committed ones (nothing is looked up in the library then)."""
+    from torch_motion_correction_amd import _build, _lib
+
+    assert name in declared_entry_points(header), f"{name} is not declared in the header"
+    table = _lib.SIGNATURES if signatures is None else signatures
+    assert name in table, f"{name} is not bound"
+    if header is None and signatures is None:
+        assert getattr(_lib.load(), name) is not None
+    wrong = binding_disagreement(name, table[name], header)
+    assert wrong is None, f"{name}: {wrong}"
+    if want is not None:
+        assert table[name] == want, f"{name}: bound as {table[name]}"
+    if source is not None:
+        assert source in _build.SOURCES and os.path.exists(os.path.join(_build.CSRC, source[0])), source
+
+
+# ------------------------------------------------------------------ host programs, run as child processes
+
+SANITIZE = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+PLAIN = ["-O1", "-std=c++17"]
+
+
+def run_host_program(source, tmp_path, *args, sanitize=True):
+    """Builds tests/`source` (or `source` as it is where it is an absolute path) into `tmp_path` with clang++ -- the
+    ROCm one, else the one on PATH, else the test is skipped -- against csrc/, under the address and
+    undefined-behaviour sanitizers unless `sanitize` is False, and runs it with `args` as a child process: it must
+    return 0, end its output with OK and print no FAIL.  -> the CompletedProcess.  Nothing sanitized is loaded into
+    this process."""
+    cxx = "/opt/rocm/lib/llvm/bin/clang++"
+    if not os.path.exists(cxx):
+        cxx = shutil.which("clang++")
+    if not cxx:
+        pytest.skip("no clang++ on this machine")
+    exe = os.path.join(str(tmp_path), os.path.splitext(os.path.basename(source))[0])
+    subprocess.run([cxx, *(SANITIZE if sanitize else PLAIN), "-I", CSRC, os.path.join(ROOT, "tests", source),
+                    "-o", exe, *([] if sanitize else ["-lm"])], check=True)
+    res = subprocess.run([exe, *(str(a) for a in args)], capture_output=True, text=True)
+    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
+    assert "FAIL" not in res.stdout, res.stdout[-2000:]
+    return res
 
 
 # ------------------------------------------------------------------ NaN-filled and NaN-guarded buffers

@@ -5,14 +5,13 @@ hand-worked answers on 4 x 4 cases."""
 
 import ctypes
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import calibration_reference as cr
+from kernel_harness import assert_entry_point
 import torch_motion_correction_amd as mc
 from torch_motion_correction_amd import _lib, calibration
 
@@ -32,15 +31,8 @@ def test_names_exist():
 
 
 def test_header_and_signatures_agree_on_the_new_entry_point():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "mcorr.h")).read()
-    declared = set(re.findall(r"^int\s+(mc_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.SIGNATURES)
-    name = "mc_raw_pixel_sums"
-    assert name in declared and getattr(_lib.load(), name) is not None
-    args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
     vp, i32 = ctypes.c_void_p, ctypes.c_int
-    assert _lib.SIGNATURES[name] == [vp if "*" in a else i32 for a in args] == [vp, i32, i32, i32, i32, vp, vp, vp]
+    assert_entry_point("mc_raw_pixel_sums", [vp, i32, i32, i32, i32, vp, vp, vp])
 
 
 def test_entry_point_validates_on_the_host():

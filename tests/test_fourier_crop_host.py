@@ -4,13 +4,12 @@ and the float64 identities of the definition, which pin the expected-value helpe
 
 import ctypes
 import inspect
-import os
-import re
 
 import pytest
 import torch
 
 from crop_reference import band_limited, crop64 as crop_ref  # noqa: F401  (tests/test_fourier_crop.py imports them here)
+from kernel_harness import assert_entry_point
 from torch_motion_correction_amd import _lib
 
 
@@ -140,14 +139,8 @@ def test_unsupported_even_sizes_name_the_supported_ones(shape):
 
 
 def test_entry_point_is_declared_bound_and_exported():
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include",
-                               "mcorr.h")).read()
-    declared = set(re.findall(r"^int\s+(mc_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.SIGNATURES)
-    assert "mc_full_cols_crop" in declared
-    assert getattr(_lib.load(), "mc_full_cols_crop") is not None
     vp, i32 = ctypes.c_void_p, ctypes.c_int
-    assert _lib.SIGNATURES["mc_full_cols_crop"] == [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    assert_entry_point("mc_full_cols_crop", [vp, vp, vp, i32, i32, i32, i32, i32, vp])
 
 
 def _p(i):

@@ -6,20 +6,16 @@ sanitizers (tests/host_raw_group.cpp, a stand-alone program started as a child p
 
 import ctypes
 import inspect
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import group_reference as gr
+from kernel_harness import assert_entry_point, run_host_program
 import torch_motion_correction_amd as mc
 from torch_motion_correction_amd import _lib, api
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_names_and_parameter_lists():
@@ -40,21 +36,12 @@ def test_names_and_parameter_lists():
 
 
 def test_header_and_signatures_agree_on_the_entry_point():
-    header = open(os.path.join(ROOT, "include", "mcorr.h")).read()
-    declared = set(re.findall(r"^int\s+(mc_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.SIGNATURES)
-    name = "mc_raw_group_frames"
-    assert name in declared and getattr(_lib.load(), name) is not None
-    args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
     vp, i32 = ctypes.c_void_p, ctypes.c_int
-    assert _lib.SIGNATURES[name] == [vp if "*" in a else i32 for a in args] == [vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    assert_entry_point("mc_raw_group_frames", [vp, i32, i32, i32, i32, i32, vp, vp, vp])
 
 
 def test_the_object_is_in_the_build():
-    from torch_motion_correction_amd import _build
-
-    assert ("raw_group.hip", "raw_group", []) in _build.SOURCES
-    assert os.path.exists(os.path.join(_build.CSRC, "raw_group.hip"))
+    assert_entry_point("mc_raw_group_frames", source=("raw_group.hip", "raw_group", []))
 
 
 def test_entry_point_validates_on_the_host():
@@ -168,15 +155,5 @@ def test_kernel_body_on_the_host_under_sanitizers(tmp_path):
     workgroup in turn on exactly-sized heap buffers, vector and element path, u8 and i16, the shapes and groups of
     tests/test_frame_groups.py, the int16 edge and the overflow flag, against a naive loop.  Nothing sanitized is
     loaded into this process.  Needs clang++ (ext_vector_type, __builtin_nontemporal_*); the ROCm one is used."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
-    exe = tmp_path / "host_raw_group"
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_raw_group.cpp"), "-o", str(exe)], check=True)
-    res = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
-    assert res.stdout.count(" path: ok") == 92 and "FAIL" not in res.stdout
+    res = run_host_program("host_raw_group.cpp", tmp_path)
+    assert res.stdout.count(" path: ok") == 92

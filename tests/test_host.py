@@ -14,6 +14,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import oracle
+from kernel_harness import declared_entry_points, run_host_program
 from oracle import thirdparty_semantics as tp
 from torch_motion_correction_amd import _lib, lattice, multi_gpu, plan, spline
 
@@ -204,8 +205,7 @@ def test_axis_taps_bad_kind():
 
 
 def test_library_exports_every_declared_symbol():
-    header = open(os.path.join(ROOT, "include", "mcorr.h")).read()
-    declared = set(re.findall(r"^int\s+(mc_\w+)\s*\(", header, flags=re.M))
+    declared = declared_entry_points()
     assert len(declared) >= 20
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
     lib = _lib.load()
@@ -895,20 +895,7 @@ def test_wave_fft_index_algebra_on_the_host(tmp_path, src):
     pruned butterflies and in-lane / lane-permute real-FFT unpack of both wave transforms
     (2048- and 512-point rows, 1024-point columns) are executed lane by lane on the CPU and compared with a
     double-precision DFT.  Needs clang++ (ext_vector_type); the ROCm one is used."""
-    import shutil
-    import subprocess
-
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "a.out"
-    subprocess.run([cxx, "-O1", "-std=c++17", "-I", os.path.join(root, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(root, "tests", src), "-o", str(exe), "-lm"], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    assert out.strip().endswith("OK"), out
+    run_host_program(src, tmp_path, sanitize=False)
 
 
 def test_every_name_the_reference_exports_is_exported_here():

@@ -1,5 +1,6 @@
-"""tests/kernel_harness.py on the CPU: what "this entry point ran", "nothing was written outside the buffer" and "the
-same inputs as before" mean, pinned once for every kernel test that imports them."""
+"""tests/kernel_harness.py on the CPU: what "this entry point ran", "the header and the ctypes table agree", "the host
+program passed under the sanitizers", "nothing was written outside the buffer" and "the same inputs as before" mean,
+pinned once for every test that imports them."""
 
 import pytest
 import torch
@@ -119,19 +120,110 @@ def test_byte_buffer_typed_views():
             kh.assert_byte_guards(out, whole, "typed")
 
 
+# ------------------------------------------------------------------ the header against the ctypes table
+
+SYNTHETIC = """/* int mc_in_a_comment(int a); */
+// int mc_in_a_line_comment(int a);
+int mc_other(int a);  // one int
+int mc_nothing(void);
+int mc_made_up(const unsigned char* data, long long n,
+    int h, unsigned seed, float x /* host */, int64_t m, double d,
+    long long* out /* host */, const int64_t* off, const double m4[4], const mc_xc_geom* geom, void* stream);
+int mc_odd(int a, size_t n);
+"""
+
+
 def test_header_signature():
-    import ctypes
+    import ctypes as C
 
     from torch_motion_correction_amd import _lib
 
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    text = "int mc_other(int a);\nint mc_made_up(const unsigned char* data, long long n,\n    int h, void* stream);\n"
-    assert kh.header_signature("mc_made_up", text) == [vp, i64, i32, vp]
-    assert kh.header_signature("mc_other", text) == [i32]
-    with pytest.raises(AttributeError):
-        kh.header_signature("mc_absent", text)
+    assert kh.declared_entry_points(SYNTHETIC) == {"mc_other", "mc_nothing", "mc_made_up", "mc_odd"}
+    assert kh.header_parameters("mc_made_up", SYNTHETIC) == [
+        "const unsigned char* data", "long long n", "int h", "unsigned seed", "float x", "int64_t m", "double d",
+        "long long* out", "const int64_t* off", "const double m4[4]", "const mc_xc_geom* geom", "void* stream"]
+    vp = C.c_void_p
+    assert kh.header_signature("mc_made_up", SYNTHETIC) == [
+        vp, C.c_int64, C.c_int, C.c_uint, C.c_float, C.c_int64, C.c_double, vp, vp, vp, vp, vp]
+    spelt_out = [vp, C.c_int64, C.c_int, C.c_uint, C.c_float, C.c_int64, C.c_double, C.POINTER(C.c_int64),
+                 C.POINTER(C.c_int64), C.POINTER(C.c_double), _lib.GP, vp]
+    assert kh.binding_disagreement("mc_made_up", spelt_out, SYNTHETIC) is None
+    assert "parameter 0" in kh.binding_disagreement("mc_made_up", [C.POINTER(C.c_int64)] + spelt_out[1:], SYNTHETIC)
+    assert kh.header_signature("mc_other", SYNTHETIC) == [C.c_int] and kh.header_signature("mc_nothing", SYNTHETIC) == []
+    for absent in ("mc_absent", "mc_in_a_comment", "mc_in_a_line_comment"):
+        with pytest.raises(KeyError):
+            kh.header_signature(absent, SYNTHETIC)
+    with pytest.raises(ValueError, match="size_t n"):
+        kh.header_signature("mc_odd", SYNTHETIC)  # an unknown base type is no int
+
+
+def test_every_declared_entry_point_is_bound_as_declared():
+    from torch_motion_correction_amd import _lib
+
+    declared = kh.declared_entry_points()
+    assert declared == set(_lib.SIGNATURES) and len(declared) >= 89
+    for name in sorted(declared):
+        kh.assert_entry_point(name)
     for name in ("mc_eer_render", "mc_tiff_decode", "mc_tiff_encode", "mc_tiff_pack", "mc_mrc_decode", "mc_raw_orient"):
-        assert kh.header_signature(name) == _lib.SIGNATURES[name]  # the committed header
+        assert kh.header_signature(name) == _lib.SIGNATURES[name]  # these bind every pointer as void*
+    swapped = [_lib.GP if a is _lib.LP else a for a in _lib.SIGNATURES["mc_xcg_cols_forward"]]
+    assert "parameter 3: the header says a pointer to XcLine" in kh.binding_disagreement("mc_xcg_cols_forward", swapped)
+    with pytest.raises(AssertionError, match="not declared"):
+        kh.assert_entry_point("mc_absent")
+
+
+def test_assert_entry_point_refuses_a_binding_that_disagrees():
+    import ctypes as C
+
+    vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
+    header = "int mc_t(const void* src, int n, float x, long long* out /* host */, void* stream);\n"
+    good = [vp, i32, f32, C.POINTER(i64), vp]
+    kh.assert_entry_point("mc_t", good, header=header, signatures={"mc_t": good})
+    kh.assert_entry_point("mc_t", header=header, signatures={"mc_t": [vp, i32, f32, vp, vp]})  # a pointer as void*
+    for bad, why in (([vp, i32, f32, C.POINTER(i64)], "5 parameters, the binding 4"),
+                     ([vp, i32, i32, C.POINTER(i64), vp], "parameter 2: the header says c_float, the binding c_int"),
+                     ([vp, i32, f32, C.POINTER(C.c_double), vp], "parameter 3: the header says a pointer to c_long"),
+                     ([vp, i32, f32, i64, vp], "parameter 3"),  # a scalar for a pointer
+                     ([vp, vp, f32, vp, vp], "parameter 1")):   # a pointer for a scalar
+        with pytest.raises(AssertionError, match=why):
+            kh.assert_entry_point("mc_t", header=header, signatures={"mc_t": bad})
+    with pytest.raises(AssertionError, match="not bound"):
+        kh.assert_entry_point("mc_t", header=header, signatures={})
+    with pytest.raises(AssertionError, match="bound as"):
+        kh.assert_entry_point("mc_t", [vp, i32, f32, vp, vp], header=header, signatures={"mc_t": good})
+    with pytest.raises(AssertionError):
+        kh.assert_entry_point("mc_abi_version", source=("no_such.hip", "no_such", []))
+
+
+# ------------------------------------------------------------------ host programs
+
+PROGRAM = """#include <cstdio>
+int main(int argc, char** argv) {
+  int* a = new int[4]();
+  volatile int at = %d;
+  int v = a[at];
+  %s
+  std::printf("%%d arguments OK\\n", argc - 1 + v);
+  delete[] a;
+  return 0;
+}
+"""
+
+
+def test_run_host_program(tmp_path):
+    def source(name, at, line=""):
+        (tmp_path / name).write_text(PROGRAM % (at, line))
+        return str(tmp_path / name)
+
+    for sanitize in (True, False):
+        res = kh.run_host_program(source("fine.cpp", 3), tmp_path, "a", 2, sanitize=sanitize)
+        assert res.returncode == 0 and res.stdout == "2 arguments OK\n"
+    with pytest.raises(AssertionError):
+        kh.run_host_program(source("fails.cpp", 3, 'std::printf("case 1: FAIL\\n");'), tmp_path)
+    with pytest.raises(AssertionError):
+        kh.run_host_program(source("no_ok.cpp", 3, 'std::printf("OK\\n"); return 3;'), tmp_path)
+    with pytest.raises(AssertionError, match="heap-buffer-overflow"):
+        kh.run_host_program(source("past.cpp", 4), tmp_path)  # one int past new int[4]: the flags are in effect
 
 
 def test_nan_and_nan_empty(nan_empty):

@@ -5,8 +5,6 @@ check their arguments before any device is touched; the header and the ctypes ta
 
 import ctypes
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ import torch
 
 import global_refine_reference as gr
 import local_refine_reference as lr
+from kernel_harness import assert_entry_point, header_parameters
 import torch_motion_correction_amd as mc
 from torch_motion_correction_amd import _lib, engine
 
@@ -191,18 +190,11 @@ NEW = {"mc_xc_aligned_refs_patches": 15, "mc_xc_refine_update_patches": 13}
 
 
 def test_header_and_signatures_agree_on_the_new_entry_points():
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include",
-                               "mcorr.h")).read()
-    declared = set(re.findall(r"^int\s+(mc_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.SIGNATURES)
-    lib = _lib.load()
     vp, i32 = ctypes.c_void_p, ctypes.c_int
     for name, nargs in NEW.items():
-        assert name in declared and getattr(lib, name) is not None
-        args = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1).split(",")
+        args = header_parameters(name)
         assert len(args) == nargs == len(_lib.SIGNATURES[name])
-        want = [vp if "*" in a else i32 for a in args]
-        assert _lib.SIGNATURES[name] == want, name
+        assert_entry_point(name, [vp if "*" in a else i32 for a in args])
 
 
 def _p(i):

@@ -10,17 +10,15 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import magnification_reference as mr
+from kernel_harness import assert_entry_point, header_parameters, run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -52,20 +50,16 @@ def test_names_parameters_and_defaults(mc):
 
 
 def test_sources_signatures_and_header_agree():
-    from torch_motion_correction_amd import _build, _lib
+    from torch_motion_correction_amd import _build
 
-    assert ("affine_resample.hip", "affine_resample", []) in _build.SOURCES
-    for name in ("affine_resample.hip", "affine_resample.h"):
-        assert os.path.exists(os.path.join(_build.CSRC, name))
     vp, i32 = ctypes.c_void_p, ctypes.c_int
-    assert _lib.SIGNATURES["mc_affine_resample"] == [vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_double),
-                                                     ctypes.c_float, vp, vp]
-    with open(os.path.join(ROOT, "include", "mcorr.h")) as fh:
-        header = fh.read()
-    args = re.search(r"^int\s+mc_affine_resample\s*\(([^;]*)\);", header, flags=re.M | re.S).group(1)
-    kinds = ["*" if "*" in a.replace("/* host */", "") else a.split()[0] for a in args.split(",")]
+    assert_entry_point("mc_affine_resample",
+                       [vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_double), ctypes.c_float, vp, vp],
+                       source=("affine_resample.hip", "affine_resample", []))
+    assert os.path.exists(os.path.join(_build.CSRC, "affine_resample.h"))
+    args = header_parameters("mc_affine_resample")
+    kinds = ["*" if "*" in a else a.split()[0] for a in args]
     assert kinds == ["*", "int", "int", "int", "int", "const", "float", "*", "*"] and "const double m[4]" in args
-    assert _lib.load().mc_affine_resample is not None
     rule = open(os.path.join(_build.CSRC, "affine_resample.h")).read()
     assert "hip/hip_runtime" not in rule and "THE RULE" in rule and "ACCUMULATION" in rule
     # the header's window bound, restated: floor(1.25 * (TILE - 1)) + 1 + 4 rows of STRIDE floats, in 64 KiB of LDS
@@ -292,11 +286,6 @@ def test_bodies_on_the_host_under_sanitizers(tmp_path):
     quarter turns and reflections among them: the largest windows).  Frame and window are allocated to their exact
     sizes: a stray read is a sanitizer report.  The output is compared with the restatement's within its bound, the
     filled pixels bit for bit.  Nothing sanitized is loaded into this process."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
     records, fills = [], (0.0, -3.5)
     scales = ((0.9, 0.9, 0.0), (1.1, 1.1, 0.0), (0.9, 1.1, 30.0), (1.1, 0.9, 117.0), (1.0, 1.0, 0.0), (1.1, 1.1, 45.0))
     for h, w in ((4, 4), (5, 7), (33, 65)):
@@ -316,10 +305,5 @@ def test_bodies_on_the_host_under_sanitizers(tmp_path):
             records.append(_record(frame, np.array(m), 1.5))
     cases = tmp_path / "cases.bin"
     cases.write_bytes(b"".join(records))
-    exe = tmp_path / "host_affine_resample"
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_affine_resample.cpp"), "-o", str(exe)], check=True)
-    res = subprocess.run([str(exe), str(cases)], capture_output=True, text=True)
-    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
-    assert f"{len(records)} cases, 0 failures" in res.stdout and "FAIL" not in res.stdout
+    res = run_host_program("host_affine_resample.cpp", tmp_path, cases)
+    assert f"{len(records)} cases, 0 failures" in res.stdout

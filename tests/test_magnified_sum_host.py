@@ -8,9 +8,7 @@ window and per-pixel bodies run on the CPU under the address and undefined-behav
 import ctypes
 import inspect
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,9 +17,8 @@ import torch
 import magnification_reference as mr
 import magnified_sum_reference as ms
 import rigid_reference as rr
-from kernel_harness import header_signature
+from kernel_harness import assert_entry_point, run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 
 
@@ -61,19 +58,14 @@ def test_sources_signatures_and_header_agree():
     from torch_motion_correction_amd import _build, _lib
 
     entry = ("affine_warp_sum.hip", "affine_warp_sum", [])
-    assert entry in _build.SOURCES and _build.SOURCES[-1] != entry
+    assert _build.SOURCES[-1] != entry
     stems = [s[1] for s in _build.SOURCES]
     assert stems.index("affine_warp_sum") < stems.index("tiff_encode") < stems.index("tiff_decode") == len(stems) - 1
-    for name in ("affine_warp_sum.hip", "affine_warp_sum.h", "affine_resample.h"):
+    for name in ("affine_warp_sum.h", "affine_resample.h"):
         assert os.path.exists(os.path.join(_build.CSRC, name))
-    vp, i32 = ctypes.c_void_p, ctypes.c_int
-    want = [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
-    assert header_signature("mc_affine_warp_sum") == want
-    sig = _lib.SIGNATURES["mc_affine_warp_sum"]
-    assert [vp if a is ctypes.POINTER(ctypes.c_double) else a for a in sig] == want
-    assert sig[7] is ctypes.POINTER(ctypes.c_double)  # the matrix: four host doubles
-    lib = _lib.load()
-    assert lib.mc_affine_warp_sum is not None and lib.mc_abi_version() == 1
+    vp, i32, matrix = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double)  # the matrix: four host doubles
+    assert_entry_point("mc_affine_warp_sum", [vp, i32, vp, vp, i32, i32, i32, matrix, vp, vp, vp, vp], source=entry)
+    assert _lib.load().mc_abi_version() == 1
     rule = open(os.path.join(_build.CSRC, "affine_warp_sum.h")).read()
     assert '#include "affine_resample.h"' in rule and "hip/hip_runtime" not in rule
     assert "THE RULE" in rule and "THE SUM" in rule and "THE WINDOW" in rule
@@ -299,22 +291,12 @@ def test_bodies_on_the_host_under_sanitizers(tmp_path):
     masks are compared with the restatement bit for bit, the sums within the derived bound; identity M with
     whole-pixel shifts bit for bit with the fp32 sequential sum; a movie shifted wholly outside sums to exact zeros
     with every (tile, frame) skipped.  Nothing sanitized is loaded into this process."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
     cases = _cases()
     blob = b"".join(struct.pack("<4i4d", *stack.shape, 0, *np.asarray(m, dtype=np.float64).ravel())
                     + shifts.astype("<f4").tobytes() + stack.astype("<f4").tobytes() for stack, m, shifts in cases)
     (tmp_path / "cases.bin").write_bytes(blob)
-    exe = tmp_path / "host_affine_warp_sum"
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_affine_warp_sum.cpp"), "-o", str(exe)], check=True)
-    res = subprocess.run([str(exe), str(tmp_path / "cases.bin"), str(tmp_path / "results.bin")], capture_output=True, text=True)
-    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
-    assert f"{len(cases)} cases, 0 failures" in res.stdout and "FAIL" not in res.stdout
+    res = run_host_program("host_affine_warp_sum.cpp", tmp_path, tmp_path / "cases.bin", tmp_path / "results.bin")
+    assert f"{len(cases)} cases, 0 failures" in res.stdout
     raw = (tmp_path / "results.bin").read_bytes()
     pos = 0
     for i, (stack, m, shifts) in enumerate(cases):

@@ -7,10 +7,7 @@ and undefined-behaviour sanitizers (tests/host_mrc_encode.cpp, a stand-alone pro
 import ctypes
 import inspect
 import os
-import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,9 +15,7 @@ import torch
 
 import mrc_encode_reference as er
 import mrc_reference as mr
-from kernel_harness import header_signature
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kernel_harness import assert_entry_point, run_host_program
 
 
 @pytest.fixture(scope="module")
@@ -63,13 +58,8 @@ def test_sources_signatures_and_header_agree():
     for name in ("mrc_encode.hip", "mrc_encode.h"):
         assert os.path.exists(os.path.join(_build.CSRC, name))
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    want = [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp]
-    assert header_signature("mc_mrc_encode") == want == _lib.SIGNATURES["mc_mrc_encode"]
-    lib = _lib.load()
-    assert lib.mc_mrc_encode is not None and lib.mc_abi_version() == 1
-    with open(os.path.join(ROOT, "include", "mcorr.h")) as fh:
-        declared = set(re.findall(r"^int\s+(mc_\w+)\s*\(", fh.read(), flags=re.M))
-    assert declared == set(_lib.SIGNATURES)
+    assert_entry_point("mc_mrc_encode", [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp])
+    assert _lib.load().mc_abi_version() == 1
     rule = open(os.path.join(_build.CSRC, "mrc_encode.h")).read()
     assert "NOT been confirmed" in rule  # the 4-bit layout rests on the format descriptions; the header says so
     assert "hip/hip_runtime" not in rule and "THE SCRATCH RULE" in rule
@@ -259,11 +249,6 @@ def test_bodies_on_the_host_under_sanitizers(tmp_path):
     entry point refuses another), with and without flip_rows, with samples outside the mode's range.  The movie's and
     the payload's allocations are exact and their leads poisoned: a stray byte is a sanitizer report.  Payload and
     statistics are compared with the restatement's.  Nothing sanitized is loaded into this process."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
     records, seen = [], set()
     for dtype, mode in er.KINDS:
         elem = int(dtype[1])
@@ -282,10 +267,5 @@ def test_bodies_on_the_host_under_sanitizers(tmp_path):
         assert all((dtype, mode, "out", a) in seen for a in range(16))
     cases = tmp_path / "cases.bin"
     cases.write_bytes(b"".join(records))
-    exe = tmp_path / "host_mrc_encode"
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_mrc_encode.cpp"), "-o", str(exe)], check=True)
-    res = subprocess.run([str(exe), str(cases)], capture_output=True, text=True)
-    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
-    assert f"{len(records)} cases, 0 failures" in res.stdout and "FAIL" not in res.stdout
+    res = run_host_program("host_mrc_encode.cpp", tmp_path, cases)
+    assert f"{len(records)} cases, 0 failures" in res.stdout

@@ -6,18 +6,15 @@ sanitizers (tests/host_mrc.cpp, a stand-alone program started as a child process
 
 import ctypes
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import mrc_reference as mr
-from kernel_harness import header_signature
+from kernel_harness import assert_entry_point, run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = (0, 1, 2, 6, 12, 101)
 
 
@@ -57,7 +54,7 @@ def test_names_are_exported(mc):
 
 
 def test_sources_signatures_and_header_agree():
-    from torch_motion_correction_amd import _build, _lib
+    from torch_motion_correction_amd import _build
 
     assert ("mrc_decode.hip", "mrc_decode", []) in _build.SOURCES
     assert ("raw_orient.hip", "raw_orient", []) in _build.SOURCES
@@ -67,10 +64,8 @@ def test_sources_signatures_and_header_agree():
     for name in ("mrc_decode.hip", "raw_orient.hip", "mrc.h"):
         assert os.path.exists(os.path.join(_build.CSRC, name))
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    for name, want in (("mc_mrc_decode", [vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
-                       ("mc_raw_orient", [vp, i32, i32, i32, i32, i32, i32, vp, vp])):
-        assert header_signature(name) == want == _lib.SIGNATURES[name]
-        assert getattr(_lib.load(), name) is not None
+    assert_entry_point("mc_mrc_decode", [vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp])
+    assert_entry_point("mc_raw_orient", [vp, i32, i32, i32, i32, i32, i32, vp, vp])
     rule = open(os.path.join(_build.CSRC, "mrc.h")).read()
     assert "NOT been confirmed" in rule  # the 4-bit layout rests on the format descriptions; mrc.h says so
 
@@ -338,11 +333,6 @@ def test_bodies_on_the_host_under_sanitizers(tmp_path):
     misaligned to themselves), widths around one and several units, odd widths in mode 101 with a padding nibble of
     15, with and without flip_rows.  Input and output allocations are exact and their leads poisoned: a stray byte
     is a sanitizer report.  Nothing sanitized is loaded into this process."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
     records = []
     kinds = [(0, 0, 1), (0, 0, 0), (1, 0, 0), (1, 1, 0), (6, 0, 0), (12, 1, 0), (2, 0, 0), (2, 1, 0), (101, 0, 0)]
     for mode, swap, ub in kinds:
@@ -357,10 +347,5 @@ def test_bodies_on_the_host_under_sanitizers(tmp_path):
                 records.append(_record(mode, swap, ub, flip, shape, lead_in, lead_out, payload, want.tobytes()))
     cases = tmp_path / "cases.bin"
     cases.write_bytes(b"".join(records))
-    exe = tmp_path / "host_mrc"
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_mrc.cpp"), "-o", str(exe)], check=True)
-    res = subprocess.run([str(exe), str(cases)], capture_output=True, text=True)
-    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
-    assert f"{len(records)} cases, 0 failures" in res.stdout and "FAIL" not in res.stdout
+    res = run_host_program("host_mrc.cpp", tmp_path, cases)
+    assert f"{len(records)} cases, 0 failures" in res.stdout

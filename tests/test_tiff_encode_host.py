@@ -9,16 +9,14 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import tiff_reference as tr
-from kernel_harness import header_signature
+from kernel_harness import assert_entry_point, header_parameters, run_host_program
 from tiff_files import walk_ifds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -89,21 +87,15 @@ def test_names_parameter_lists_and_defaults(mc):
 
 
 def test_header_signatures_and_build_agree():
-    from torch_motion_correction_amd import _build, _lib
+    from torch_motion_correction_amd import _build
 
-    header = open(os.path.join(ROOT, "include", "mcorr.h")).read()
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    want = {"mc_tiff_encode": [vp, i32, i32, i32, i32, i32, vp, i64, i64, vp, vp],
-            "mc_tiff_pack": [vp, i64, vp, vp, i64, vp, i64, vp]}
-    for name, types in want.items():
-        assert header_signature(name) == types == _lib.SIGNATURES[name]
-        assert getattr(_lib.load(), name) is not None
-    assert re.search(r"^int\s+mc_tiff_encode_slot_bytes\s*\(long long strip_bytes, long long\* slot_bytes", header,
-                     flags=re.M)
-    assert _lib.SIGNATURES["mc_tiff_encode_slot_bytes"] == [i64, ctypes.POINTER(i64)]
-    assert ("tiff_encode.hip", "tiff_encode", []) in _build.SOURCES
-    for name in ("tiff_encode.hip", "tiff_lzw_encode.h"):
-        assert os.path.exists(os.path.join(_build.CSRC, name))
+    source = ("tiff_encode.hip", "tiff_encode", [])
+    assert_entry_point("mc_tiff_encode", [vp, i32, i32, i32, i32, i32, vp, i64, i64, vp, vp], source)
+    assert_entry_point("mc_tiff_pack", [vp, i64, vp, vp, i64, vp, i64, vp], source)
+    assert_entry_point("mc_tiff_encode_slot_bytes", [i64, ctypes.POINTER(i64)], source)
+    assert header_parameters("mc_tiff_encode_slot_bytes") == ["long long strip_bytes", "long long* slot_bytes"]
+    assert os.path.exists(os.path.join(_build.CSRC, "tiff_lzw_encode.h"))
 
 
 # ------------------------------------------------------------------ the size bound
@@ -163,11 +155,6 @@ def test_strip_loop_on_the_host_under_sanitizers(golden, tmp_path):
     -fsanitize=address,undefined into a program of its own and run as a child process on exactly-sized, poisoned
     buffers.  Its streams must equal tr.encode_strip's byte for byte, and tr.decode_strip must give the input back.
     Nothing sanitized is loaded into this process."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
     rng = np.random.default_rng(2)
     inputs = [b""] + [bytes([b]) for b in range(256)] + [bytes(n) for n in range(1, 1001)]
     inputs += [rng.poisson(1.0, n).astype(np.uint8).tobytes() for n in (63, 64, 65, 700, 7000)]
@@ -185,14 +172,9 @@ def test_strip_loop_on_the_host_under_sanitizers(golden, tmp_path):
         records.append(struct.pack("<2I", len(data), len(want)) + data + want)
     cases = tmp_path / "cases.bin"
     cases.write_bytes(b"".join(records))
-    exe = tmp_path / "host_tiff_lzw_encode"
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_tiff_lzw_encode.cpp"), "-o", str(exe)], check=True)
-    res = subprocess.run([str(exe), str(cases)], capture_output=True, text=True)
-    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
+    res = run_host_program("host_tiff_lzw_encode.cpp", tmp_path, cases)
     n_cases = int(re.search(r"(\d+) cases, 0 failures", res.stdout).group(1))
-    assert n_cases == 6 * len(records) + 1 and "FAIL" not in res.stdout
+    assert n_cases == 6 * len(records) + 1
 
 
 def test_libtiff_strips_compared_and_recorded(golden):

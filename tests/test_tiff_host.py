@@ -9,9 +9,7 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,7 +17,7 @@ import torch
 
 import tiff_files
 import tiff_reference as tr
-from kernel_harness import header_signature
+from kernel_harness import assert_entry_point, run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "tiff_lzw_libtiff.npz")
@@ -108,16 +106,10 @@ def test_names_parameter_lists_and_defaults(mc):
 def test_header_signatures_and_build_agree(mc):
     from torch_motion_correction_amd import _build, _lib
 
-    header = open(os.path.join(ROOT, "include", "mcorr.h")).read()
-    declared = set(re.findall(r"^int\s+(mc_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(_lib.SIGNATURES)
-    name = "mc_tiff_decode"
-    assert name in declared and getattr(_lib.load(), name) is not None
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    assert _lib.SIGNATURES[name] == header_signature(name) == [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp,
-                                                               vp, i64, vp]
+    assert_entry_point("mc_tiff_decode", [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp],
+                       source=("tiff_decode.hip", "tiff_decode", []))
     assert _build.SOURCES[-1] == ("tiff_decode.hip", "tiff_decode", [])
-    assert os.path.exists(os.path.join(_build.CSRC, "tiff_decode.hip"))
     assert os.path.exists(os.path.join(_build.CSRC, "tiff_lzw.h"))
     assert _lib.load().mc_abi_version() == 1
 
@@ -451,11 +443,6 @@ def test_strip_loop_on_the_host_under_sanitizers(golden, tmp_path):
     strip of the committed libtiff files, encoder-made strips of every option, the malformed strips of
     tests/test_tiff_decode.py, a short strip cut at every length, each strip also decoded into fewer bytes than it
     holds, garbage, the empty and every one-byte stream.  Nothing sanitized is loaded into this process."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        cxx = shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no clang++ on this machine")
     records = []
     for name in NAMES[:4]:
         strips, rps, _, pixels = fixture_strips(golden, name)
@@ -480,11 +467,6 @@ def test_strip_loop_on_the_host_under_sanitizers(golden, tmp_path):
         records.append(_record(0, s, len(noise), want))
     cases = tmp_path / "cases.bin"
     cases.write_bytes(b"".join(records))
-    exe = tmp_path / "host_tiff_lzw"
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "torch_motion_correction_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_tiff_lzw.cpp"), "-o", str(exe)], check=True)
-    res = subprocess.run([str(exe), str(cases)], capture_output=True, text=True)
-    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-4000:]
+    res = run_host_program("host_tiff_lzw.cpp", tmp_path, cases)
     n_cases = int(re.search(r"(\d+) cases, 0 failures", res.stdout).group(1))
-    assert n_cases > 5 * len(records) and "FAIL" not in res.stdout
+    assert n_cases > 5 * len(records)

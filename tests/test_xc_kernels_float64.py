@@ -501,14 +501,11 @@ def test_patch_jobs_two_ordinary_passes(dev, calls, switches, p):
 def _arg(name, param):
     """Position of the argument `param` of the entry point `name`, read from its declaration in include/mcorr.h (and
     the declaration has as many arguments as _lib.SIGNATURES[name])."""
-    import os
     import re
 
     from torch_motion_correction_amd import _lib
 
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mcorr.h")) as fh:
-        decl = re.search(r"^int\s+" + name + r"\s*\(([^;]*)\);", fh.read(), flags=re.M | re.S).group(1)
-    names = [re.search(r"(\w+)\s*$", a).group(1) for a in decl.split(",")]
+    names = [re.search(r"(\w+)\s*$", a).group(1) for a in kernel_harness.header_parameters(name)]
     assert len(names) == len(_lib.SIGNATURES[name]) and names.count(param) == 1, (name, names)
     return names.index(param)
 
