@@ -526,6 +526,18 @@ int mc_full_cols_shift_sum_cm(const void* ST, const float* shifts, int nframes, 
  *                      row sizes (H = 512 .. 4096 or 8184; W = 128 .. 8192 or 11520), else MC_ERR_UNSUPPORTED. */
 int mc_full_cols_crop(const void* S, void* S2, const void* tw_col, int njobs, int H, int W, int pitch, int pitch2,
                       void* stream);
+/* Fourier cropping to a given size (H2, W2), both even, H2 < H, W2 <= W ("-FtBin 1.5", 3, 4/3; a K3 counting-mode
+ * movie by 2): y = irfft2(G, (H2, W2)) of G = the rows -H2/2 <= ky < H2/2 (signed; the new Nyquist row from the
+ * negative side) and columns 0 <= kx <= W2/2 of F, scaled by 1 / (H2 W2): the frame's sum is kept.
+ *   mc_full_cols_crop_to  per job: columns kx <= W2/2 of S (H x pitch; the others are never read): fft along y, the
+ *                      kept rows * 1 / (H2 W2), ifft along y at H2 points -> S2 (H2 x pitch2, pitch2 =
+ *                      mc_full_spectrum_pitch(W2); its padding columns hold nothing defined).  Between
+ *                      mc_full_rows_forward(_raw) at (H, W) and mc_full_rows_inverse at (H2, W2), which takes these
+ *                      output sizes besides those above.  tw_col: the H-point table, tw_col2: the H2-point table.
+ *                      (H, H2) is one of (512, 384), (4096, 3072), (4092, 2046), (8184, 5456), (8184, 2728); W a
+ *                      row size above; W2 one too, or 2880, 3072, 3840 or 7680; else MC_ERR_UNSUPPORTED. */
+int mc_full_cols_crop_to(const void* S, void* S2, const void* tw_col, const void* tw_col2, int njobs, int H, int W,
+                         int H2, int W2, int pitch, int pitch2, void* stream);
 
 /* correct_motion_fast (correct_motion.py:430-498): K3 variant multiplying spectrum
  * idx[p] by exp(-2*pi*i*(fy*sy+fx*sx)), shifts[p]=(sy,sx) px, then inverse columns. */

@@ -26,6 +26,7 @@ SOURCES = [("xcg_rows_inv.hip", "xcg_rows_inv", []), ("xcg_cols_inv.hip", "xcg_c
            ("xc_rows_fwd_wg.hip", "xc_rows_fwd_wg", []), ("xc_rows_fwd_wave.hip", "xc_rows_fwd_wave", []),
            # row-major full spectra over full_common.h: per-frame transforms / fused sums and the raw row pass
            ("full_fft.hip", "full_fft", []), ("full_sums.hip", "full_sums", []), ("fourier_crop.hip", "fourier_crop", []),
+           ("fourier_crop_to.hip", "fourier_crop_to", []),
            ("xc_cols.hip", "xc_cols", []), ("xc_search.hip", "xc_search", []),
            # warp_*.hip and field_tables.hip (one object per kernel family; the field warp is three objects over
            # warp_field_common.h: production kernels, the two fallback kernels, lattice tables and splines): the SLP

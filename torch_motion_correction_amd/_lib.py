@@ -85,6 +85,7 @@ SIGNATURES = {
     "mc_full_cols_shift_sum_cm": [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, i32, i32, f32,
                                   vp],
     "mc_full_cols_crop": [vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "mc_full_cols_crop_to": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "mc_fourier_shift_cols_inverse": [vp, vp, vp, vp, vp, f32, i32, GP, vp],
     "mc_xc_rows_inverse_store": [vp, vp, vp, i64, vp, i32, GP, vp],
     "mc_xcg_rows_forward": [vp, vp, i64, vp, vp, vp, vp, vp, LP, i32, GP, vp],

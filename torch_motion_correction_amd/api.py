@@ -18,6 +18,7 @@ peaks).  Q4-Q9 are plain semantics and are always reproduced.
 from __future__ import annotations
 
 import math
+import operator
 
 import torch
 
@@ -1062,6 +1063,108 @@ def motion_correct_raw_binned(movie, gain, pixel_spacing, binning=2, patch_sidel
         if want_counts:
             out.append(_hot_counts_out(counts, movie.shape[0], dev))  # (moved to out_dev with the rest)
         return tuple(x.to(out_dev) for x in out)
+
+
+# ------------------------------------------------------------------ Fourier cropping to a given size
+
+
+def _check_crop_to_args(shape_in, shape):
+    """Even frames and an even, positive (h2, w2) no larger than them (ValueError), a pair of shapes the cropping
+    passes take (NotImplementedError naming them) -> (h2, w2) as ints -- all before any device is touched."""
+    h, w = int(shape_in[-2]), int(shape_in[-1])
+    try:
+        h2, w2 = (operator.index(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"shape must be two integers (h2, w2), got {shape!r}") from None
+    if h % 2 or w % 2 or h < 2 or w < 2:
+        raise ValueError(f"Fourier cropping needs frames with an even number of rows and columns, got {h} x {w}")
+    if h2 < 2 or w2 < 2:
+        raise ValueError(f"shape must be positive, got {h2} x {w2}")
+    if h2 % 2 or w2 % 2:
+        raise ValueError(f"Fourier cropping needs an even number of rows and columns in shape, got {h2} x {w2}")
+    if h2 > h or w2 > w:
+        raise ValueError(f"shape {h2} x {w2} exceeds the frames, {h} x {w}: Fourier cropping only makes frames smaller")
+    if not engine.fourier_crop_to_supported(h, w, h2, w2):
+        raise NotImplementedError(f"frames of {h} x {w} to {h2} x {w2}: the Fourier crop needs "
+                                  f"{engine.FOURIER_CROP_TO_SIZES}")
+    return h2, w2
+
+
+def fourier_crop_to(image, shape, device=None):
+    """Fourier cropping of a frame (h, w) or a stack (t, h, w), fp32 or fp16, to ``shape = (h2, w2)``, both even, no
+    larger than the frame: per frame ``irfft2(cat(F[:h2/2, :w2/2+1], F[h-h2/2:, :w2/2+1]), s=(h2, w2))`` of ``F =
+    rfft2(frame)`` -- the signed row frequencies -h2/2 <= ky < h2/2 (the new Nyquist row from the negative side) and
+    columns kx <= w2/2, the inverse's 1 / (h2 w2) the only scale: a frame's sum is kept.  MotionCor's ``-FtBin 1.5``
+    or 3 of a super-resolution movie, 2 of a K3 counting-mode movie, 4/3 of a 4096-row sum; ``fourier_crop_shape``
+    gives the shape for a factor, ``fourier_crop_pixel_spacing`` the pixel spacing of the result.  At (h/2, w/2) of a
+    frame ``fourier_crop`` takes, this is ``fourier_crop``, bit for bit.  Returns fp32 on ``image``'s device rule.
+    Odd or non-positive sizes and a shape beyond the frame raise ValueError; pairs outside heights 512 -> 384, 4096
+    -> 3072, 4092 -> 2046, 8184 -> 5456 / 2728 and widths 64 .. 8192 (powers of two), 5760, 11520 -> any of those or
+    2880, 3072, 3840, 7680 raise NotImplementedError (no chirp-z route, no CPU fallback)."""
+    if not isinstance(image, torch.Tensor) or image.dim() not in (2, 3):
+        raise ValueError(f"image must be (h, w) or (t, h, w), got {tuple(getattr(image, 'shape', ()))}")
+    out_shape = _check_crop_to_args(image.shape, shape)
+    with gpu_entry(image, device) as (out_dev, dev):
+        img = _stage(image, dev)
+        out = engine.fourier_crop_to(img if img.dim() == 3 else img[None], out_shape)
+        return (out if img.dim() == 3 else out[0]).to(out_dev)
+
+
+def fourier_crop_to_raw(movie, gain, shape, mean_zero=True, hot_pixel_threshold=None, return_hot_counts=False,
+                        device=None):
+    """``fourier_crop_to(condition_movie(movie, gain, mean_zero, hot_pixel_threshold), shape)`` for a RAW uint8 /
+    int16 movie without the full-size fp32 movie, by ``fourier_crop_raw``'s rules: the row transform reads the raw
+    bytes, the hot pixels enter the spectra as sparse corrections, and without hot pixels the result is bit for bit
+    that of the composition.  Returns the (t, h2, w2) fp32 movie, with ``return_hot_counts`` also the (t,) int32 hot
+    pixels per frame.  fp16 / fp32 movies and a hot-pixel list overflow take exactly condition_movie followed by
+    fourier_crop_to.  There is no one-call binned pipeline at these factors: align the result with
+    ``refine_global_motion`` / ``motion_correct_sum_fast`` at ``fourier_crop_pixel_spacing``.  Argument rules as
+    ``fourier_crop_to``."""
+    thr = engine.check_hot_pixel_threshold(hot_pixel_threshold)  # every argument rule before any device
+    _check_raw_args(movie, gain)
+    out_shape = _check_crop_to_args(movie.shape, shape)
+    want_counts = bool(return_hot_counts)
+    with gpu_entry(movie, device) as (out_dev, dev):
+        raw, gd = _stage_raw(movie, gain, dev)
+        crop = lambda src: engine.fourier_crop_to(src, out_shape)  # noqa: E731  (a RawMovie or the conditioned movie)
+        cropped, counts = _raw_or_conditioned(raw, gd, mean_zero, thr=thr, fused=crop, conditioned=crop)
+        if not want_counts:
+            return cropped.to(out_dev)
+        return cropped.to(out_dev), _hot_counts_out(counts, movie.shape[0], out_dev)
+
+
+def fourier_crop_shape(h, w, binning):
+    """The (h2, w2) ``fourier_crop_to`` takes for frames of (h, w) that lies nearest (h / binning, w / binning), for
+    a factor >= 1: (4092, 5760, 2) -> (2046, 2880), (8184, 11520, 1.5) -> (5456, 7680).  NotImplementedError, listing
+    the factors there are for that frame size, where no supported shape is within 0.5 % on both axes.  Plain Python:
+    no device."""
+    h, w = operator.index(h), operator.index(w)
+    try:
+        b = float(binning)
+    except (TypeError, ValueError):
+        raise ValueError(f"binning must be a number >= 1, got {binning!r}") from None
+    if isinstance(binning, bool) or not (math.isfinite(b) and b >= 1.0):
+        raise ValueError(f"binning must be a number >= 1, got {binning!r}")
+    shapes = engine.fourier_crop_to_shapes(h, w)
+    miss = lambda s: max(abs(s[0] * b / h - 1.0), abs(s[1] * b / w - 1.0))  # noqa: E731
+    best = min(shapes, key=miss, default=None)
+    if best is None or miss(best) > 0.005:
+        factors = sorted({round(h / h2, 4) for h2, w2 in shapes if abs((h / h2) / (w / w2) - 1.0) <= 0.005})
+        raise NotImplementedError(f"frames of {h} x {w} by {binning!r}: the Fourier crop has the factors "
+                                  f"{', '.join(f'{f:g}' for f in factors) or 'none'} for this size; it takes "
+                                  f"{engine.FOURIER_CROP_TO_SIZES}")
+    return best
+
+
+def fourier_crop_pixel_spacing(shape_in, shape_out, pixel_spacing):
+    """(ps_y, ps_x) of a frame cropped from ``shape_in`` to ``shape_out`` (their last two entries): the field of view
+    stays, so each axis' spacing grows by its own ratio, ``pixel_spacing * h / h2`` and ``pixel_spacing * w / w2``
+    (4092 / 2046 = 5760 / 2880 = 2 exactly; 8184 / 5456 = 11520 / 7680 = 1.5)."""
+    (h, w), (h2, w2) = (tuple(int(v) for v in s[-2:]) for s in (shape_in, shape_out))
+    if min(h, w, h2, w2) < 1:
+        raise ValueError(f"shapes must be positive, got {h} x {w} and {h2} x {w2}")
+    ps = float(pixel_spacing)
+    return ps * h / h2, ps * w / w2
 
 
 # ------------------------------------------------------------------ frame groups (low-dose movies)

@@ -88,6 +88,17 @@ static inline bool full_rows_ok(int W) {
 }
 static inline bool full_cols_ok(int H) { return (mc_is_pow2(H) && H >= 256 && H <= 4096) || H == 4092 || H == 8184; }
 
+// What Fourier cropping to a given size (fourier_crop_to.hip) adds, for its OUTPUT side alone: the heights its
+// column pass comes out at and the widths mc_full_rows_inverse then takes (W / 2 = 1440, 1536, 1920, 3840 points).
+// No forward pass and no other column pass takes them, so full_rows_ok / full_cols_ok stay what they were.
+static inline bool full_crop_rows_ok(int W) { return W == 2880 || W == 3072 || W == 3840 || W == 7680; }
+static inline bool full_crop_cols_ok(int H) { return H == 384 || H == 2046 || H == 2728 || H == 3072 || H == 5456; }
+// the inverse row pass: every size of the transforms above, and the cropped ones
+static inline bool full_rows_inverse_ok(int H, int W, int pitch) {
+  return (full_rows_ok(W) || full_crop_rows_ok(W)) && (full_cols_ok(H) || full_crop_cols_ok(H)) &&
+         pitch >= W / 2 + 1 && (pitch % 16) == 0;
+}
+
 // columns per workgroup: pairs while two lines fit twice into a CU's LDS, single columns above;
 // threads per workgroup: 512 for 8184 rows (264 radix-31 butterflies per column)
 template <int H>
@@ -118,6 +129,13 @@ static inline dim3 full_rows_grid(int H, int njobs) {
     MC_FULL_CASE(2048, __VA_ARGS__) MC_FULL_CASE(4096, __VA_ARGS__) MC_FULL_CASE(2880, __VA_ARGS__) \
     MC_FULL_CASE(5760, __VA_ARGS__)                                                                 \
     default: return MC_ERR_UNSUPPORTED;                                                             \
+  }
+// the inverse row pass: those, and the lines of the cropped widths 2880, 3072, 3840 and 7680
+#define MC_FULL_DISPATCH_ROWS_INVERSE(NV, ...)                                                        \
+  switch (NV) {                                                                                       \
+    MC_FULL_CASE(1440, __VA_ARGS__) MC_FULL_CASE(1536, __VA_ARGS__) MC_FULL_CASE(1920, __VA_ARGS__)   \
+    MC_FULL_CASE(3840, __VA_ARGS__)                                                                   \
+    default: MC_FULL_DISPATCH_ROWS(NV, __VA_ARGS__)                                                   \
   }
 // rows of a column line (H) taken by the staged kernels (4096: the register-resident kernels)
 #define MC_FULL_DISPATCH_COLS(HV, ...)                                                             \

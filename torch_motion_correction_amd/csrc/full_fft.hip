@@ -26,7 +26,8 @@
 // Sizes: rows of W = 64 .. 8192 (powers of two), 5760 and 11520 columns (W / 2 = 2^a 3^2 5);
 // columns of H = 256 .. 4096 (powers of two), 4092 and 8184 rows (2^a 3 11 31: radix-31 and radix-11
 // passes, mc_fft.h) -- the K3 detector's two frame formats (BASELINE configs 3 and 5) run here
-// without chirp-z.  Columns of more than 4096 rows go one column per workgroup (NC = 1).
+// without chirp-z.  Columns of more than 4096 rows go one column per workgroup (NC = 1).  full_rows_inv alone also
+// takes the sizes Fourier cropping comes out at (fourier_crop_to.hip; full_common.h: full_rows_inverse_ok).
 //
 // This file holds the per-frame transforms of correct_motion_fast; the accumulating column passes, the raw row
 // pass and its hot-pixel fix are full_sums.hip, an object of its own (one object holding both changed
@@ -238,8 +239,9 @@ int mc_full_rows_forward(const float* src, const int64_t* job_off, int64_t row_s
 int mc_full_rows_inverse(const void* S, float* out, const int64_t* out_off, int64_t out_stride,
                          const void* tw_row, int njobs, int H, int W, int pitch, void* stream) {
   if (!S || !out || !out_off || !tw_row || njobs < 1) return MC_ERR_ARG;
-  if (!full_sizes_ok(H, W, pitch) || (reinterpret_cast<uintptr_t>(out) & 7) || (out_stride & 1)) return MC_ERR_UNSUPPORTED;
-  MC_FULL_DISPATCH_ROWS(W / 2, {
+  if (!full_rows_inverse_ok(H, W, pitch) || (reinterpret_cast<uintptr_t>(out) & 7) || (out_stride & 1))
+    return MC_ERR_UNSUPPORTED;
+  MC_FULL_DISPATCH_ROWS_INVERSE(W / 2, {
     auto k = full_rows_inv<L>;
     const size_t lds = sizeof(cfloat) * ((size_t)lds_len(L) + 1 + L + 2);
     MC_SET_LDS(k, lds);

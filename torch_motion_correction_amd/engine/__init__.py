@@ -45,6 +45,9 @@ RIGID_KERNEL_HOOK = None  # callable(fn) -> calls fn(); set by bench.py to time 
 REFINE_MAX_FRAMES = 512  # mc_xc_aligned_refs / mc_xc_refine_update
 FOURIER_CROP_SIZES = ("heights 512, 1024, 2048, 4096 and 8184 and widths 128, 256, ..., 8192 and 11520 "
                       "(any combination)")
+FOURIER_CROP_TO_SIZES = ("heights 512 -> 384, 4096 -> 3072, 4092 -> 2046, 8184 -> 5456 and 8184 -> 2728 with widths "
+                         "64, 128, ..., 8192, 5760 and 11520 -> any of those or 2880, 3072, 3840 and 7680 that is no "
+                         "wider (any combination), and the halving of " + FOURIER_CROP_SIZES)
 GROUP_WINDOW_MAX = {torch.uint8: 128, torch.int16: 32768}  # frames of a window whose sum stays exact (raw_group.hip)
 
 
@@ -137,7 +140,9 @@ from .warps import (  # noqa: E402
 from .fourier import (  # noqa: E402
     _dose_weighted_sum_polyphase, _fourier_shift_polyphase, _fourier_shift_row_major, _full_row_major_ok,
     _full_spectra_chunks, _inverse_frames, _polyphase_geometry, _row_major_sums, _rows_forward, dose_weighted_sum,
-    fast_shift_sums, fast_shifts, fourier_crop, fourier_crop_supported, fourier_shift, warp_dose_weighted_sum)
+    CROP_TO_HEIGHTS, CROP_TO_WIDTHS_IN, CROP_TO_WIDTHS_OUT, fast_shift_sums, fast_shifts, fourier_crop,
+    fourier_crop_supported, fourier_crop_to, fourier_crop_to_shapes, fourier_crop_to_supported, fourier_shift,
+    warp_dose_weighted_sum)
 from .raw import (  # noqa: E402
     _HOT_NONE, _RAW_KINDS, RawMovie, _global_spectra_raw, _local_raw_check, _patch_spectra_raw, _raw_patch_plan,
     _raw_rows_forward, _warp_hot_correct, check_hot_pixel_threshold, corrected_sums, global_shifts_raw,

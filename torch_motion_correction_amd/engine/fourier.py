@@ -325,22 +325,27 @@ def fourier_crop_supported(h, w):
     return ((E._pow2(h) and 512 <= h <= 4096) or h == 8184) and ((E._pow2(w) and 128 <= w <= 8192) or w == 11520)
 
 
-def fourier_crop(src):
+def fourier_crop(src, out_shape=None):
     """Fourier cropping by 2 per axis: per frame irfft2 of the rows -h/4 <= ky < h/4 and columns kx <= w/4 of
     rfft2(frame), at (h/2, w/2), the frame's sum kept (scale 1 / ((h/2)(w/2))).  `src`: an fp32 (t, h, w) tensor, or
     a RawMovie, whose chunks are transformed from the raw bytes (_raw_rows_forward: no fp32 movie).  Per chunk of
     frames (the WORKSPACE_BYTES rule over the spectrum and its cropped copy): rows forward at (h, w) ->
     mc_full_cols_crop -> rows inverse at (h/2, w/2) straight into the (t, h/2, w/2) fp32 result.  Raises
-    McorrUnsupported for other shapes, before any launch."""
+    McorrUnsupported for other shapes, before any launch.
+
+    `out_shape` (fourier_crop_to's, which has checked it; None: the halving above, as ever): the same loop to
+    (h2, w2) -- the rows -h2/2 <= ky < h2/2 and columns kx <= w2/2, scale 1 / (h2 w2) -- with mc_full_cols_crop_to
+    as the column pass, which reads the h2-point twiddle table besides the h-point one."""
     raw = isinstance(src, E.RawMovie)
     t, h, w = src.shape
-    if not fourier_crop_supported(h, w):
+    if out_shape is None and not fourier_crop_supported(h, w):
         raise _lib.McorrUnsupported(f"no Fourier crop for frames of {h} x {w}: it takes {E.FOURIER_CROP_SIZES}")
     lib = _lib.load()
     dev = src.raw.device if raw else src.device
-    h2, w2 = h // 2, w // 2
+    h2, w2 = (h // 2, w // 2) if out_shape is None else out_shape
     pitch, pitch2 = lib.mc_full_spectrum_pitch(w), lib.mc_full_spectrum_pitch(w2)
     tw_col, tw_row2 = planmod.get_twiddles(h, dev), planmod.get_twiddles(w2, dev)
+    tw_col2 = None if out_shape is None else planmod.get_twiddles(h2, dev)
     out = torch.empty((t, h2, w2), dtype=torch.float32, device=dev)
     chunk, spans = E._chunks(t, (h * pitch + h2 * pitch2) * 8)
     S = torch.empty((chunk, h, pitch, 2), dtype=torch.float32, device=dev)
@@ -351,8 +356,51 @@ def fourier_crop(src):
             E._raw_rows_forward(src, a, n, S)
         else:
             E._rows_forward(src, a, n, S)
-        check(lib.mc_full_cols_crop(ptr(S), ptr(S2), ptr(tw_col), n, h, w, pitch, pitch2, st), "mc_full_cols_crop")
+        if out_shape is None:
+            check(lib.mc_full_cols_crop(ptr(S), ptr(S2), ptr(tw_col), n, h, w, pitch, pitch2, st), "mc_full_cols_crop")
+        else:
+            check(lib.mc_full_cols_crop_to(ptr(S), ptr(S2), ptr(tw_col), ptr(tw_col2), n, h, w, h2, w2, pitch, pitch2,
+                                           st), "mc_full_cols_crop_to")
         off = torch.arange(a, a + n, device=dev, dtype=torch.int64) * (h2 * w2)
         check(lib.mc_full_rows_inverse(ptr(S2), ptr(out), ptr(off), w2, ptr(tw_row2), n, h2, w2, pitch2, st),
               "mc_full_rows_inverse")
     return out
+
+
+# (h -> h2) pairs of mc_full_cols_crop_to; the widths mc_full_rows_forward reads and mc_full_rows_inverse writes
+CROP_TO_HEIGHTS = {512: (384,), 4096: (3072,), 4092: (2046,), 8184: (5456, 2728)}
+CROP_TO_WIDTHS_IN = tuple(1 << p for p in range(6, 14)) + (5760, 11520)
+CROP_TO_WIDTHS_OUT = tuple(sorted(CROP_TO_WIDTHS_IN + (2880, 3072, 3840, 7680)))
+
+
+def fourier_crop_to_supported(h, w, h2, w2):
+    """Frames fourier_crop_to brings from (h, w) to (h2, w2): a height pair of mc_full_cols_crop_to with any width
+    pair (w a forward row length, w2 <= w an inverse one) -- the axes are independent -- or the halving of both axes
+    fourier_crop takes."""
+    if (h2, w2) == (h // 2, w // 2) and h % 2 == 0 and w % 2 == 0 and fourier_crop_supported(h, w):
+        return True
+    return h2 in CROP_TO_HEIGHTS.get(h, ()) and w in CROP_TO_WIDTHS_IN and w2 in CROP_TO_WIDTHS_OUT and w2 <= w
+
+
+def fourier_crop_to_shapes(h, w):
+    """Every (h2, w2) fourier_crop_to_supported(h, w, h2, w2) holds for, sorted."""
+    found = {(h2, w2) for h2 in CROP_TO_HEIGHTS.get(h, ()) for w2 in CROP_TO_WIDTHS_OUT
+             if fourier_crop_to_supported(h, w, h2, w2)}
+    if fourier_crop_to_supported(h, w, h // 2, w // 2):
+        found.add((h // 2, w // 2))
+    return sorted(found)
+
+
+def fourier_crop_to(src, out_shape):
+    """Fourier cropping to `out_shape` = (h2, w2): per frame irfft2 of the rows -h2/2 <= ky < h2/2 (the new Nyquist
+    row from the negative side) and columns kx <= w2/2 of rfft2(frame), at (h2, w2), the frame's sum kept (scale
+    1 / (h2 w2)).  `src` as for fourier_crop, whose chunk loop runs it with mc_full_cols_crop_to as the column pass;
+    the halving of a frame fourier_crop takes IS fourier_crop (the same launches, the same bits).  Raises
+    McorrUnsupported for every other pair of shapes, before any launch."""
+    t, h, w = src.shape
+    h2, w2 = int(out_shape[0]), int(out_shape[1])
+    if not fourier_crop_to_supported(h, w, h2, w2):
+        raise _lib.McorrUnsupported(f"no Fourier crop from {h} x {w} to {h2} x {w2}: it takes {E.FOURIER_CROP_TO_SIZES}")
+    if (h2, w2) == (h // 2, w // 2) and fourier_crop_supported(h, w):
+        return E.fourier_crop(src)
+    return E.fourier_crop(src, (h2, w2))
