@@ -13,6 +13,7 @@ import os
 import re
 import shutil
 import subprocess
+import time
 
 import numpy as np
 import pytest
@@ -385,3 +386,261 @@ def switches(monkeypatch):
     plan._LINES.clear()
     yield engine, plan
     plan._LINES.clear()
+
+
+# ------------------------------------------------------------------ stream ordering: a delayed producer on a side stream
+#
+# tests/test_stream_order.py's method.  The inputs of a case are staged and the result `want` is computed on the
+# default stream.  Then, on a fresh side stream S: a sleep kernel (the gate), device-to-device copies of the true
+# inputs over POISONED twins, the `gate` event, and the route under test on the twins.  While S sleeps the rest of the
+# GPU is idle, so whatever the route enqueues on another side stream runs at once, on poison or on accumulators nobody
+# has cleared, and the result is grossly wrong.  (Not reliably so the null stream: on the MI355X runtime a null-stream
+# launch was ordered after S's pending work in one run and not in the next; the stream ARGUMENT of every call is what
+# pins it.)  GatedRecorder writes down, per entry-point
+# call, the stream argument and whether the gate was still pending before and after the call: a call that was made
+# after the sleep ended proves nothing and is reported as such, never counted.
+
+
+def stream_parameter(name, header=None):
+    """The index of the `stream` parameter of the entry point `name` in the header, None where it has none."""
+    for i, param in enumerate(header_parameters(name, header)):
+        if re.search(r"\bstream$", param):
+            return i
+    return None
+
+
+def stream_entry_points(names=None, header=None):
+    """The entry points among `names` (default: every name of _lib.SIGNATURES) whose header declaration has a
+    `stream` parameter, and whose binding puts a c_void_p there: pure host functions fall out."""
+    if names is None:
+        from torch_motion_correction_amd import _lib
+
+        names = _lib.SIGNATURES
+    out = set()
+    for name in names:
+        i = stream_parameter(name, header)
+        if i is not None:
+            assert header_signature(name, header)[i] is ctypes.c_void_p, f"{name}: stream is no pointer"
+            out.add(name)
+    return out
+
+
+def poisoned(x):
+    """The poisoned twin of a device input, a new tensor: NaN for floating point, the bitwise complement for a u8 /
+    i16 movie.  An int32 / int64 input is an index or offset table in this suite and is copied as it is: a launch on
+    the wrong stream then still reads poisoned samples, but never indexes outside an allocation."""
+    if x.is_floating_point():
+        return torch.full_like(x, float("nan"))
+    if x.dtype in (torch.uint8, torch.int16, torch.bool):
+        return torch.bitwise_not(x) if x.dtype != torch.bool else torch.logical_not(x)
+    assert x.dtype in (torch.int32, torch.int64), x.dtype
+    return x.clone()
+
+
+def _tensor_slots(obj):
+    """(holder, key) of every tensor of a case's input: a tensor itself is slot (None, None); an object (a RawMovie,
+    a DefectFill) holds its tensors as attributes.  A tensor inside a tuple, list or dict attribute would be shared
+    with the true input and never poisoned: AssertionError."""
+    if isinstance(obj, torch.Tensor):
+        return [(None, None)]
+    for k, v in vars(obj).items():
+        assert not _holds_tensor(v), (f"{type(obj).__name__}.{k} holds tensors in a container: they would not be "
+                                      "poisoned")
+    return [(obj, k) for k, v in sorted(vars(obj).items()) if isinstance(v, torch.Tensor)]
+
+
+def _holds_tensor(v):
+    if isinstance(v, (tuple, list)):
+        return any(isinstance(x, torch.Tensor) or _holds_tensor(x) for x in v)
+    if isinstance(v, dict):
+        return any(isinstance(x, torch.Tensor) or _holds_tensor(x) for x in v.values())
+    return False
+
+
+def poisoned_twins(inputs):
+    """{name: input} -> ({name: poisoned twin}, [(twin tensor, true tensor), ...]): a tensor's twin is poisoned(); an
+    object's twin is a shallow copy whose tensor attributes are poisoned twins (everything else is shared)."""
+    import copy
+
+    twins, pairs = {}, []
+    for name, obj in inputs.items():
+        if obj is None or not (isinstance(obj, torch.Tensor) or hasattr(obj, "__dict__")):
+            twins[name] = obj  # a scalar, a tuple, a string: passed through
+            continue
+        if isinstance(obj, torch.Tensor):
+            twins[name] = poisoned(obj)
+            pairs.append((twins[name], obj))
+            continue
+        twin = copy.copy(obj)
+        for _, k in _tensor_slots(obj):
+            true = getattr(obj, k)
+            setattr(twin, k, poisoned(true))
+            pairs.append((getattr(twin, k), true))
+        twins[name] = twin
+    return twins, pairs
+
+
+class GatedRecorder(Recorder):
+    """Recorder that knows about the gate.  Armed with the `gate` event (anything with .query()) and the side
+    stream's handle, it writes down per entry-point call, in `log`: (name, the `stream` argument as an int, 0 for the
+    null stream, None where the entry point takes none; gate pending before the call; gate pending after it
+    returned).  Unarmed it is a Recorder."""
+
+    def __init__(self, lib, header=None):
+        super().__init__(lib)
+        self.log, self.gate, self.stream, self.enqueue_ms = [], None, None, None
+        self._header, self._slot = header, {}
+
+    def arm(self, gate, stream):
+        self.clear()
+        self.gate, self.stream = gate, int(stream)
+
+    def disarm(self):
+        """No call is logged from here on; the log and the armed stream stay for the assertions."""
+        self.gate = None
+
+    def clear(self):
+        super().clear()
+        del self.log[:]
+
+    def _stream_of(self, name, a):
+        if name not in self._slot:
+            try:
+                self._slot[name] = stream_parameter(name, self._header)
+            except KeyError:
+                self._slot[name] = None
+        i = self._slot[name]
+        if i is None:
+            return None
+        v = a[i]
+        v = getattr(v, "value", v)
+        return 0 if v is None else int(v)
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*a):
+            self.names.append(name)
+            self.args.setdefault(name, []).append(a)
+            if self.gate is None:
+                return fn(*a)
+            before = not self.gate.query()
+            out = fn(*a)
+            self.log.append((name, self._stream_of(name, a), before, not self.gate.query()))
+            return out
+
+        return call
+
+    def streams_ok(self, *names):
+        """Every recorded call of `names` (default: of every stream-taking entry point that ran) had the armed stream
+        as its stream argument."""
+        for name, st, _, _ in self.log:
+            if st is not None and (not names or name in names):
+                assert st == self.stream, f"{name} was launched on stream {st:#x}, not on {self.stream:#x}"
+        for name in names:
+            assert any(n == name for n, *_ in self.log), f"{name} did not run ({sorted(set(self.names))})"
+
+    def proven(self, *names):
+        """Every call of each of `names` ran at least once, on the armed stream, with the gate pending when it was
+        called AND when it returned (the entry point did not wait for the stream).  A call after the sleep has ended
+        proves nothing: AssertionError('inconclusive ...'), never a pass."""
+        self.streams_ok(*names)
+        for name in names:
+            for n, _, before, after in self.log:
+                if n == name:
+                    assert before, f"inconclusive: the gate had opened before {name} was called"
+                    assert after, f"{name} returned after the gate had opened: it waited for the stream"
+
+    def pending(self):
+        """The names whose every call had the gate pending before and after, in first-call order (a survey)."""
+        bad = {n for n, _, b, a in self.log if not (b and a)}
+        return [n for n in dict.fromkeys(n for n, *_ in self.log) if n not in bad]
+
+
+def sleep_cycles_for(ms_per_cycle, target_ms):
+    """The `cycles` argument of torch.cuda._sleep for a delay of `target_ms`, from a measured rate."""
+    assert ms_per_cycle > 0 and target_ms > 0
+    return max(1, int(round(target_ms / ms_per_cycle)))
+
+
+def calibrate_sleep(cycles=20_000_000):
+    """ms per cycle of torch.cuda._sleep on the current device, timed once with two events."""
+    torch.cuda._sleep(1000)  # the kernel's first launch loads its code
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    torch.cuda._sleep(cycles)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / cycles
+
+
+def gated_run(route, inputs, rec, cycles, want=None):
+    """The delayed-producer run of `route(**inputs)` -> (want, got, S).  `inputs`: {name: device tensor, object with
+    device tensors as attributes (RawMovie), or plain value}, staged and synchronised by the caller.  `want` is
+    route(**inputs) on the default stream (computed here unless given; it also fills every plan and table cache, so
+    that nothing behind the gate copies from host memory).  Then on a fresh side stream S: sleep, copy the true
+    inputs over their poisoned twins, record the gate, arm `rec`, run the route on the twins, synchronise S."""
+    if want is None:
+        want = route(**inputs)
+    torch.cuda.synchronize()
+    twins, pairs = poisoned_twins(inputs)
+    torch.cuda.synchronize()
+    S = torch.cuda.Stream()
+    gate = torch.cuda.Event()
+    with torch.cuda.stream(S):
+        torch.cuda._sleep(cycles)
+        for twin, true in pairs:
+            twin.copy_(true, non_blocking=True)
+        gate.record(S)
+        rec.arm(gate, S.cuda_stream)
+        t0 = time.perf_counter()
+        try:
+            got = route(**twins)
+        finally:
+            rec.enqueue_ms = 1e3 * (time.perf_counter() - t0)  # the host's time in the route, read-backs included
+            rec.disarm()
+        S.synchronize()
+    return want, got, S
+
+
+def leaves(x):
+    """The tensors of a route's result (a tensor, or nested tuples / lists with None allowed), in order."""
+    if x is None:
+        return []
+    if isinstance(x, torch.Tensor):
+        return [x]
+    if isinstance(x, (tuple, list)):
+        return [t for v in x for t in leaves(v)]
+    return []  # a float, a history on the CPU as a list ...
+
+
+def assert_same_bits(got, want, what):
+    """Every tensor of `got` equals its twin in `want` bit for bit (NaN included: compared as integers)."""
+    g, w = leaves(got), leaves(want)
+    assert len(g) == len(w) and len(w) >= 1, f"{what}: {len(g)} results, {len(w)} wanted"
+    for i, (a, b) in enumerate(zip(g, w)):
+        assert a.shape == b.shape and a.dtype == b.dtype, f"{what}[{i}]: {a.shape} {a.dtype} vs {b.shape} {b.dtype}"
+        a, b = a.detach().contiguous().cpu(), b.detach().contiguous().cpu()
+        bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[a.element_size()]
+        if a.dtype == torch.bool:
+            bits = torch.bool
+        same = torch.equal(a.view(bits), b.view(bits))
+        if not same:
+            bad = int((a.view(bits) != b.view(bits)).sum())
+            nans = int(torch.isnan(a).sum()) if a.is_floating_point() else 0
+            raise AssertionError(f"{what}[{i}]: {bad} of {a.numel()} elements differ ({nans} NaN)")
+
+
+def assert_close_rel(got, want, rel, what, exact=()):
+    """Every floating-point tensor of `got` within rel * max |want| of its twin, NaN never; every integer tensor,
+    and every tensor whose position is in `exact`, equal bit for bit."""
+    g, w = leaves(got), leaves(want)
+    assert len(g) == len(w) and len(w) >= 1, f"{what}: {len(g)} results, {len(w)} wanted"
+    for i, (a, b) in enumerate(zip(g, w)):
+        assert a.shape == b.shape and a.dtype == b.dtype, f"{what}[{i}]: {a.shape} {a.dtype} vs {b.shape} {b.dtype}"
+        if i in exact or not a.is_floating_point():
+            assert_same_bits(a, b, f"{what}[{i}]")
+            continue
+        e = rel_err(a, b)
+        assert e <= rel, f"{what}[{i}]: relative error {e!r} beyond {rel!r}"  # NaN fails: not <=

@@ -354,3 +354,147 @@ def test_switches_restores_every_switch_assigned_in_the_body(former, switches):
     plan._LINES["stale"] = None
     assert all(_switch_values()[k] != v for k, v in former.items())
 
+
+
+# ------------------------------------------------------------------ stream ordering: the delayed-producer tools
+
+_HEADER = """
+/* a comment with void* stream in it */
+int mc_a(const float* x, int n, void* stream);
+int mc_b(int n);
+int mc_c(void* stream, int n);  // the stream need not come last
+"""
+
+
+class _Gate:
+    """An event whose query() answers True (the sleep has ended) from the `opens`-th question on."""
+
+    def __init__(self, opens):
+        self.asked, self.opens = 0, opens
+
+    def query(self):
+        self.asked += 1
+        return self.asked > self.opens
+
+
+def test_stream_parameter_and_stream_entry_points():
+    assert kh.stream_parameter("mc_a", _HEADER) == 2 and kh.stream_parameter("mc_b", _HEADER) is None
+    assert kh.stream_parameter("mc_c", _HEADER) == 0
+    assert kh.stream_entry_points(["mc_a", "mc_b", "mc_c"], _HEADER) == {"mc_a", "mc_c"}
+    with pytest.raises(KeyError):
+        kh.stream_parameter("mc_d", _HEADER)
+    taking = kh.stream_entry_points()  # the committed header over _lib.SIGNATURES
+    assert {"mc_normalize", "mc_tiff_decode", "mc_xc_rows_forward"} <= taking
+    assert not taking & {"mc_abi_version", "mc_xc_near_rows", "mc_warp_scratch_bytes", "mc_local_loss_tiles"}
+
+
+def test_poisoned_twins():
+    f = torch.arange(6, dtype=torch.float32).reshape(2, 3)
+    u = torch.tensor([0, 1, 254, 255], dtype=torch.uint8)
+    i = torch.tensor([-32768, -1, 0, 5], dtype=torch.int16)
+    idx = torch.tensor([3, 1, 2], dtype=torch.int64)
+    assert bool(torch.isnan(kh.poisoned(f)).all()) and kh.poisoned(f).shape == f.shape
+    assert kh.poisoned(u).tolist() == [255, 254, 1, 0] and kh.poisoned(i).tolist() == [32767, 0, -1, -6]
+    assert torch.equal(kh.poisoned(idx), idx) and kh.poisoned(idx).data_ptr() != idx.data_ptr()  # an index table
+    assert kh.poisoned(f.half()).dtype == torch.float16
+
+    class Movie:
+        pass
+
+    m = Movie()
+    m.raw, m.mu, m.kind, m.nothing = u, f, 0, None
+    twins, pairs = kh.poisoned_twins(dict(x=f, m=m, n=7, none=None, name="catmull_rom"))
+    assert twins["n"] == 7 and twins["none"] is None and twins["name"] == "catmull_rom"
+    assert twins["m"] is not m and twins["m"].kind == 0 and twins["m"].nothing is None
+    assert twins["m"].raw.tolist() == [255, 254, 1, 0] and bool(torch.isnan(twins["m"].mu).all())
+    assert m.raw is u and m.mu is f and u.tolist() == [0, 1, 254, 255]  # the true inputs are untouched
+    assert len(pairs) == 3
+    m.frames = [u]  # a tensor in a container would be shared with the true input, unpoisoned
+    with pytest.raises(AssertionError, match="Movie.frames holds tensors in a container"):
+        kh.poisoned_twins(dict(m=m))
+    m.frames = {"a": (1, [f])}
+    with pytest.raises(AssertionError, match="Movie.frames holds tensors"):
+        kh.poisoned_twins(dict(m=m))
+    m.frames = [1, 2, (3, "x")]  # plain values in containers are shared, as every non-tensor is
+    assert len(kh.poisoned_twins(dict(m=m))[1]) == 2
+    for twin, true in pairs:  # what gated_run enqueues behind the gate
+        twin.copy_(true)
+    assert torch.equal(twins["x"], f) and torch.equal(twins["m"].raw, u) and torch.equal(twins["m"].mu, f)
+
+
+class _StreamLib:
+    def mc_a(self, *a):
+        return 0
+
+    def mc_b(self, *a):
+        return 0
+
+    def mc_c(self, *a):
+        return 0
+
+
+def test_gated_recorder_proves_only_with_the_gate_pending():
+    import ctypes
+
+    S = 0x7F00
+    rec = kh.GatedRecorder(_StreamLib(), header=_HEADER)
+    rec.mc_a(None, 1, ctypes.c_void_p(S))  # unarmed: a Recorder
+    assert rec.names == ["mc_a"] and rec.log == []
+    rec.arm(_Gate(opens=4), S)
+    assert rec.names == []  # arming starts a new record
+    rec.mc_a(None, 1, ctypes.c_void_p(S))  # questions 1, 2: pending before and after
+    rec.mc_b(3)  # questions 3, 4: no stream parameter
+    rec.mc_c(ctypes.c_void_p(S), 1)  # questions 5, 6: the gate has opened
+    rec.disarm()
+    rec.mc_a(None, 1, ctypes.c_void_p(S))  # not logged
+    assert rec.log == [("mc_a", S, True, True), ("mc_b", None, True, True), ("mc_c", S, False, False)]
+    assert rec.names == ["mc_a", "mc_b", "mc_c", "mc_a"]  # the Recorder's interface goes on
+    rec.streams_ok()
+    rec.streams_ok("mc_a", "mc_c")
+    rec.proven("mc_a")
+    assert rec.pending() == ["mc_a", "mc_b"]
+    with pytest.raises(AssertionError, match="inconclusive: the gate had opened before mc_c"):
+        rec.proven("mc_c")
+    with pytest.raises(AssertionError, match="mc_d did not run"):
+        rec.proven("mc_d")
+    # pending when called, open when it returned: the entry point waited for the stream
+    rec.arm(_Gate(opens=1), S)
+    rec.mc_a(None, 1, ctypes.c_void_p(S))
+    with pytest.raises(AssertionError, match="mc_a returned after the gate had opened"):
+        rec.proven("mc_a")
+    # the null stream (None, or a c_void_p of 0) and any other stream are not S
+    for wrong in (None, ctypes.c_void_p(0), ctypes.c_void_p(0x1234)):
+        rec.arm(_Gate(opens=10), S)
+        rec.mc_a(None, 1, wrong)
+        with pytest.raises(AssertionError, match="mc_a was launched on stream"):
+            rec.proven("mc_a")
+        with pytest.raises(AssertionError, match="mc_a was launched on stream"):
+            rec.streams_ok()
+    assert rec.log[-1][1] == 0x1234
+
+
+def test_sleep_cycles_and_comparisons():
+    assert kh.sleep_cycles_for(0.5e-6, 100.0) == 200_000_000 and kh.sleep_cycles_for(1.0, 0.2) == 1
+    with pytest.raises(AssertionError):
+        kh.sleep_cycles_for(0.0, 100.0)
+    a = torch.tensor([1.0, float("nan"), -0.0])
+    assert kh.leaves((a, None, [a, (a,)], 3.0)) == [a, a, a]
+    kh.assert_same_bits((a, [a]), (a.clone(), [a.clone()]), "same")  # NaN equals NaN: bits are compared
+    with pytest.raises(AssertionError, match=r"x\[0\]: 1 of 3 elements differ"):
+        kh.assert_same_bits(a, torch.tensor([1.0, float("nan"), 0.0]), "x")  # -0.0 is not +0.0
+    with pytest.raises(AssertionError, match="1 results, 2 wanted"):
+        kh.assert_same_bits(a, (a, a), "x")
+    with pytest.raises(AssertionError, match="0 results"):
+        kh.assert_same_bits(None, None, "x")
+    b = torch.tensor([1.0, 2.0, 100.0])
+    kh.assert_close_rel(b + 5e-3, b, 1e-4, "close")
+    with pytest.raises(AssertionError, match="relative error"):
+        kh.assert_close_rel(b + 0.1, b, 1e-4, "far")
+    with pytest.raises(AssertionError, match="relative error"):
+        kh.assert_close_rel(torch.tensor([1.0, float("nan"), 100.0]), b, 1e-4, "poison")
+    n = torch.tensor([3, 4], dtype=torch.int32)
+    kh.assert_close_rel((b + 5e-3, n), (b, n.clone()), 1e-4, "integers exact")
+    with pytest.raises(AssertionError, match=r"x\[1\]\[0\]: 1 of 2 elements differ"):
+        kh.assert_close_rel((b, n + torch.tensor([0, 1], dtype=torch.int32)), (b, n), 1.0, "x")  # integers: exact
+    with pytest.raises(AssertionError, match=r"x\[0\]\[0\]: 3 of 3"):
+        kh.assert_close_rel((b + 5e-3, n), (b, n), 1e-4, "x", exact=(0,))  # a float leaf named exact

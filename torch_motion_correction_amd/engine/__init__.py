@@ -54,17 +54,34 @@ GROUP_WINDOW_MAX = {torch.uint8: 128, torch.int16: 32768}  # frames of a window 
 # ------------------------------------------------------------------ shared helpers
 
 
-_CONST: dict = {}
+_CONST: dict = {}  # any stream may read an entry: _cached synchronises the stream that built it, once per key
 
 
 def _cached(key, build):
-    """Small device-resident index/tap tables, built once per (shape, device)."""
+    """Small device-resident index/tap tables, built once per (shape, device).  Some builders copy from host memory
+    (blocking), some run a device kernel (torch.arange on the device) on the current stream: the building stream is
+    synchronised (_sync_built: the current stream of the TABLES' device, which need not be the current device)
+    before the entry is stored, because every later call reads it from whichever stream is current then, with no
+    ordering against this one."""
     v = _CONST.get(key)
     if v is None:
         if len(_CONST) > 512:
             _CONST.clear()
-        v = _CONST[key] = build()
+        v = build()
+        _sync_built(v)
+        _CONST[key] = v
     return v
+
+
+def _sync_built(v):
+    """Synchronise the current stream of every device a freshly built table (a tensor, or tuples of them) lives on:
+    the stream its builder ran on."""
+    if isinstance(v, torch.Tensor):
+        if v.is_cuda:
+            torch.cuda.current_stream(v.device).synchronize()
+    elif isinstance(v, (tuple, list)):
+        for x in v:
+            _sync_built(x)
 
 
 def _i32(a, device):

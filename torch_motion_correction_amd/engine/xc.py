@@ -175,7 +175,9 @@ def mask_spectrum(pl, dev):
         g = pl.geom
         ones = torch.ones((g.H, g.W), dtype=torch.float32, device=dev)
         off = torch.zeros(1, dtype=torch.int64, device=dev)
-        pl.mhat = _forward_spectra(ones, off, g.W, None, pl, None, use_filter=False)[0].contiguous()
+        mhat = _forward_spectra(ones, off, g.W, None, pl, None, use_filter=False)[0].contiguous()
+        torch.cuda.current_stream(dev).synchronize()  # cached on the plan, read from any stream: as plan.get_xc_plan
+        pl.mhat = mhat
     return pl.mhat
 
 

@@ -163,7 +163,7 @@ def bluestein_size(n: int) -> int:
     return bluestein_size_for(2 * n - 1)
 
 
-_LINES: dict = {}
+_LINES: dict = {}  # any stream may read an entry: host-made tables behind blocking copies from host memory, or _TWIDDLES
 USE_DIRECT_LINES = True  # tests: False forces chirp-z on the mixed-radix lengths too
 
 
@@ -247,8 +247,8 @@ def row_chords(mask: torch.Tensor) -> torch.Tensor:
     return (torch.stack([first, last], dim=1) * 4).to(torch.int32).contiguous()
 
 
-_PLANS: dict = {}
-_TWIDDLES: dict = {}
+_PLANS: dict = {}  # any stream may read an entry: get_xc_plan synchronises the stream that built its tables, once per key
+_TWIDDLES: dict = {}  # any stream may read an entry: made on the host, one blocking copy from host memory
 
 
 def get_twiddles(n: int, device) -> torch.Tensor:
@@ -288,6 +288,10 @@ def get_xc_plan(h: int, w: int, pixel_spacing: float, b_factor: float, frequency
     plan = XcPlan(geom, mask, filt, get_twiddles(w, device), get_twiddles(h, device), low, high)
     if w % 4 == 0:
         plan.chord = row_chords(mask)
+    # the entry outlives this call and is read from ANY stream later, with no ordering against this one: the kernels
+    # and torch ops above have finished before it is published.  Once per key (the first call for a key blocks on
+    # the twiddles' copy from host memory anyway); a cached plan costs nothing per call.
+    torch.cuda.current_stream(device).synchronize()
     _PLANS[key] = plan
     return plan
 
