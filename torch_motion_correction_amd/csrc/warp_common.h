@@ -85,6 +85,23 @@ __device__ __forceinline__ void rigid_store4(float* p, float a, float b, float c
   __builtin_nontemporal_store(v, reinterpret_cast<rigid_f4*>(p));
 }
 
+// Frame f's weights of the strip at (x0, y0): Wv = the wave's 5 RIGID_ROWS row weights, one per lane (read
+// back with readlane), W5 = the 5 column taps of the lane's 4 pixels.  Needs w % 4 == 0.
+__device__ __forceinline__ void rigid_load_weights(const RigidArgs& a, int f, int y0, int x0, int lane,
+                                                   float (&W5)[5][4], float& Wv) {
+  const int h = a.h, w = a.w;
+  Wv = 0.f;
+  const int64_t idx = (int64_t)y0 * 5 + lane;
+  if (lane < 5 * RIGID_ROWS && idx < (int64_t)h * 5) Wv = a.Wy[(int64_t)f * 5 * h + idx];
+  const float* Wx = a.Wx + (int64_t)f * 5 * w + x0;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (x0 < w) t = *reinterpret_cast<const float4*>(Wx + (int64_t)j * w);
+    W5[j][0] = t.x; W5[j][1] = t.y; W5[j][2] = t.z; W5[j][3] = t.w;
+  }
+}
+
 // The rigid warp's scratch, Wy[f][h][5] | Wx[f][5][w] | S[f][2], carved from `scratch` (16-byte aligned).
 struct RigidTables {
   float* Wy;
@@ -111,6 +128,32 @@ static inline RigidTables rigid_tables_layout(float* scratch, int nframes, int h
 // it is not part of the C ABI.
 __attribute__((visibility("hidden"))) void mc_rigid_tables_launch(const float* shifts_px, int nframes, int h, int w,
                                                                   const RigidTables& t, hipStream_t s);
+// What every rigid entry refuses with MC_ERR_ARG, after its own storage-kind rule (MC_ERR_UNSUPPORTED).
+// phase 0: weight tables + resampling; 1: tables only (writes no image); 2: resampling only, the tables of an
+// earlier phase-1 call with the same arguments are in `scratch`.
+static inline int rigid_check_args(const void* frames, const float* shifts_px, const float* scratch,
+                                   const float* out_frames, const float* out_sum, int nframes, int h, int w, int phase) {
+  if (!frames || !shifts_px || !scratch || (phase != 1 && !out_frames && !out_sum)) return MC_ERR_ARG;
+  if (nframes < 1 || h < 2 || w < 2 || (((uintptr_t)scratch) & 15) || phase < 0 || phase > 2) return MC_ERR_ARG;
+  return MC_OK;
+}
+// the phase's table launch; true: the phase ends there
+static inline bool rigid_phase_tables(int phase, const float* shifts_px, int nframes, int h, int w, const RigidTables& t,
+                                      hipStream_t s) {
+  if (phase != 2) mc_rigid_tables_launch(shifts_px, nframes, h, w, t, s);
+  return phase == 1;
+}
+// kernel arguments for tiles of WX x WY waves
+static inline RigidArgs rigid_args(const void* frames, int nframes, int h, int w, const RigidTables& t, float* out_frames,
+                                   float* out_sum, int WX, int WY, int frames_in_grid) {
+  RigidArgs a;
+  a.frames = static_cast<const float*>(frames); a.nframes = nframes; a.h = h; a.w = w; a.S = t.S; a.Wy = t.Wy; a.Wx = t.Wx;
+  a.out_frames = out_frames; a.out_sum = out_sum;
+  a.tiles_x = (w + RIGID_LANES * 4 * WX - 1) / (RIGID_LANES * 4 * WX);
+  a.tiles_y = (h + WY * RIGID_ROWS - 1) / (WY * RIGID_ROWS);
+  a.frames_in_grid = frames_in_grid;
+  return a;
+}
 
 // Launch selection (mc_pick, mc_common.h) over what a warp kernel writes: `go` gets the matching
 // std::bool_constant tags.  Entry points reject "neither frames nor sum" before they get here.

@@ -32,14 +32,11 @@
 #define RIGID_NQ (RIGID_TROWS * RIGID_QUADS)           // quads per tile (2448)
 #define RIGID_QPT ((RIGID_NQ + 255) / 256)             // quads per thread (10)
 
-// pass 0: S[f][axis] = min_p floor(u(p)) - p.  One workgroup per (frame, axis): no atomics,
-// no pre-set of S (80 words fought over by 1280 workgroups cost 20 us in atomics alone).
-__global__ __launch_bounds__(256) void rigid_base(const float* __restrict__ shifts, int nframes, int h,
-                                                  int w, int* __restrict__ S) {
+// This thread's share of min_p floor(u(p)) - p over an axis of n samples shifted by s (256 threads).  The
+// shuffle tree and part[4] stay written out in rigid_base and rigid_tail: inside this helper, in any form,
+// they changed both kernels' code.
+__device__ __forceinline__ int rigid_min_offset(float s, int n) {
 #pragma clang fp contract(off)
-  const int f = blockIdx.x, axis = blockIdx.y;
-  const int n = axis == 0 ? h : w;
-  const float s = shifts[2 * f + axis];
   // clamp the (finite) offset so absurd shifts cannot overflow
   const float lim = 3.0f * (float)n + 16.f;
   int di = 0x7fffffff;
@@ -48,6 +45,17 @@ __global__ __launch_bounds__(256) void rigid_base(const float* __restrict__ shif
     const float d = floorf(u) - (float)p;
     di = min(di, (int)fminf(fmaxf(d, -lim), lim));
   }
+  return di;
+}
+
+// pass 0: S[f][axis] = min_p floor(u(p)) - p.  One workgroup per (frame, axis): no atomics,
+// no pre-set of S (80 words fought over by 1280 workgroups cost 20 us in atomics alone).
+__global__ __launch_bounds__(256) void rigid_base(const float* __restrict__ shifts, int nframes, int h,
+                                                  int w, int* __restrict__ S) {
+#pragma clang fp contract(off)
+  const int f = blockIdx.x, axis = blockIdx.y;
+  const int n = axis == 0 ? h : w;
+  int di = rigid_min_offset(shifts[2 * f + axis], n);
   for (int off = 32; off > 0; off >>= 1) di = min(di, __shfl_xor(di, off));
   __shared__ int part[4];
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = di;
@@ -118,13 +126,7 @@ __global__ __launch_bounds__(256) void rigid_tail(const float* __restrict__ shif
     shifts_px[2 * f + axis] = s;
   }
   const int n = axis == 0 ? h : w;
-  const float lim = 3.0f * (float)n + 16.f;
-  int di = 0x7fffffff;
-  for (int p = threadIdx.x; p < n; p += 256) {
-    const float u = grid_chain((float)p + s, (float)n);
-    const float d = floorf(u) - (float)p;
-    di = min(di, (int)fminf(fmaxf(d, -lim), lim));
-  }
+  int di = rigid_min_offset(s, n);
   for (int off = 32; off > 0; off >>= 1) di = min(di, __shfl_xor(di, off));
   __shared__ int part[4];
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = di;
@@ -330,11 +332,43 @@ __device__ __forceinline__ float rigid_dot5(float a0, float b0, float a1, float 
   return __builtin_fmaf(a4, b4, r);
 }
 
-template <bool WRITE_FRAMES, bool WRITE_SUM, bool FULL>
-__device__ __forceinline__ void rigid_strip_dma(const RigidArgs& a, const float4* wrow, int f,
-                                                int y0, int x0, float wyv,
-                                                const float (&wx)[5][4],
-                                                float (&acc)[RIGID_ROWS][4]) {
+#define RDH_QH (RIGID_DMA_WX * 32 + 1)  // 16-byte units (8 samples) per tile row
+__device__ __forceinline__ float rh_lo(unsigned v) {
+  return (float)__builtin_bit_cast(_Float16, (unsigned short)(v & 0xffffu));
+}
+__device__ __forceinline__ float rh_hi(unsigned v) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(v >> 16)); }
+
+
+// How window row rr in LDS becomes the lane's 8 samples e[0..7]: all that the two storages' strips differ in
+struct RowF32 {
+  const float4* wrow;  // the lane's first quad
+  __device__ __forceinline__ void operator()(int rr, float (&e)[8]) const {
+    const float4 q0 = wrow[rr * RD_QUADS], q1 = wrow[rr * RD_QUADS + 1];
+    e[0] = q0.x; e[1] = q0.y; e[2] = q0.z; e[3] = q0.w;
+    e[4] = q1.x; e[5] = q1.y; e[6] = q1.z; e[7] = q1.w;
+  }
+};
+template <int P>  // parity of the window's first column
+struct RowHalf {
+  const uint2* wrow;  // the lane's first 8-byte unit (4 samples)
+  __device__ __forceinline__ void operator()(int rr, float (&e)[8]) const {
+    constexpr int UNITS8 = 2 * RDH_QH;  // 8-byte units per tile row
+    const uint2 u0 = wrow[rr * UNITS8], u1 = wrow[rr * UNITS8 + 1];
+    if constexpr (P == 0) {
+      e[0] = rh_lo(u0.x); e[1] = rh_hi(u0.x); e[2] = rh_lo(u0.y); e[3] = rh_hi(u0.y);
+      e[4] = rh_lo(u1.x); e[5] = rh_hi(u1.x); e[6] = rh_lo(u1.y); e[7] = rh_hi(u1.y);
+    } else {
+      const unsigned u2x = reinterpret_cast<const unsigned*>(wrow + rr * UNITS8 + 2)[0];
+      e[0] = rh_hi(u0.x); e[1] = rh_lo(u0.y); e[2] = rh_hi(u0.y); e[3] = rh_lo(u1.x);
+      e[4] = rh_hi(u1.x); e[5] = rh_lo(u1.y); e[6] = rh_hi(u1.y); e[7] = rh_lo(u2x);
+    }
+  }
+};
+
+// NT: frames leave by rigid_store4 (non-temporal; the fp32 kernel, measured there), else by a plain 16-byte store
+template <bool WRITE_FRAMES, bool WRITE_SUM, bool FULL, bool NT, class Row>
+__device__ __forceinline__ void rigid_strip(const RigidArgs& a, const Row row, int f, int y0, int x0, float wyv,
+                                            const float (&wx)[5][4], float (&acc)[RIGID_ROWS][4]) {
   const int h = a.h, w = a.w;
   // FULL: the whole tile lies inside the image -> no per-row predicates, the strip is
   // one basic block and the scheduler can run the LDS reads ahead of the arithmetic
@@ -343,8 +377,8 @@ __device__ __forceinline__ void rigid_strip_dma(const RigidArgs& a, const float4
 #pragma unroll
   for (int rr = 0; rr < RIGID_ROWS + 4; ++rr) {
     if ((rr % RIGID_SB) == 0) __builtin_amdgcn_sched_barrier(0);
-    const float4 q0 = wrow[rr * RD_QUADS], q1 = wrow[rr * RD_QUADS + 1];
-    const float e[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+    float e[8];
+    row(rr, e);
     float* Hn = H[rr % 5];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
@@ -361,7 +395,10 @@ __device__ __forceinline__ void rigid_strip_dma(const RigidArgs& a, const float4
         o[k] = rigid_dot5(wy[0], H[(ro + 0) % 5][k], wy[1], H[(ro + 1) % 5][k], wy[2], H[(ro + 2) % 5][k], wy[3],
                           H[(ro + 3) % 5][k], wy[4], H[(ro + 4) % 5][k]);
       if (FULL || (y0 + ro < h && x0 < w)) {
-        if (WRITE_FRAMES) rigid_store4(orow + (int64_t)ro * w, o[0], o[1], o[2], o[3]);
+        if (WRITE_FRAMES) {
+          if (NT) rigid_store4(orow + (int64_t)ro * w, o[0], o[1], o[2], o[3]);
+          else *reinterpret_cast<float4*>(orow + (int64_t)ro * w) = make_float4(o[0], o[1], o[2], o[3]);
+        }
         if (WRITE_SUM) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) acc[ro][k] += o[k];
@@ -450,35 +487,23 @@ void warp_rigid_dma(RigidArgs a) {
 
   float wx[5][4];
   float wyv = 0.f;
-  auto load_weights = [&](int f, float (&W5)[5][4], float& Wv) {
-    Wv = 0.f;
-    const int64_t idx = (int64_t)y0 * 5 + lane;
-    if (lane < 5 * RIGID_ROWS && idx < (int64_t)h * 5) Wv = a.Wy[(int64_t)f * 5 * h + idx];
-    const float* Wx = a.Wx + (int64_t)f * 5 * w + x0;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (x0 < w) t = *reinterpret_cast<const float4*>(Wx + (int64_t)j * w);
-      W5[j][0] = t.x; W5[j][1] = t.y; W5[j][2] = t.z; W5[j][3] = t.w;
-    }
-  };
   const int strip = (wvy * RIGID_ROWS) * QUADS + wvx * RIGID_LANES + lane;  // this lane's first quad
 
-  load_weights(f_lo, wx, wyv);
+  rigid_load_weights(a, f_lo, y0, x0, lane, wx, wyv);
   dma(f_lo, b0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (patch(f_lo, b0)) __syncthreads();
   for (int f = f_lo; f < f_hi; ++f) {
     const float4* t = b0 + strip;
-    if (full_tile) rigid_strip_dma<WRITE_FRAMES, WRITE_SUM, true>(a, t, f, y0, x0, wyv, wx, acc);
-    else rigid_strip_dma<WRITE_FRAMES, WRITE_SUM, false>(a, t, f, y0, x0, wyv, wx, acc);
+    if (full_tile) rigid_strip<WRITE_FRAMES, WRITE_SUM, true, true>(a, RowF32{t}, f, y0, x0, wyv, wx, acc);
+    else rigid_strip<WRITE_FRAMES, WRITE_SUM, false, true>(a, RowF32{t}, f, y0, x0, wyv, wx, acc);
     if (f + 1 < f_hi) {
       // single buffer, several workgroups per CU: other workgroups cover this one's latency,
       // so nothing is double-buffered here (registers are the scarce resource)
       __syncthreads();  // everyone must be done reading before the tile is refilled
       dma(f + 1, b0);
-      load_weights(f + 1, wx, wyv);
+      rigid_load_weights(a, f + 1, y0, x0, lane, wx, wyv);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (patch(f + 1, b0)) __syncthreads();
@@ -512,59 +537,6 @@ void warp_rigid_dma(RigidArgs a) {
 // strip bodies with compile-time sample positions: a lane's 8-sample window is the halfs
 // [4 L + p, 4 L + p + 8) of the tile row = two (p = 0) or three (p = 1) aligned ds_read_b64.
 // Tile rows hold RDH_QH = 32 RIGID_DMA_WX + 1 units of 8 samples.  Requires w % 8 == 0 and 16-byte aligned frames.
-#define RDH_QH (RIGID_DMA_WX * 32 + 1)  // 16-byte units (8 samples) per tile row
-__device__ __forceinline__ float rh_lo(unsigned v) {
-  return (float)__builtin_bit_cast(_Float16, (unsigned short)(v & 0xffffu));
-}
-__device__ __forceinline__ float rh_hi(unsigned v) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(v >> 16)); }
-
-template <bool WRITE_FRAMES, bool WRITE_SUM, bool FULL, int P>
-__device__ __forceinline__ void rigid_strip_half(const RigidArgs& a, const uint2* wrow, int f, int y0, int x0,
-                                                 float wyv, const float (&wx)[5][4],
-                                                 float (&acc)[RIGID_ROWS][4]) {
-  const int h = a.h, w = a.w;
-  float* orow = WRITE_FRAMES ? a.out_frames + (int64_t)f * h * w + (int64_t)y0 * w + x0 : nullptr;
-  float H[5][4];
-#pragma unroll
-  for (int rr = 0; rr < RIGID_ROWS + 4; ++rr) {
-    constexpr int UNITS8 = 2 * RDH_QH;  // 8-byte units per tile row
-    if ((rr % RIGID_SB) == 0) __builtin_amdgcn_sched_barrier(0);
-    const uint2 u0 = wrow[rr * UNITS8], u1 = wrow[rr * UNITS8 + 1];
-    float e[8];
-    if constexpr (P == 0) {
-      e[0] = rh_lo(u0.x); e[1] = rh_hi(u0.x); e[2] = rh_lo(u0.y); e[3] = rh_hi(u0.y);
-      e[4] = rh_lo(u1.x); e[5] = rh_hi(u1.x); e[6] = rh_lo(u1.y); e[7] = rh_hi(u1.y);
-    } else {
-      const unsigned u2x = reinterpret_cast<const unsigned*>(wrow + rr * UNITS8 + 2)[0];
-      e[0] = rh_hi(u0.x); e[1] = rh_lo(u0.y); e[2] = rh_hi(u0.y); e[3] = rh_lo(u1.x);
-      e[4] = rh_hi(u1.x); e[5] = rh_lo(u1.y); e[6] = rh_hi(u1.y); e[7] = rh_lo(u2x);
-    }
-    float* Hn = H[rr % 5];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      Hn[k] = rigid_dot5(wx[0][k], e[k], wx[1][k], e[k + 1], wx[2][k], e[k + 2], wx[3][k], e[k + 3], wx[4][k], e[k + 4]);
-    if (rr >= 4) {
-      const int ro = rr - 4;
-      float wy[5];
-#pragma unroll
-      for (int i = 0; i < 5; ++i)
-        wy[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wyv), ro * 5 + i));
-      float o[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        o[k] = rigid_dot5(wy[0], H[(ro + 0) % 5][k], wy[1], H[(ro + 1) % 5][k], wy[2], H[(ro + 2) % 5][k], wy[3],
-                          H[(ro + 3) % 5][k], wy[4], H[(ro + 4) % 5][k]);
-      if (FULL || (y0 + ro < h && x0 < w)) {
-        if (WRITE_FRAMES) *reinterpret_cast<float4*>(orow + (int64_t)ro * w) = make_float4(o[0], o[1], o[2], o[3]);
-        if (WRITE_SUM) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) acc[ro][k] += o[k];
-        }
-      }
-    }
-  }
-}
-
 template <bool WRITE_FRAMES, bool WRITE_SUM>
 __global__ __launch_bounds__(RIGID_LANES* RIGID_DMA_WX* RIGID_DMA_WY, RIGID_DMA_MINW)
 void warp_rigid_dma_h(RigidArgs a) {
@@ -641,6 +613,7 @@ void warp_rigid_dma_h(RigidArgs a) {
 
   float wx[5][4];
   float wyv = 0.f;
+  // rigid_load_weights, written out: the shared function changed three of this kernel's four instantiations
   auto load_weights = [&](int f) {
     wyv = 0.f;
     const int64_t idx = (int64_t)y0 * 5 + lane;
@@ -664,11 +637,11 @@ void warp_rigid_dma_h(RigidArgs a) {
   for (int f = f_lo; f < f_hi; ++f) {
     const int par = __builtin_amdgcn_readfirstlane((xt + a.S[2 * f + 1] - 1) & 1);
     if (par) {
-      if (full_tile) rigid_strip_half<WRITE_FRAMES, WRITE_SUM, true, 1>(a, strip, f, y0, x0, wyv, wx, acc);
-      else rigid_strip_half<WRITE_FRAMES, WRITE_SUM, false, 1>(a, strip, f, y0, x0, wyv, wx, acc);
+      if (full_tile) rigid_strip<WRITE_FRAMES, WRITE_SUM, true, false>(a, RowHalf<1>{strip}, f, y0, x0, wyv, wx, acc);
+      else rigid_strip<WRITE_FRAMES, WRITE_SUM, false, false>(a, RowHalf<1>{strip}, f, y0, x0, wyv, wx, acc);
     } else {
-      if (full_tile) rigid_strip_half<WRITE_FRAMES, WRITE_SUM, true, 0>(a, strip, f, y0, x0, wyv, wx, acc);
-      else rigid_strip_half<WRITE_FRAMES, WRITE_SUM, false, 0>(a, strip, f, y0, x0, wyv, wx, acc);
+      if (full_tile) rigid_strip<WRITE_FRAMES, WRITE_SUM, true, false>(a, RowHalf<0>{strip}, f, y0, x0, wyv, wx, acc);
+      else rigid_strip<WRITE_FRAMES, WRITE_SUM, false, false>(a, RowHalf<0>{strip}, f, y0, x0, wyv, wx, acc);
     }
     if (f + 1 < f_hi) {
       __syncthreads();  // everyone must be done reading before the tile is refilled
@@ -705,40 +678,29 @@ void mc_rigid_tables_launch(const float* shifts_px, int nframes, int h, int w, c
 
 extern "C" {
 
-// phase 0: weight tables + resampling; 1: tables only; 2: resampling only, the
-// tables of an earlier phase-1 call with the same arguments are in `scratch`
-int mc_warp_rigid_phase_t(const void* frames_any, int storage, int nframes, int h, int w, const float* shifts_px,
+// phase: see rigid_check_args (warp_common.h)
+int mc_warp_rigid_phase_t(const void* frames, int storage, int nframes, int h, int w, const float* shifts_px,
                           float* scratch, float* out_frames, float* out_sum, int phase, void* stream) {
-  const float* frames = static_cast<const float*>(frames_any);
   if (storage != MC_STORE_F32 && storage != MC_STORE_F16) return MC_ERR_UNSUPPORTED;
   // fp16 frames: only the LDS-DMA kernel's 512 x 32 geometry, rows of whole 8-sample units
-  if (storage == MC_STORE_F16 && ((w % 8) != 0 || (((uintptr_t)frames_any) & 15) ||
+  if (storage == MC_STORE_F16 && ((w % 8) != 0 || (((uintptr_t)frames) & 15) ||
                                   (out_frames && (((uintptr_t)out_frames) & 15))))
     return MC_ERR_UNSUPPORTED;
-  if (!frames || !shifts_px || !scratch || (phase != 1 && !out_frames && !out_sum)) return MC_ERR_ARG;  // phase 1 writes no image
-  if (nframes < 1 || h < 2 || w < 2 || (((uintptr_t)scratch) & 15) || phase < 0 || phase > 2) return MC_ERR_ARG;
+  if (const int e = rigid_check_args(frames, shifts_px, scratch, out_frames, out_sum, nframes, h, w, phase)) return e;
   hipStream_t s = (hipStream_t)stream;
   const RigidTables t = rigid_tables_layout(scratch, nframes, h, w);
-  if (phase != 2) {
-    mc_rigid_tables_launch(shifts_px, nframes, h, w, t, s);
-    if (phase == 1) return mc_check_launch();
-  }
-  RigidArgs a;
-  a.frames = frames; a.nframes = nframes; a.h = h; a.w = w; a.S = t.S; a.Wy = t.Wy; a.Wx = t.Wx;
-  a.out_frames = out_frames; a.out_sum = out_sum;
+  if (rigid_phase_tables(phase, shifts_px, nframes, h, w, t, s)) return mc_check_launch();
   // the LDS-DMA kernels' 512 x 32 tiles (fp16 frames have no other kernel), else warp_rigid's 256 x 32
   const bool half = storage == MC_STORE_F16;
   const bool dma_ok = half || ((w % 4 == 0) && ((((uintptr_t)frames) & 15) == 0) &&
                                (!out_frames || ((((uintptr_t)out_frames) & 15) == 0)));
   const int WX = dma_ok ? RIGID_DMA_WX : 1, WY = dma_ok ? RIGID_DMA_WY : RIGID_WAVES;
-  a.tiles_x = (w + RIGID_LANES * 4 * WX - 1) / (RIGID_LANES * 4 * WX);
-  a.tiles_y = (h + WY * RIGID_ROWS - 1) / (WY * RIGID_ROWS);
   // Without the fused sum every frame is its own block: blocks are dispatched frame-major, so the
   // resident ones always work on neighbouring tiles of ONE frame and halo rows / shared 128-byte
   // lines hit in L2 (FETCH_SIZE 2.76 GB for 2.68 GB of frames).  With the sum a block keeps its
   // tile's partial sums in registers over all frames; blocks drift apart in time and the same
   // halos miss (3.7 GB) -- measured 0.97 ms vs 1.28 ms at 40 x 4096^2.
-  a.frames_in_grid = out_sum ? 0 : 1;
+  const RigidArgs a = rigid_args(frames, nframes, h, w, t, out_frames, out_sum, WX, WY, out_sum ? 0 : 1);
   const dim3 grid(a.tiles_x * a.tiles_y, a.frames_in_grid ? (nframes + a.frames_in_grid - 1) / a.frames_in_grid : 1),
       block(RIGID_LANES, WX * WY);
   mc_pick_outputs(out_frames != nullptr, out_sum != nullptr, [&](auto F, auto S) {

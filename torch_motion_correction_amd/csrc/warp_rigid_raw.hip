@@ -309,20 +309,8 @@ __global__ __launch_bounds__(RIGID_LANES * 8, 2) void warp_rigid_raw(RigidRawArg
 
   float wx[5][4], wxn[5][4];
   float wyv = 0.f, wyvn = 0.f;
-  auto load_weights = [&](int f, float (&W5)[5][4], float& Wv) {
-    Wv = 0.f;
-    const int64_t idx = (int64_t)y0 * 5 + lane;
-    if (lane < 5 * RIGID_ROWS && idx < (int64_t)h * 5) Wv = a.Wy[(int64_t)f * 5 * h + idx];
-    const float* Wx = a.Wx + (int64_t)f * 5 * w + x0;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (x0 < w) t = *reinterpret_cast<const float4*>(Wx + (int64_t)j * w);
-      W5[j][0] = t.x; W5[j][1] = t.y; W5[j][2] = t.z; W5[j][3] = t.w;
-    }
-  };
 
-  load_weights(0, wx, wyv);
+  rigid_load_weights(a, 0, y0, x0, lane, wx, wyv);
   dma(0, wb0);
   cache_load(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -332,7 +320,7 @@ __global__ __launch_bounds__(RIGID_LANES * 8, 2) void warp_rigid_raw(RigidRawArg
   for (int f = 0; f < a.nframes; ++f) {
     if (NBUF == 2 && f + 1 < a.nframes) {
       dma(f + 1, cur ? wb0 : wb1);  // lands under this frame's arithmetic
-      load_weights(f + 1, wxn, wyvn);
+      rigid_load_weights(a, f + 1, y0, x0, lane, wxn, wyvn);
     }
     if (!cache_covers(f)) {  // the same frames for every wave of the tile: a rendezvous, then the re-load
       __syncthreads();       // everyone has finished the frames that used the old position
@@ -354,7 +342,7 @@ __global__ __launch_bounds__(RIGID_LANES * 8, 2) void warp_rigid_raw(RigidRawArg
       if constexpr (NBUF == 1) {
         rr_wave_sync();  // this wave's reads of the window are done (in-order DS queue)
         dma(f + 1, wb0);
-        load_weights(f + 1, wx, wyv);
+        rigid_load_weights(a, f + 1, y0, x0, lane, wx, wyv);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         patch(f + 1, wb0);
       } else {
@@ -450,22 +438,15 @@ static int warp_rigid_raw_impl(const void* raw, int storage, const float* gain, 
                                int w, const float* shifts_px, float* scratch, float* out_frames, float* out_sum,
                                int phase, bool accumulate, void* stream) {
   if (storage != MC_STORE_U8 && storage != MC_STORE_I16) return MC_ERR_UNSUPPORTED;
-  if (!raw || !gain || !mu || !shifts_px || !scratch || (phase != 1 && !out_frames && !out_sum)) return MC_ERR_ARG;
-  if (nframes < 1 || h < 2 || w < 2 || (((uintptr_t)scratch) & 15) || phase < 0 || phase > 2) return MC_ERR_ARG;
+  if (!gain || !mu) return MC_ERR_ARG;
+  if (const int e = rigid_check_args(raw, shifts_px, scratch, out_frames, out_sum, nframes, h, w, phase)) return e;
   if ((w % 4) || (((uintptr_t)raw) & 15) || (((uintptr_t)gain) & 15) || (out_frames && (((uintptr_t)out_frames) & 15)) ||
       w < 16 || nframes > RR_PAR_MAX)
     return MC_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const RigidTables t = rigid_tables_layout(scratch, nframes, h, w);
-  if (phase != 2) {
-    mc_rigid_tables_launch(shifts_px, nframes, h, w, t, s);
-    if (phase == 1) return mc_check_launch();
-  }
-  RigidRawArgs ra;
-  ra.r.frames = static_cast<const float*>(raw); ra.r.nframes = nframes; ra.r.h = h; ra.r.w = w;
-  ra.r.S = t.S; ra.r.Wy = t.Wy; ra.r.Wx = t.Wx; ra.r.out_frames = out_frames; ra.r.out_sum = out_sum;
-  ra.r.tiles_x = (w + 511) / 512; ra.r.tiles_y = (h + 31) / 32; ra.r.frames_in_grid = 0;
-  ra.gain = gain; ra.mu = mu;
+  if (rigid_phase_tables(phase, shifts_px, nframes, h, w, t, s)) return mc_check_launch();
+  const RigidRawArgs ra = {rigid_args(raw, nframes, h, w, t, out_frames, out_sum, 2, 4, 0), gain, mu};  // 2 x 4 waves: 512 x 32
   const dim3 grid(ra.r.tiles_x * ra.r.tiles_y), block(RIGID_LANES, 8);
   mc_pick(storage == MC_STORE_I16, [&](auto I16) {
     mc_pick_outputs_accum(out_frames != nullptr, out_sum != nullptr, accumulate, [&](auto F, auto S, auto A) {
