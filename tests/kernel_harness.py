@@ -3,8 +3,10 @@ which entry points of libmcorr ran (Recorder, `calls`), what the header says of 
 them so (header_signature, assert_entry_point), a host program built and run under the sanitizers as a child process
 (run_host_program), that nothing was written outside an output buffer (nan_buffer, assert_guards, nan_empty; byte_buffer, assert_byte_guards for the
 byte-moving kernels), the inputs (float_stack, raw_movie, gain, raw_setup), the worst error over bound per
-output family (ratios_fixture, worse) and the engine's test switches (`switches`).  tests/test_kernel_harness_host.py
-pins every one of them on the CPU.
+output family (ratios_fixture, worse), the engine's test switches (`switches`), the delayed-producer run of
+tests/test_stream_order.py (gated_run and its tools) and what tests/test_input_contract.py holds a route's inputs to
+(relocated, twins, snapshot, assert_inputs_unchanged).  tests/test_kernel_harness_host.py pins every one of them on
+the CPU.
 
 A test module takes a fixture with `from kernel_harness import calls  # noqa: F401`."""
 
@@ -457,27 +459,81 @@ def _holds_tensor(v):
     return False
 
 
-def poisoned_twins(inputs):
-    """{name: input} -> ({name: poisoned twin}, [(twin tensor, true tensor), ...]): a tensor's twin is poisoned(); an
-    object's twin is a shallow copy whose tensor attributes are poisoned twins (everything else is shared)."""
+def _has_tensors(obj):
+    """A tensor, or an object that may hold tensors as attributes; a scalar, a tuple, a string, None are not."""
+    return obj is not None and (isinstance(obj, torch.Tensor) or hasattr(obj, "__dict__"))
+
+
+def twins(inputs, fn):
+    """{name: input} -> ({name: twin}, [(twin tensor, true tensor), ...]): a tensor's twin is fn(tensor); an object's
+    twin is a shallow copy whose tensor attributes (_tensor_slots) are fn of the true ones (everything else is
+    shared); a scalar, a tuple, a string, None is passed through."""
     import copy
 
-    twins, pairs = {}, []
+    out, pairs = {}, []
     for name, obj in inputs.items():
-        if obj is None or not (isinstance(obj, torch.Tensor) or hasattr(obj, "__dict__")):
-            twins[name] = obj  # a scalar, a tuple, a string: passed through
+        if not _has_tensors(obj):
+            out[name] = obj
             continue
         if isinstance(obj, torch.Tensor):
-            twins[name] = poisoned(obj)
-            pairs.append((twins[name], obj))
+            out[name] = fn(obj)
+            pairs.append((out[name], obj))
             continue
         twin = copy.copy(obj)
         for _, k in _tensor_slots(obj):
             true = getattr(obj, k)
-            setattr(twin, k, poisoned(true))
+            setattr(twin, k, fn(true))
             pairs.append((getattr(twin, k), true))
-        twins[name] = twin
-    return twins, pairs
+        out[name] = twin
+    return out, pairs
+
+
+def poisoned_twins(inputs):
+    """twins() with poisoned(): what gated_run copies the true inputs over behind the gate."""
+    return twins(inputs, poisoned)
+
+
+def relocated(x, lead_bytes=16):
+    """A copy of the tensor `x` (any dtype narrower than 16 bytes, any device) that starts ONE ELEMENT past a 16-byte
+    boundary of a larger allocation: contiguous, equal to `x`, data_ptr() % 16 == element_size().  In front of it lie
+    `lead_bytes` (whole 16-byte pieces, at least one) and the one element, behind it the rest of its last piece and
+    one whole piece more, so a kernel that rounds its pointer down or reads a whole last piece stays inside the
+    allocation.  The padding is all-ones bytes: NaN for a floating-point reader, -1 / 255 for an integer one.  (An
+    empty tensor has no start to speak of and is cloned.)"""
+    if x.numel() == 0:
+        return x.detach().clone()
+    size = x.element_size()
+    assert lead_bytes >= 16 and lead_bytes % 16 == 0 and size < 16, (lead_bytes, size)
+    start, nbytes = lead_bytes + size, x.numel() * size
+    total = (start + nbytes + 15) // 16 * 16 + 16
+    flat = torch.full((total,), 255, dtype=torch.uint8, device=x.device)
+    assert flat.data_ptr() % 16 == 0
+    view = flat[start:start + nbytes].view(x.dtype).view(x.shape)
+    view.copy_(x.detach())
+    assert view.is_contiguous() and view.data_ptr() % 16 == size and total - start - nbytes >= 16
+    return view
+
+
+def snapshot(inputs):
+    """{name: input} -> [(label, the tensor itself, a copy of it on the CPU), ...] over every tensor of the inputs,
+    those an object holds (_tensor_slots) included; the label is `name` or `name.attribute`."""
+    snap = []
+    for name, obj in inputs.items():
+        if _has_tensors(obj):
+            for holder, k in _tensor_slots(obj):
+                x = obj if holder is None else getattr(obj, k)
+                snap.append((name if holder is None else f"{name}.{k}", x, x.detach().cpu().clone()))
+    return snap
+
+
+def assert_inputs_unchanged(inputs, snap, what):
+    """Every tensor of `inputs` that snapshot() saw holds the bits it held then (the device is read here: the caller
+    synchronises first), and every input still holds the SAME tensors: one rebound on an object fails too."""
+    now = {label: x for label, x, _ in snapshot(inputs)}
+    for label, x, then in snap:
+        if label.split(".")[0] in inputs:
+            assert now.get(label) is x, f"{what}: the input {label} was replaced by another tensor"
+            assert_same_bits(x, then, f"{what}: the input {label} was written to:")
 
 
 class GatedRecorder(Recorder):

@@ -422,6 +422,119 @@ def test_poisoned_twins():
     assert torch.equal(twins["x"], f) and torch.equal(twins["m"].raw, u) and torch.equal(twins["m"].mu, f)
 
 
+@pytest.mark.parametrize("dtype", [torch.uint8, torch.bool, torch.int16, torch.float16, torch.int32, torch.float32,
+                                   torch.int64, torch.float64, torch.complex64], ids=str)
+@pytest.mark.parametrize("shape", [(1,), (3, 5, 7), (2, 16), (0,)], ids=str)
+def test_relocated_starts_one_element_past_a_boundary(dtype, shape):
+    n = 1
+    for s in shape:
+        n *= s
+    x = torch.arange(n) % 120 + 1
+    x = (x % 2 == 1).view(shape) if dtype == torch.bool else x.to(dtype).view(shape)
+    size = x.element_size()
+    if n == 0:  # nothing to start anywhere
+        y = kh.relocated(x)
+        assert y.dtype == dtype and y.shape == x.shape and y is not x
+        return
+    for lead in (16, 48):
+        y = kh.relocated(x, lead)
+        assert y.dtype == dtype and y.shape == x.shape and y.is_contiguous() and y.data_ptr() != x.data_ptr()
+        assert y.data_ptr() % 16 == size  # one element past a boundary, never on one
+        kh.assert_same_bits(y, x, "relocated")
+        whole = y.untyped_storage()
+        first, total = y.data_ptr() - whole.data_ptr(), whole.nbytes()
+        assert whole.data_ptr() % 16 == 0 and first == lead + size  # `lead` bytes of whole pieces, then the element
+        behind = total - first - n * size
+        assert 16 <= behind < 48 and total % 16 == 0  # the rest of the last piece and one whole piece more
+        assert (first + n * size + 15) // 16 * 16 + 16 == total
+        pad = torch.empty(0, dtype=torch.uint8).set_(whole)
+        assert bool((pad[:first] == 255).all()) and bool((pad[first + n * size:] == 255).all())  # all-ones padding
+        if dtype.is_floating_point:  # what a load at the next lower boundary reads first: NaN
+            assert bool(torch.isnan(pad[lead:lead + size].view(dtype)).all())
+    y.view(torch.uint8).zero_() if dtype != torch.bool else y.zero_()
+    assert bool((x.view(torch.uint8) if dtype != torch.bool else x).any())  # a copy: the source is left alone
+    for bad in (0, 8, 20):
+        with pytest.raises(AssertionError):
+            kh.relocated(x, bad)
+
+
+def test_relocated_of_a_view_and_of_a_gradient_leaf():
+    base = torch.arange(24, dtype=torch.float32).view(4, 6)
+    y = kh.relocated(base.t())  # not contiguous: the copy is, in the view's own order
+    assert y.is_contiguous() and torch.equal(y, base.t()) and y.data_ptr() % 16 == 4
+    leaf = base.clone().requires_grad_()
+    assert not kh.relocated(leaf).requires_grad and torch.equal(kh.relocated(leaf), base)
+
+
+def test_twins_applies_fn_to_every_tensor():
+    f = torch.arange(6, dtype=torch.float32).reshape(2, 3)
+    u = torch.tensor([0, 1, 254, 255], dtype=torch.uint8)
+
+    class Movie:
+        pass
+
+    m = Movie()
+    m.raw, m.mu, m.kind, m.nothing = u, f, 0, None
+    inputs = dict(x=f, m=m, n=7, none=None, name="catmull_rom", shape=(2, 3))
+    seen = []
+
+    def fn(x):
+        seen.append(x)
+        return kh.relocated(x)
+
+    out, pairs = kh.twins(inputs, fn)
+    assert [id(x) for x in seen] == [id(f), id(f), id(u)]  # x, then m's attributes in sorted order: mu, raw
+    assert out["n"] == 7 and out["none"] is None and out["name"] == "catmull_rom" and out["shape"] == (2, 3)
+    assert out["m"] is not m and type(out["m"]) is Movie and out["m"].kind == 0 and out["m"].nothing is None
+    assert m.raw is u and m.mu is f  # the true object keeps its tensors
+    assert [(a.data_ptr() % 16, b.data_ptr() == t.data_ptr()) for (a, b), t in zip(pairs, (f, f, u))] == \
+        [(4, True), (4, True), (1, True)]
+    assert pairs[0][0] is out["x"] and pairs[1][0] is out["m"].mu and pairs[2][0] is out["m"].raw
+    assert torch.equal(out["x"], f) and torch.equal(out["m"].raw, u) and torch.equal(out["m"].mu, f)
+    # poisoned_twins is twins with poisoned, pair for pair
+    a, ap = kh.poisoned_twins(inputs)
+    b, bp = kh.twins(inputs, kh.poisoned)
+    assert len(ap) == len(bp) == 3 and all(x[1] is y[1] for x, y in zip(ap, bp))
+    kh.assert_same_bits([x for x, _ in ap], [x for x, _ in bp], "poisoned twins")
+    assert a.keys() == b.keys() == inputs.keys()
+    m.frames = [u]  # the container assertion stays, whatever fn is
+    with pytest.raises(AssertionError, match="Movie.frames holds tensors in a container"):
+        kh.twins(dict(m=m), kh.relocated)
+    assert kh.twins(dict(n=3, s="x"), lambda x: 1 / 0) == (dict(n=3, s="x"), [])  # no tensor: fn is never called
+
+
+def test_snapshot_and_assert_inputs_unchanged():
+    class Movie:
+        pass
+
+    m = Movie()
+    m.raw, m.mu, m.kind = torch.tensor([0, 1, 254, 255], dtype=torch.uint8), torch.tensor([1.0, float("nan")]), 0
+    idx = torch.tensor([3, 1, 2], dtype=torch.int64)
+    z = torch.tensor([0.0, -0.0])
+    inputs = dict(m=m, idx=idx, z=z, n=7, none=None)
+    snap = kh.snapshot(inputs)
+    assert [label for label, _, _ in snap] == ["m.mu", "m.raw", "idx", "z"]
+    assert all(x is y for (_, x, _), y in zip(snap, (m.mu, m.raw, idx, z)))
+    assert all(c.data_ptr() != x.data_ptr() and c.device.type == "cpu" for _, x, c in snap)
+    kh.assert_inputs_unchanged(inputs, snap, "untouched")  # NaN included: bits are compared
+    z[0] = -0.0  # equal as a number, another bit pattern
+    with pytest.raises(AssertionError, match="case: the input z was written to"):
+        kh.assert_inputs_unchanged(inputs, snap, "case")
+    kh.assert_inputs_unchanged({k: v for k, v in inputs.items() if k != "z"}, snap, "the others")  # named inputs only
+    z[0] = 0.0
+    m.raw[2] = 253  # a tensor an object holds
+    with pytest.raises(AssertionError, match=r"case: the input m.raw was written to:\[0\]: 1 of 4 elements differ"):
+        kh.assert_inputs_unchanged(inputs, snap, "case")
+    m.raw[2] = 254
+    kh.assert_inputs_unchanged(inputs, snap, "restored")
+    kept, m.mu = m.mu, m.mu.clone()  # rebound to an equal tensor: no longer the caller's
+    with pytest.raises(AssertionError, match="the input m.mu was replaced by another tensor"):
+        kh.assert_inputs_unchanged(inputs, snap, "case")
+    m.mu = kept
+    kh.assert_inputs_unchanged(inputs, snap, "restored")
+    assert kh.snapshot(dict(n=3, none=None)) == []
+
+
 class _StreamLib:
     def mc_a(self, *a):
         return 0

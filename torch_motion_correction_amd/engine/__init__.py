@@ -161,8 +161,8 @@ from .fourier import (  # noqa: E402
     fourier_crop_supported, fourier_crop_to, fourier_crop_to_shapes, fourier_crop_to_supported, fourier_shift,
     warp_dose_weighted_sum)
 from .raw import (  # noqa: E402
-    _HOT_NONE, _RAW_KINDS, RawMovie, _global_spectra_raw, _local_raw_check, _patch_spectra_raw, _raw_patch_plan,
-    _raw_rows_forward, _warp_hot_correct, check_hot_pixel_threshold, corrected_sums, global_shifts_raw,
+    _HOT_NONE, _RAW_KINDS, RawMovie, _global_spectra_raw, _local_raw_check, _on_boundary, _patch_spectra_raw,
+    _raw_patch_plan, _raw_rows_forward, _warp_hot_correct, check_hot_pixel_threshold, corrected_sums, global_shifts_raw,
     global_shifts_raw_refined, hot_list_capacity, patch_field_raw, raw_fused_supported, warp_dose_weighted_sum_raw,
     warp_field_raw, warp_rigid_raw)
 from .condition import check_group, condition_movie, group_frames_raw, sum_frames  # noqa: E402

@@ -81,7 +81,8 @@ def _full_row_major_ok(h, w):
 
 def _fourier_shift_row_major(img, shifts):
     """fourier_shift on power-of-two frames: rows forward -> (columns forward, phase ramp, columns
-    inverse) in one in-place kernel -> rows inverse, the spectrum row-major throughout."""
+    inverse) in one in-place kernel -> rows inverse, the spectrum row-major throughout.  A stack that starts off an
+    8-byte boundary is restaged a chunk at a time (_rows_forward's rule); the output is a fresh buffer."""
     lib = _lib.load()
     t, h, w = img.shape
     dev = img.device
@@ -94,8 +95,7 @@ def _fourier_shift_row_major(img, shifts):
     shifts = shifts.to(dev, torch.float32).contiguous()
     for a, n in spans:
         off = torch.arange(a, a + n, device=dev, dtype=torch.int64) * (h * w)
-        check(lib.mc_full_rows_forward(ptr(img), ptr(off), w, ptr(S), ptr(tw_row), n, h, w, pitch, st),
-              "mc_full_rows_forward")
+        E._rows_forward(img, a, n, S)
         check(lib.mc_full_cols_shift(ptr(S), ptr(shifts[a:a + n]), ptr(tw_col), 1.0 / (h * w), n, h, w, pitch, st),
               "mc_full_cols_shift")
         check(lib.mc_full_rows_inverse(ptr(S), ptr(out), ptr(off), w, ptr(tw_row), n, h, w, pitch, st),

@@ -35,6 +35,12 @@ def hot_list_capacity(t, h, w):
     return max(4096, (t * h * w) // 4096)
 
 
+def _on_boundary(x, nbytes=16):
+    """`x` where it starts on an `nbytes` boundary (or is None), else one copy of it that does: the staging rule of
+    every tensor the raw kernels read with vector loads."""
+    return x if x is None or x.data_ptr() % nbytes == 0 else x.clone()
+
+
 class RawMovie:
     """A raw detector movie with what the fused kernels need to condition it on the fly
     (c = raw * gain - mu_f, examples/ttMotion.py:90-121, 180-199): the (t,h,w) u8 / i16 stack, the (h,w)
@@ -48,7 +54,10 @@ class RawMovie:
     `hot_keys` (n,) int64 = f*h*w + pixel index, ascending, `hot_rv` (n, 2) = {replacement, value} -- and
     `hot_counts` (t,) int32; the statistics are those of the frames after replacement.  global_shifts_raw and
     warp_rigid_raw apply the list as sparse corrections.  Reading the list's length back costs one small
-    device-to-host copy; more hot pixels than hot_list_capacity() raise McorrUnsupported."""
+    device-to-host copy; more hot pixels than hot_list_capacity() raise McorrUnsupported.
+
+    The raw kernels read `raw` and `gain` in 16-byte units: a movie or a gain that starts off a 16-byte boundary
+    (a view out of a larger buffer) is restaged here, with one copy; neither is ever written."""
 
     def __init__(self, raw, gain, mean_zero=True, hot_pixel_threshold=None):
         thr = check_hot_pixel_threshold(hot_pixel_threshold)
@@ -57,9 +66,9 @@ class RawMovie:
             raise TypeError(f"the fused raw path reads uint8 or int16 frames, got {raw.dtype}")
         t, h, w = raw.shape
         dev = raw.device
-        self.raw = raw.contiguous()
+        self.raw = _on_boundary(raw.contiguous())
         self.gain = (torch.ones((h, w), dtype=torch.float32, device=dev) if gain is None
-                     else gain.detach().to(device=dev, dtype=torch.float32).contiguous())
+                     else _on_boundary(gain.detach().to(device=dev, dtype=torch.float32).contiguous()))
         if tuple(self.gain.shape) != (h, w):
             raise ValueError(f"gain reference {tuple(self.gain.shape)} does not match the frames {(h, w)}")
         self.kind = _RAW_KINDS[raw.dtype]
@@ -99,35 +108,51 @@ class RawMovie:
                                       1 if mean_zero else 0, ptr(hstats), ptr(self.stats), ptr(self.mu),
                                       ptr(self.sub), ptr(self.mean_rstd), st), "mc_raw_hot_finalize")
 
+    def staged(self):
+        """This movie where `raw` and `gain` start on a 16-byte boundary and the {r, v} pairs of `hot_rv` on an
+        8-byte one (every movie the constructor built, and every window of one); else a shallow copy of it with one
+        restaging copy of each of the three that does not (a movie whose tensors were since replaced by views out
+        of larger buffers).  The first line of every route that hands them to a raw kernel: those refuse
+        (MC_ERR_UNSUPPORTED) what is off its boundary."""
+        if self.raw.data_ptr() % 16 == 0 and self.gain.data_ptr() % 16 == 0 and \
+                (self.hot_rv is None or self.hot_rv.data_ptr() % 8 == 0):
+            return self
+        rm = object.__new__(E.RawMovie)
+        rm.__dict__.update(self.__dict__)
+        rm.raw, rm.gain, rm.hot_rv = _on_boundary(self.raw), _on_boundary(self.gain), _on_boundary(self.hot_rv, 8)
+        return rm
+
     def window(self, a, n):
         """Frames [a, a+n) as a RawMovie of their own, without a copy of the movie: views of raw / mu / sub /
         stats / hot_counts, the same gain and mean_rstd, and the hot pixels of those frames -- the slice of the
         sorted `hot_keys` in [a*h*w, (a+n)*h*w), rebased to the window's first frame.  The warps and their hot-pixel
-        corrections (_warp_hot_correct) then work per window unchanged."""
+        corrections (_warp_hot_correct) then work per window unchanged.  (Views of the staged() movie: of this one
+        unless its tensors were replaced by ones off their boundary.)"""
         t, h, w = self.shape
         if not (0 <= a and n >= 1 and a + n <= t):
             raise ValueError(f"frame window [{a}, {a + n}) outside a movie of {t} frames")
         hw = h * w
+        src = self.staged()
         win = object.__new__(E.RawMovie)
-        win.raw = self.raw[a:a + n]
+        win.raw = src.raw[a:a + n]
         # the raw kernels read 16-byte units from the first frame's first byte (h*w % 64 == 0 on every
         # row-major shape, so every window of those is aligned)
         assert win.raw.data_ptr() % 16 == 0, "frame window not 16-byte aligned"
-        win.gain, win.kind, win.shape = self.gain, self.kind, (n, h, w)
-        win.hot_pixel_threshold = self.hot_pixel_threshold
-        win.stats, win.mu, win.sub, win.mean_rstd = self.stats[a:a + n], self.mu[a:a + n], self.sub[a:a + n], self.mean_rstd
+        win.gain, win.kind, win.shape = src.gain, src.kind, (n, h, w)
+        win.hot_pixel_threshold = src.hot_pixel_threshold
+        win.stats, win.mu, win.sub, win.mean_rstd = src.stats[a:a + n], src.mu[a:a + n], src.sub[a:a + n], src.mean_rstd
         win.n_hot = 0
         win.hot_keys = win.hot_rv = win.hot_counts = None
-        if self.hot_counts is not None:
-            win.hot_counts = self.hot_counts[a:a + n]
-        if self.n_hot:
+        if src.hot_counts is not None:
+            win.hot_counts = src.hot_counts[a:a + n]
+        if src.n_hot:
             if getattr(self, "_frame_starts", None) is None:  # one device-to-host copy per movie
                 bounds = torch.arange(t + 1, device=self.raw.device, dtype=torch.int64) * hw
                 self._frame_starts = torch.searchsorted(self.hot_keys, bounds).tolist()
             lo, hi = self._frame_starts[a], self._frame_starts[a + n]
             win.n_hot = hi - lo
-            win.hot_keys = self.hot_keys[lo:hi] - a * hw
-            win.hot_rv = self.hot_rv[lo:hi]
+            win.hot_keys = src.hot_keys[lo:hi] - a * hw
+            win.hot_rv = src.hot_rv[lo:hi]
         return win
 
     def device_tensors(self):
@@ -160,6 +185,7 @@ def global_shifts_raw(rm: E.RawMovie, reference_frame, pixel_spacing, b_factor, 
 def _global_spectra_raw(rm, reference_frame, pixel_spacing, b_factor, frequency_range, after_k1=None):
     """The filtered pruned spectra of global_shifts_raw and their plan -> (S (t, nkx, nky, 2), plan)."""
     lib = _lib.load()
+    rm = rm.staged()
     t, h, w = rm.shape
     dev = rm.raw.device
     _lib.normalize_frame_index(reference_frame, t)  # IndexError before any launch, as the fp32 path
@@ -206,6 +232,7 @@ def warp_rigid_raw(rm: E.RawMovie, lattices, pixel_spacing, want_frames=True, wa
     """``warp(..., rigid=True)`` of the conditioned movie without materialising it (mc_warp_rigid_raw).
     `out_sum`: the (h, w) buffer the sum goes to (implies want_sum); with `accumulate` the sum is added to what it
     holds (mc_warp_rigid_raw_accumulate) -- the hot-pixel corrections of these frames too."""
+    rm = rm.staged()
     t, h, w = rm.shape
     dev = rm.raw.device
     total = E._sum_target(out_sum, want_sum, accumulate, h, w, dev)
@@ -298,6 +325,7 @@ def warp_field_raw(rm: E.RawMovie, lattices, pixel_spacing, want_frames=True, wa
     (mc_warp_frames_raw).  Raises McorrUnsupported outside the raw kernel's shapes.  `out_sum` / `accumulate` as in
     warp_rigid_raw (mc_warp_frames_raw_accumulate)."""
     _local_raw_check(rm)
+    rm = rm.staged()
     t, h, w = rm.shape
     dev = rm.raw.device
     total = E._sum_target(out_sum, want_sum, accumulate, h, w, dev)
