@@ -43,7 +43,7 @@ def wrap(p, n):
 def parabola_offset(v0, v1, v2):
     """estimate_motion_xc.py:465-481: no offset when the outer samples are equal."""
     if v2 != v0:
-        return 0.5 * (v0 - v2) / (v0 - 2 * v1 + v2)
+        return type(v0)(0.5) * (v0 - v2) / (v0 - 2 * v1 + v2)
     return 0.0
 
 
@@ -75,30 +75,58 @@ def integer_shifts(S, shape, ref):
     return s
 
 
-def refine_shifts(S, shape, reference_frame=None, start=None, max_iterations=10, threshold=0.01, damping=None):
+FAULTS = ("own frame", "sign", "reference row", "stale", "window offset")
+
+
+def refine_shifts(S, shape, reference_frame=None, start=None, max_iterations=10, threshold=0.01, damping=None,
+                  residuals=None, dtype=np.float64, fault=None):
     """-> (shifts (t, 2) float64 px, history [max |r| per iteration], offsets [(t, 2) parabola offsets per iteration]).
-    `damping`: the update factor, default (t - 1)/t."""
+    `damping`: the update factor, default (t - 1)/t.  `residuals`: a list that receives r (t, 2) of every iteration.
+    `dtype`: np.float32 runs every statement of the estimator in fp32 (complex64 spectra, numpy's fp32 FFT): the fp32
+    stand-in of the host tests.  `fault`: one of FAULTS, a deliberately wrong chain for the tests that must reject it
+    ('own frame': the current frame stays in its own reference; 'sign': the x residual is applied with the opposite
+    sign; 'reference row': no re-centring; 'stale': the frame after the reference frame is ramped with the shifts of
+    the previous iteration; 'window offset' belongs to the patch form and changes nothing here)."""
+    assert fault is None or fault in FAULTS, fault
+    real = np.dtype(dtype).type
     t = S.shape[0]
     h, w = shape
     ref = frame_index(t // 2 if reference_frame is None else reference_frame, t)
     if t == 1:
         return np.zeros((1, 2)), [], []
-    s = integer_shifts(S, shape, ref) if start is None else np.array(start, dtype=np.float64)
-    fy, fx = np.fft.fftfreq(h)[:, None], np.fft.rfftfreq(w)[None, :]
-    damp = (t - 1) / t if damping is None else damping
+    if real is not np.float64:
+        S = np.asarray(S).astype(np.complex64)
+    s = (integer_shifts(S, shape, ref) if start is None else np.array(start, dtype=np.float64)).astype(real)
+    fy, fx = np.fft.fftfreq(h)[:, None].astype(real), np.fft.rfftfreq(w)[None, :].astype(real)
+    damp = (real(t - 1) / real(t) if real is not np.float64 else (t - 1) / t) if damping is None else damping
     history, offsets = [], []
+    prev = s
     for _ in range(max_iterations):
-        G = S * np.exp(2j * np.pi * (fy[None] * s[:, 0, None, None] + fx[None] * s[:, 1, None, None]))
+        used = s
+        if fault == "stale":
+            used = s.copy()
+            used[(ref + 1) % t] = prev[(ref + 1) % t]
+        prev = s
+        G = S * np.exp(2j * np.pi * (fy[None] * used[:, 0, None, None] + fx[None] * used[:, 1, None, None]))
         A = G.sum(0)
-        r, off = np.zeros((t, 2)), np.zeros((t, 2))
+        r, off = np.zeros((t, 2), dtype=real), np.zeros((t, 2), dtype=real)
         for f in range(t):
-            cc = np.fft.irfft2(np.conj((A - G[f]) / (t - 1)) * G[f], s=shape)
+            REF = A / t if fault == "own frame" else (A - G[f]) / (t - 1)
+            cc = np.fft.irfft2(np.conj(REF) * G[f], s=shape)
+            assert cc.dtype == real
             r[f, 0], r[f, 1], off[f, 0], off[f, 1] = residual(cc)
-        s = s + damp * r
-        s = s - s[ref]
-        s[ref] = 0.0
+        step = damp * r
+        if fault == "sign":
+            step[:, 1] = -step[:, 1]
+        s = s + step
+        if fault != "reference row":
+            s = s - s[ref]
+            s[ref] = 0.0
+        assert s.dtype == real
         history.append(float(np.abs(r).max()))
         offsets.append(off)
+        if residuals is not None:
+            residuals.append(r)
         if history[-1] < threshold:
             break
     return s, history, offsets

@@ -73,30 +73,50 @@ def patch_spectra(movie, pixel_spacing, p, offsets, b_factor=500, frequency_rang
     return S
 
 
-def refine_patches(S, p, start, offsets, reference_frame=None, max_iterations=10, threshold=0.01, damping=None):
+def refine_patches(S, p, start, offsets, reference_frame=None, max_iterations=10, threshold=0.01, damping=None,
+                   dtype=np.float64, fault=None):
     """-> (shifts (t, npatch, 2) float64 px, history [max |r| per iteration], parabola offsets [(t, npatch, 2) per
-    iteration], residuals [(t, npatch, 2) per iteration]).  `damping`: the update factor, default (t - 1)/t."""
+    iteration], residuals [(t, npatch, 2) per iteration]).  `damping`: the update factor, default (t - 1)/t.
+    `dtype`, `fault`: as global_refine_reference.refine_shifts (np.float32: the fp32 stand-in; a deliberately wrong
+    chain); 'window offset' leaves the window offset of patch 0 out of its ramp."""
+    assert fault is None or fault in gr.FAULTS, fault
+    real = np.dtype(dtype).type
     t, npatch = S.shape[:2]
     ref = gr.frame_index(t // 2 if reference_frame is None else reference_frame, t)
-    s = np.array(start, dtype=np.float64).reshape(t, npatch, 2)
+    s = np.array(start, dtype=np.float64).reshape(t, npatch, 2).astype(real)
     if t == 1:
         return np.zeros((1, npatch, 2)), [], [], []
-    o = np.asarray(offsets, dtype=np.float64)
-    fy, fx = np.fft.fftfreq(p)[:, None], np.fft.rfftfreq(p)[None, :]
-    damp = (t - 1) / t if damping is None else damping
+    if real is not np.float64:
+        S = np.asarray(S).astype(np.complex64)
+    o = np.asarray(offsets, dtype=real)
+    fy, fx = np.fft.fftfreq(p)[:, None].astype(real), np.fft.rfftfreq(p)[None, :].astype(real)
+    damp = (real(t - 1) / real(t) if real is not np.float64 else (t - 1) / t) if damping is None else damping
     history, parabola, residuals = [], [], []
+    prev = s
     for _ in range(max_iterations):
-        r, off = np.zeros((t, npatch, 2)), np.zeros((t, npatch, 2))
+        used = s
+        if fault == "stale":
+            used = s.copy()
+            used[(ref + 1) % t] = prev[(ref + 1) % t]
+        prev = s
+        r, off = np.zeros((t, npatch, 2), dtype=real), np.zeros((t, npatch, 2), dtype=real)
         for q in range(npatch):
-            d = s[:, q] - o[:, q]
+            d = used[:, q] if (fault == "window offset" and q == 0) else used[:, q] - o[:, q]
             G = S[:, q] * np.exp(2j * np.pi * (fy[None] * d[:, 0, None, None] + fx[None] * d[:, 1, None, None]))
             A = G.sum(0)
             for f in range(t):
-                cc = np.fft.irfft2(np.conj((A - G[f]) / (t - 1)) * G[f], s=(p, p))
+                REF = A / t if fault == "own frame" else (A - G[f]) / (t - 1)
+                cc = np.fft.irfft2(np.conj(REF) * G[f], s=(p, p))
+                assert cc.dtype == real
                 r[f, q, 0], r[f, q, 1], off[f, q, 0], off[f, q, 1] = gr.residual(cc)
-        s = s + damp * r
-        s = s - s[ref][None]
-        s[ref] = 0.0
+        step = damp * r
+        if fault == "sign":
+            step[..., 1] = -step[..., 1]
+        s = s + step
+        if fault != "reference row":
+            s = s - s[ref][None]
+            s[ref] = 0.0
+        assert s.dtype == real
         history.append(float(np.abs(r).max()))
         parabola.append(off)
         residuals.append(r)

@@ -25,8 +25,8 @@ Cases (shared with tests/test_iteration_reference_host.py):
   LocalMotionProblem on a (3, 384, 384) stack with 256-px patches: ntiles > 1, sums and ncc_grad_sums against the
    float64 definitions applied to its own spectra.
 
-Worst error / bound: this file prints RATIO lines; DESIGN.md section 6 records them (the MI355X column is outstanding
-until a complete run of this file is recorded) next to the fp32 CPU stand-in's ratios of the host test.
+Worst error / bound: this file prints RATIO lines; DESIGN.md section 6 records them, from a complete run on an MI355X,
+next to the fp32 CPU stand-in's ratios of the host test.
 """
 
 import ctypes as C
